@@ -22,6 +22,11 @@ a driver run of --warmup 5 --steps 20 timed 14 ms of GPU work that began 3.5 ms 
 left idle — inside the ~20 ms the clocks take to settle — and hid 40 extra scans in front to
 compensate.  A 1 024-query step is 22 ms: --warmup is exactly what runs, and it is enough.)
 Inputs are in HBM when the timed region starts.  Rank 0 prints ONE JSON line.
+
+A plain N = 1 run sets up, warms up, times the steps and prints the headline line.  Everything else the N = 1 line
+can carry (the other batch sizes, the flagged modes' comparisons with the exact scan, `cpu_baseline` and the oracle
+check of the timed path, `strong_scaling_reference`, the `ingest` and `ivf` legs) runs with --full only.
+--dump-outputs DIR writes what the last timed step returned (scores, ids) as DIR/<name>.npy.
 """
 import argparse
 import ctypes
@@ -89,7 +94,12 @@ def main():
                          "scan, scores within ~1e-3 of the fp32 cosine; recall@k vs the fp32 index is reported")
     ap.add_argument("--prefilter", nargs="?", const="bf16", default=None, choices=["bf16", "int8"],
                     help="flagged mode (not the parity default): bf16 (half the bytes per pass) or int8 (a quarter) candidate "
-                         "scan + exact fp32 re-rank; recall vs the flat scan is reported")
+                         "scan + exact fp32 re-rank; recall vs the flat scan is reported (with --full)")
+    ap.add_argument("--full", action="store_true",
+                    help="N = 1: also run every leg and check outside the headline (other batch sizes, flagged-mode recall, "
+                         "cpu_baseline + timed-path oracle check, strong_scaling_reference, ingest, ivf); off by default")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step returned as DIR/<name>.npy (float32 / float64)")
     args = ap.parse_args()
 
     import numpy as np
@@ -181,13 +191,13 @@ def main():
                         g = (i * LPS + j) % n_batches
                         step_q[j * B:(j + 1) * B].copy_(pool[g * B:(g + 1) * B])
             return search.search_batch(step_q, k, B)
-        out = None
+        outs = []
         for j in range(LPS):   # one step = LPS launch groups of B queries each
             g = (i * LPS + j) % n_batches
             if rank == 0:
                 q_buf.copy_(pool[g * B:(g + 1) * B])
-            out = search.search(q_buf, k)  # scan + merge (N = 1), or the peer-store exchange per group
-        return out
+            outs.append(search.search(q_buf, k))  # scan + merge (N = 1), or the peer-store exchange per group
+        return outs
 
     # EXACTLY --warmup untimed steps, nothing else.
     for i in range(args.warmup):
@@ -210,6 +220,11 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+
+    if args.dump_outputs and rank == 0:
+        # the last timed step's answers as its caller receives them: one (scores, ids) pair per step, or per launch group
+        last_s, last_i = out if batched else (torch.cat([o[0] for o in out]), torch.cat([o[1] for o in out]))
+        dump_outputs(np, args.dump_outputs, {"scores": last_s, "ids": last_i})
 
     ms_per_step = elapsed / args.steps * 1e3
     qps = B * LPS * args.steps / elapsed
@@ -282,7 +297,7 @@ def main():
     # Outside the timed region, single GPU only: the same scan at the other batch sizes SURVEY §8d
     # asks for (B <= 16 runs the NT=1 kernel variant, purely HBM-bound; B = 32 sits at the HBM / fp32-
     # MFMA corner).  Reported next to the headline, never as `value`.
-    if world == 1 and not args.prefilter and not bf16 and rank == 0:
+    if args.full and world == 1 and not args.prefilter and not bf16 and rank == 0:
         others = []
         for Bo in (16, 1):
             if Bo == B:
@@ -305,7 +320,7 @@ def main():
                            "frac": round(ach / HBM_PEAK_GBPS, 4)})
         result["roofline_other_batches"] = others
 
-    if rank == 0 and world == 1 and args.prefilter:
+    if args.full and rank == 0 and world == 1 and args.prefilter:
         # the flagged mode is approximate in principle: measure it against the exact flat scan
         qh = pool[:B].cpu().numpy()
         s_p, i_p = idx.search(qh, k)
@@ -315,7 +330,7 @@ def main():
         result["prefilter_recall_vs_flat"] = float(np.mean([len(set(i_p[r]) & set(i_f[r])) / k for r in range(B)]))
         result["prefilter_scores_bit_identical"] = bool(np.array_equal(s_p[i_p == i_f], s_f[i_p == i_f]))
 
-    if rank == 0 and world == 1 and bf16:
+    if args.full and rank == 0 and world == 1 and bf16:
         # the flagged mode against the parity path: the same first rows as an fp32 index and as a bf16 index
         sample = min(args.cpu_sample_rows, n_local)
         ref = eng.open_index("bench-f32-sample", capacity_rows=sample)
@@ -333,17 +348,17 @@ def main():
         if not args.no_cpu_baseline:
             result.update(cpu_baseline_and_recall(np, torch, eng, ref, pool, args, n_local, dim, B, k))
             result["recall_at_k_note"] = "recall_at_k / max_abs_cosine_err above are the fp32 parity path's on the sample"
-    elif rank == 0 and world == 1 and not args.no_cpu_baseline:
+    elif args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         result.update(cpu_baseline_and_recall(np, torch, eng, idx, pool, args, n_local, dim, B, k))
         if not args.prefilter:
             # the TIMED path's own output: the last launch group of the timed loop (32 queries over ALL rows of the shard)
             # against the oracle's fp64 ranking of the same rows — not a separate launch over a prefix
             g_last = ((args.warmup + args.steps - 1) * LPS + LPS - 1) % n_batches
-            last = (out[0][-B:], out[1][-B:]) if batched else out
+            last = (out[0][-B:], out[1][-B:]) if batched else out[-1]
             result.update(timed_path_check(np, idx, pool[g_last * B:(g_last + 1) * B], last, n_local, k))
 
-    if rank == 0 and world == 1 and not args.no_scale_ref and not bf16 and not args.prefilter and dim == 1024 and B == 32 \
-            and rows_global == 1_000_000:
+    if args.full and rank == 0 and world == 1 and not args.no_scale_ref and not bf16 and not args.prefilter and dim == 1024 \
+            and B == 32 and rows_global == 1_000_000:
         # Outside the timed region: BASELINE configs[3]'s corpus (10 M x 1024 fp32 = 41 GB) on THIS one GPU, the same step
         # (1 024 queries, one engine call).  `bench.py --gpus N` (N > 1) shards exactly this corpus over N ranks ("strong"
         # scaling): its `value` is to be compared with N x THIS number, not with the 1 M-row headline above.
@@ -374,13 +389,13 @@ def main():
         except Exception as e:  # noqa: BLE001 — the reference leg must not take the headline down
             result["strong_scaling_reference"] = {"error": f"{type(e).__name__}: {e}"}
 
-    if rank == 0 and world == 1 and not args.no_ingest and not bf16 and not args.prefilter and dim == 1024:
+    if args.full and rank == 0 and world == 1 and not args.no_ingest and not bf16 and not args.prefilter and dim == 1024:
         # BASELINE configs[2]'s larger half (the "embedding" of "embedding + ANN"): after the timed search region and
         # outside it.  The search index is dropped first so the encoder does not share HBM bandwidth accounting with it.
         eng.synchronize()
         result["ingest"] = ingest_leg(np, torch, local_rank, args.ingest_batches)
 
-    if rank == 0 and world == 1 and not args.no_ivf and not bf16 and not args.prefilter and dim == 1024:
+    if args.full and rank == 0 and world == 1 and not args.no_ivf and not bf16 and not args.prefilter and dim == 1024:
         # BASELINE configs[4] at one GPU's share (12.5 M of the 100 M rows), outside the timed region: the search index is
         # dropped first (the IVF leg holds 51 GB of rows + the IVF's own 51 GB copy)
         eng.synchronize()
@@ -737,7 +752,7 @@ def ivf_mode(np, torch, dist, args, world, rank, local_rank, dev, coll):
     eng.kernel_timing_begin(args.steps * LPS)
     t0 = time.perf_counter()
     for i in range(args.steps):
-        step(args.warmup + i)
+        out = step(args.warmup + i)
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -748,6 +763,8 @@ def ivf_mode(np, torch, dist, args, world, rank, local_rank, dev, coll):
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(np, args.dump_outputs, {"scores": out[0], "ids": out[1]})
     qps = B * LPS * args.steps / elapsed
     # probed rows on THIS shard: the last step's per-group counts (the batch call reports them); one fine-scan launch per step
     per_step = float(scanned_dev.sum().item())
@@ -802,6 +819,29 @@ def ivf_mode(np, torch, dist, args, world, rank, local_rank, dev, coll):
     ivf.close()
     eng.close()
     return result
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(np, out_dir, arrays):
+    """--dump-outputs: every (name, tensor) of `arrays` as out_dir/<name>.npy, floating outputs as float32 and integer ids as
+    float64 (exact below 2^53).  Above 64 MB in all, the same seeded sample of rows is kept of every array, and the sampled
+    row numbers are written as rows.npy."""
+    host = {}
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy()
+        host[name] = a.astype(np.float32 if a.dtype.kind == "f" else np.float64)
+    total = sum(a.nbytes for a in host.values())
+    if total > DUMP_LIMIT_BYTES:
+        n = next(iter(host.values())).shape[0]
+        keep = int(DUMP_LIMIT_BYTES // (total / n + 8))
+        rows = np.sort(np.random.default_rng(0).choice(n, size=keep, replace=False))
+        host = {name: a[rows] for name, a in host.items()}
+        host["rows"] = rows.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in host.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def pmc_traffic(kernel: str, bytes_per_launch: int):

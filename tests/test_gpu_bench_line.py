@@ -1,5 +1,6 @@
-"""bench.py's JSON line, end to end on the GPU box (VERDICT r2 #2a, #4, #5): the N = 1 line carries `roofline`,
-`cpu_baseline` and the `ingest` leg (BASELINE configs[2]'s encoder forward at batch 256 x 512); an N > 1 launch — two
+"""bench.py's JSON line, end to end on the GPU box (VERDICT r2 #2a, #4, #5): the N = 1 line carries `roofline`, and
+with --full `cpu_baseline` and the `ingest` leg (BASELINE configs[2]'s encoder forward at batch 256 x 512); a plain
+N = 1 run carries the headline only and can dump its last step's answers; an N > 1 launch — two
 ranks sharing the test GPU over gloo, the rehearsal mode — defaults to BASELINE configs[3] (the fixed 10 M-row corpus,
 strong scaling) and proves in the line itself who took part and that the merged result is the merge of the shards."""
 import json
@@ -25,7 +26,7 @@ def _line(cmd, env=None, timeout=900):
 
 
 def test_single_gpu_line_has_roofline_cpu_baseline_and_ingest(gpu):
-    j = _line([sys.executable, "bench.py", "--steps", "3", "--warmup", "2", "--cpu-sample-rows", "50000",
+    j = _line([sys.executable, "bench.py", "--full", "--steps", "3", "--warmup", "2", "--cpu-sample-rows", "50000",
                "--cpu-hnsw-rows", "2000", "--ingest-batches", "2", "--ivf-rows", "400000", "--ivf-nlist", "256",
                "--ivf-queries", "256"])
     assert j["n_gpus"] == 1 and j["scaling"] == "weak" and j["dtype"] == "f32" and j["vs_baseline"] is None
@@ -64,6 +65,26 @@ def test_single_gpu_line_has_roofline_cpu_baseline_and_ingest(gpu):
     # cluster structure is what an IVF finds: at every nprobe the clustered corpus recalls more than the iid one
     assert all(c["recall_at_10"] > w["recall_at_10"] for c, w in zip(ivf["clustered"]["sweep"], ivf["iid_worst_case"]["sweep"]))
     assert ivf["clustered"]["sweep"][0]["queries_per_s"] > ivf["clustered"]["flat_queries_per_s_same_shard"]
+
+
+def test_plain_single_gpu_line_is_the_headline_and_dumps_its_last_step(gpu, tmp_path):
+    """Without --full the N = 1 line is the timed steps and nothing else; --dump-outputs writes the last timed step's
+    answers (1 024 queries x top-10), and the same arguments give the same answers."""
+    import numpy as np
+    cmd = [sys.executable, "bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1", "--dump-outputs"]
+    j = _line(cmd + [str(tmp_path / "a")])
+    assert j["steps"] == 3 and j["warmup"] == 1 and j["unit"] == "queries/s" and j["higher_is_better"] is True
+    assert j["dtype"] == "f32" and abs(j["value"] - 1024 * 1e3 / j["ms_per_step"]) <= 1e-3 * j["value"]
+    assert j["roofline"]["launches"] == 3 * 32
+    for key in ("cpu_baseline", "recall_at_k", "timed_path_check", "roofline_other_batches", "strong_scaling_reference",
+                "ingest", "ivf"):
+        assert key not in j, key
+    s, i = np.load(tmp_path / "a" / "scores.npy"), np.load(tmp_path / "a" / "ids.npy")
+    assert s.dtype == np.float32 and i.dtype == np.float64 and s.shape == i.shape == (1024, 10)
+    assert np.all(np.diff(s, axis=1) <= 0) and np.all(np.abs(s) <= 1.0 + 1e-6)
+    assert np.all((i >= 0) & (i < 1_000_000) & (i == np.round(i)))
+    _line(cmd + [str(tmp_path / "b")])
+    assert np.array_equal(np.load(tmp_path / "b" / "scores.npy"), s) and np.array_equal(np.load(tmp_path / "b" / "ids.npy"), i)
 
 
 def test_two_rank_line_defaults_to_configs3_and_proves_itself(gpu):
