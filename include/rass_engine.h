@@ -246,11 +246,27 @@ int rass_index_search_device_batch(rass_index_t* idx, const float* d_queries, in
 #define RASS_PREFILTER_OFF 0
 #define RASS_PREFILTER_BF16 1
 #define RASS_PREFILTER_INT8 2
+/* RASS_PREFILTER_INT8_EXACT (3): certified int8 search — answers are the flat scan's, ids and scores, bit for bit, for every
+ * query with k <= 32.  Per pass of 16 queries: an int8 scan with each query carried as hi + lo int8 vectors keeps the 128 best
+ * candidates, they are re-ranked exactly in fp32, a per-query certificate (DESIGN.md §3 "certified int8 search") proves that no
+ * row outside them can enter the top-k, and the exact fp32 flat scan runs for the queries whose certificate fails.  Every
+ * device search API stays stream-ordered (the fallback reads its query count on the device).  k > 32 takes the exact passes. */
+#define RASS_PREFILTER_INT8_EXACT 3
 int rass_index_set_prefilter(rass_index_t* idx, int enable);
-int rass_index_get_prefilter(const rass_index_t* idx);   /* the mode: 0 / 1 / 2 */
+int rass_index_get_prefilter(const rass_index_t* idx);   /* the mode: 0 / 1 / 2 / 3 */
+/* Mode 3's device counters since the mode was set (searched queries, certified queries, queries that took the fp32
+ * fallback) and the certificate's row maxima R = max |y - s_y y8|, V = max |s_y y8|.  Synchronises the engine's stream. */
+int rass_index_certify_stats(rass_index_t* idx, int64_t* queries, int64_t* certified, int64_t* fallbacks, float* R, float* V);
+/* Mode 3's parity hook for <= 32 device queries: the 128 candidates per query the certificate covers ([nq][128] int8
+ * candidate scores and LOCAL rows, (score desc, row asc), -inf / -1 past the end), tau [nq] (every eligible row outside the
+ * list scores at most tau; -inf: none is outside) and the certificate flags [nq] (1 = certified at this k).  Stream-ordered.
+ * RASS_ERR_UNSUPPORTED unless the index is in mode 3. */
+int rass_index_candidates_exact_device(rass_index_t* idx, const float* d_queries, int nq, int k, const int32_t* d_q_filter,
+                                       float* d_cand_scores, int64_t* d_cand_rows, float* d_tau, int32_t* d_certified);
 /* The candidate lists of the active prefilter mode for <= 32 device queries, BEFORE the exact re-rank: [nq][32] candidate
  * scores (bf16: fp32-accumulated dot of the bf16-rounded operands; int8: as above) and LOCAL rows, (score desc, row asc),
- * -inf / -1 past the end.  Parity hook of the integer path (tests compare it with the oracle bit for bit); stream-ordered. */
+ * -inf / -1 past the end.  Parity hook of the integer path (tests compare it with the oracle bit for bit); stream-ordered.
+ * RASS_ERR_UNSUPPORTED in mode 3 (rass_index_candidates_exact_device). */
 int rass_index_candidates_device(rass_index_t* idx, const float* d_queries, int nq, const int32_t* d_q_filter,
                                  float* d_cand_scores, int64_t* d_cand_rows);
 

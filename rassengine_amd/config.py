@@ -43,9 +43,11 @@ RASS_IVF_DTYPE = os.getenv("RASS_IVF_DTYPE", "f32")            # the IVF's own c
 # Candidate scan of a flat index's searches with k <= 16: "off" (exact fp32 scan, the default), "bf16" (half the bytes per pass)
 # or "int8" (a quarter: per-row-scaled int8 copy); the 32 candidates per query are re-scored exactly in fp32 either way
 # (include/rass_engine.h: rass_index_set_prefilter).  The reference's own index is approximate (HNSW, app/main.py:563-572).
+# "int8_exact": the int8 scan keeps 128 candidates, a per-query certificate proves the exact top-k among them and the fp32
+# scan answers the queries it cannot prove: the flat scan's results bit for bit, for k <= 32.
 RASS_PREFILTER = os.getenv("RASS_PREFILTER", "off").strip().lower() or "off"
-if RASS_PREFILTER not in ("off", "bf16", "int8"):
-    raise ValueError(f"RASS_PREFILTER must be off, bf16 or int8, not {RASS_PREFILTER!r}")
+if RASS_PREFILTER not in ("off", "bf16", "int8", "int8_exact"):
+    raise ValueError(f"RASS_PREFILTER must be off, bf16, int8 or int8_exact, not {RASS_PREFILTER!r}")
 try:
     RASS_IVF_REBUILD_FRACTION = float(os.getenv("RASS_IVF_REBUILD_FRACTION", "0.25"))
 except ValueError:

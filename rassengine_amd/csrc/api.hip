@@ -91,6 +91,7 @@ struct ScanExt {
     const int32_t* d_q_mask = nullptr;
     const float* d_after_s = nullptr;
     const int64_t* d_after_i = nullptr;
+    const int32_t* d_live = nullptr;   // device scalar: 0 = every workgroup exits (the certified mode's fallback)
 };
 
 struct ScratchLayout {
@@ -158,6 +159,9 @@ struct rass_engine {
     // scratch of rass_index_search_device_batch (every launch group's queries, lists and sample bests), grown on demand
     unsigned char* d_batch = nullptr;
     size_t batch_bytes = 0;
+    // workspace of the certified int8 search (prefilter mode 3): one pass of kCertQ queries, grown on demand
+    unsigned char* d_cert = nullptr;
+    size_t cert_bytes = 0;
     // host-API staging
     float* d_qraw = nullptr;        // [32][dim]
     int32_t* d_qfilter = nullptr;   // [32]
@@ -204,6 +208,10 @@ struct rass_index {
     signed char* d_rows_i8 = nullptr;       // tile16i copy (prefilter mode 2), rows of stride_i8 bytes
     float* d_row_scale = nullptr;           // [capacity] max|x| / 127 of every row (prefilter mode 2)
     int64_t stride_i8 = 0;                  // stride rounded up to 512
+    // prefilter mode 3 (certified int8 search): [R, V, Y] as float bits (monotone maxima over every row ever quantised) and
+    // the counters [queries, certified, fallbacks]; allocated when the mode is first set
+    unsigned* d_cert_stats = nullptr;
+    unsigned long long* d_cert_counts = nullptr;
     std::vector<uint8_t> host_deleted;  // tombstone bitmap mirror (host)
     std::mutex mu;
 };
@@ -224,7 +232,7 @@ int index_reserve(rass_index* idx, int64_t need_rows) {
     hipStream_t st = idx->eng->stream;
     const bool want_f32 = idx->dtype == RASS_F32;                  // a bf16 index holds the bf16 slab ONLY
     const bool want_b16 = idx->dtype == RASS_BF16 || idx->prefilter == 1;
-    const bool want_i8 = idx->prefilter == 2;
+    const bool want_i8 = idx->prefilter >= 2;
     const size_t elem = want_f32 ? sizeof(float) : 2;
     void* nmain = nullptr;  // the dtype's own slab
     hipError_t e = hipMalloc(&nmain, (size_t)cap * idx->stride * elem);
@@ -413,6 +421,7 @@ int scan_launch(const float* d_corpus, int64_t n_rows, int64_t stride, const int
         a.q_filter_mask = ext->d_q_mask;
         a.q_after_score = ext->d_after_s;
         a.q_after_id = ext->d_after_i;
+        a.live_nq = ext->d_live;
     }
     if (plan) {
         a.work_tile = plan->work_tile;
@@ -441,7 +450,8 @@ int scan_launch(const float* d_corpus, int64_t n_rows, int64_t stride, const int
         HIP_TRY(hipEventRecord(timing->ev_pool[2 * timing->ev_used + 1], st));
         timing->ev_used += 1;
     }
-    HIP_TRY(rass::launch_merge_topk(part_scores, part_ids, grid, nq, k, d_out_scores, d_out_ids, st, id_map));
+    HIP_TRY(rass::launch_merge_topk(part_scores, part_ids, grid, nq, k, d_out_scores, d_out_ids, st, id_map, 0, 0, nullptr,
+                                    ext ? ext->d_live : nullptr));
     return RASS_OK;
 }
 
@@ -604,6 +614,176 @@ int prefilter_launch(rass_index* idx, const float* d_queries, int nq, const int3
     return RASS_OK;
 }
 
+
+// ---- prefilter mode 3: certified int8 search (DESIGN.md §3 "certified int8 search") ---------------------------------------
+struct CertLayout {
+    size_t q_padded, q8, qinfo, sample, list_s, list_r, list_n, list_floor, cand_rows, rr_s, rr_i, tau, fail_idx, fail_flag, fail_n, fb_q,
+        fb_filter, fb_mask, fb_s, fb_i, hook_s, hook_i, total;
+};
+
+CertLayout cert_layout(int grid, int64_t stride, int64_t stride_i8, int dim) {
+    CertLayout L;
+    size_t off = 0;
+    auto take = [&](size_t bytes) {
+        const size_t o = off;
+        off = (off + bytes + 255) / 256 * 256;
+        return o;
+    };
+    const size_t Q = rass::kCertQ, slots = (size_t)grid * Q * rass::kCertWgCap;
+    L.q_padded = take(4 * Q * stride * sizeof(float));   // x 4: one copy per re-ranked chunk of 32 candidates
+    L.q8 = take(2 * Q * stride_i8);
+    L.qinfo = take(Q * sizeof(rass::CertQInfo));
+    L.sample = take((size_t)rass::kMaxSampleGroups * Q * sizeof(float));
+    L.list_s = take(slots * sizeof(float));
+    L.list_r = take(slots * sizeof(int32_t));
+    L.list_n = take((size_t)grid * Q * sizeof(int32_t));
+    L.list_floor = take((size_t)grid * Q * sizeof(float));
+    L.cand_rows = take(Q * rass::kCertC * sizeof(int64_t));
+    L.rr_s = take(Q * rass::kCertC * sizeof(float));
+    L.rr_i = take(Q * rass::kCertC * sizeof(int64_t));
+    L.tau = take(Q * sizeof(float));
+    L.fail_idx = take(Q * sizeof(int32_t));
+    L.fail_flag = take(Q * sizeof(int32_t));
+    L.fail_n = take(sizeof(int32_t));
+    L.fb_q = take(Q * dim * sizeof(float));
+    L.fb_filter = take(Q * sizeof(int32_t));
+    L.fb_mask = take(Q * sizeof(int32_t));
+    L.fb_s = take(Q * RASS_MAX_K * sizeof(float));
+    L.fb_i = take(Q * RASS_MAX_K * sizeof(int64_t));
+    L.hook_s = take((size_t)RASS_MAX_QBATCH * RASS_MAX_K * sizeof(float));     // the parity hook's own search result
+    L.hook_i = take((size_t)RASS_MAX_QBATCH * RASS_MAX_K * sizeof(int64_t));
+    L.total = off;
+    return L;
+}
+
+// Mode 3, k <= 32: per pass of <= 16 queries — hi + lo int8 queries, the sample floor, the int8 candidate scan, the selection of
+// 128 candidates and tau, their exact re-rank, the certificate, the fp32 flat scan of the failed queries (exits on the device
+// when none failed) and its scatter.  Stream-ordered: the host reads nothing back.  The optional outputs (the parity hook
+// rass_index_candidates_exact_device) are [nq][128] candidates, tau [nq] and the certificate flags [nq].
+int cert_launch(rass_index* idx, const float* d_queries, int nq, const int32_t* d_q_filter, const int32_t* d_q_filter_mask, int k,
+                int64_t id_base, float* d_out_scores, int64_t* d_out_ids, const int32_t* d_row_tag, rass_engine* eng, hipStream_t st,
+                const int64_t* id_map, float* d_cand_s = nullptr, int64_t* d_cand_r = nullptr, float* d_tau = nullptr,
+                int32_t* d_certified = nullptr) {
+    if (nq < 1 || nq > RASS_MAX_QBATCH) return fail(RASS_ERR_INVALID, "nq must be in [1, RASS_MAX_QBATCH]");
+    if (k < 1 || k > RASS_MAX_K) return fail(RASS_ERR_INVALID, "k must be in [1, RASS_MAX_K]");
+    if (d_q_filter_mask && !d_q_filter) return fail(RASS_ERR_INVALID, "a filter mask needs a filter");
+    const int64_t rows = idx->rows.load(std::memory_order_acquire);
+    const int64_t stride = idx->stride;
+    const int dim = idx->dim;
+    const int64_t n_tiles = (rows + 63) / 64;
+    const int grid = (int)std::min<int64_t>(std::max<int64_t>(n_tiles, 1), std::min(eng->n_cus, rass::kMaxGridSel));
+    const CertLayout L = cert_layout(grid, stride, idx->stride_i8, dim);
+    if (eng->cert_bytes < L.total) {
+        HIP_TRY(hipStreamSynchronize(st));   // growth only: the buffer may still be read by an earlier pass
+        if (eng->d_cert) HIP_TRY(hipFree(eng->d_cert));
+        eng->d_cert = nullptr;
+        eng->cert_bytes = 0;
+        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&eng->d_cert), L.total));
+        eng->cert_bytes = L.total;
+    }
+    unsigned char* ws = eng->d_cert;
+    if (!d_out_scores || !d_out_ids) {   // the parity hook: the search's result is not reported
+        d_out_scores = reinterpret_cast<float*>(ws + L.hook_s);
+        d_out_ids = reinterpret_cast<int64_t*>(ws + L.hook_i);
+    }
+    float* q_padded = reinterpret_cast<float*>(ws + L.q_padded);
+    signed char* q8 = reinterpret_cast<signed char*>(ws + L.q8);
+    rass::CertQInfo* qinfo = reinterpret_cast<rass::CertQInfo*>(ws + L.qinfo);
+    int64_t* cand_rows = reinterpret_cast<int64_t*>(ws + L.cand_rows);
+    float* rr_s = reinterpret_cast<float*>(ws + L.rr_s);
+    int64_t* rr_i = reinterpret_cast<int64_t*>(ws + L.rr_i);
+    int32_t* fail_n = reinterpret_cast<int32_t*>(ws + L.fail_n);
+    // the sample floor: the 128th of the per-workgroup maxima of a sample launch over the first S tiles of every workgroup (S grows
+    // with the slab so that the floor keeps the candidates under the selection's capacity); none where every row fits anyway
+    const bool floor_on = grid >= rass::kCertC && rows > rass::kCertSelCap && grid <= rass::kMaxSampleGroups;
+    const int64_t per_wg = n_tiles / std::max(grid, 1);
+    const int S = (int)std::max<int64_t>(1, std::min<int64_t>(8, per_wg / 16));
+    const bool timed = eng->ev_on && (size_t)(2 * eng->ev_used + 1) < eng->ev_pool.size();
+    for (int p0 = 0; p0 < nq; p0 += rass::kCertQ) {
+        const int b = std::min(rass::kCertQ, nq - p0);
+        HIP_TRY(rass::launch_normalize_rows_f32(d_queries + (int64_t)p0 * dim, dim, q_padded, stride, b, dim, st, rass::kCertQ));
+        HIP_TRY(rass::launch_queries_to_i8_hilo(q_padded, q8, qinfo, stride, idx->stride_i8, st));
+        rass::ScanI8CertArgs a;
+        a.corpus = idx->d_rows_i8;
+        a.row_scale = idx->d_row_scale;
+        a.row_tag = d_row_tag;
+        a.q_i8 = q8;
+        a.qinfo = qinfo;
+        a.q_filter = d_q_filter ? d_q_filter + p0 : nullptr;
+        a.q_filter_mask = d_q_filter_mask ? d_q_filter_mask + p0 : nullptr;
+        a.row_stride = idx->stride_i8;
+        a.n_rows = (int)rows;
+        a.nq = b;
+        a.sample_out = nullptr;
+        a.sample_best = nullptr;
+        a.list_s = reinterpret_cast<float*>(ws + L.list_s);
+        a.list_r = reinterpret_cast<int32_t*>(ws + L.list_r);
+        a.list_n = reinterpret_cast<int32_t*>(ws + L.list_n);
+        a.list_floor = reinterpret_cast<float*>(ws + L.list_floor);
+        if (floor_on) {
+            rass::ScanI8CertArgs sa = a;
+            sa.n_rows = (int)std::min<int64_t>(rows, (int64_t)64 * grid * S);
+            sa.sample_out = reinterpret_cast<float*>(ws + L.sample);
+            HIP_TRY(rass::launch_scan_i8_cert(sa, grid, st));
+            a.sample_best = sa.sample_out;
+            a.sample_groups = grid;
+            a.floor_rank = rass::kCertC;
+        }
+        if (timed) HIP_TRY(hipEventRecord(eng->ev_pool[2 * eng->ev_used], st));
+        HIP_TRY(rass::launch_scan_i8_cert(a, grid, st));
+        if (timed) {
+            HIP_TRY(hipEventRecord(eng->ev_pool[2 * eng->ev_used + 1], st));
+            eng->ev_used += 1;
+        }
+        float* tau = d_tau ? d_tau + p0 : reinterpret_cast<float*>(ws + L.tau);
+        HIP_TRY(rass::launch_cert_select(a.list_s, a.list_r, a.list_n, a.list_floor, grid, b, cand_rows,
+                                         d_cand_s ? d_cand_s + (int64_t)p0 * rass::kCertC : nullptr,
+                                         d_cand_r ? d_cand_r + (int64_t)p0 * rass::kCertC : nullptr, tau, st));
+        // the four chunks of 32 candidates in ONE re-rank launch of 64 "queries": chunk c of query q is entry 16 c + q, its
+        // query vector the c-th copy of q_padded
+        for (int ch = 1; ch < rass::kCertC / 32; ++ch)
+            HIP_TRY(hipMemcpyAsync(q_padded + (int64_t)ch * rass::kCertQ * stride, q_padded, (size_t)rass::kCertQ * stride * sizeof(float),
+                                   hipMemcpyDeviceToDevice, st));
+        HIP_TRY(rass::launch_rerank_f32(idx->d_rows, stride, q_padded, cand_rows, (rass::kCertC / 32) * rass::kCertQ, 32, 32,
+                                        id_map ? 0 : id_base, rr_s, rr_i, st, 0, 0, id_map));
+        rass::CertFinishArgs f;
+        f.rr_s = rr_s;
+        f.rr_i = rr_i;
+        f.tau = tau;
+        f.qinfo = qinfo;
+        f.stats = idx->d_cert_stats;
+        f.dim = dim;
+        f.nq = b;
+        f.k = k;
+        f.out_s = d_out_scores + (int64_t)p0 * k;
+        f.out_i = d_out_ids + (int64_t)p0 * k;
+        f.certified = d_certified ? d_certified + p0 : nullptr;
+        f.fail_idx = reinterpret_cast<int32_t*>(ws + L.fail_idx);
+        f.fail_flag = reinterpret_cast<int32_t*>(ws + L.fail_flag);
+        f.fail_n = fail_n;
+        f.q_raw = d_queries + (int64_t)p0 * dim;
+        f.q_filter = a.q_filter;
+        f.q_filter_mask = a.q_filter_mask;
+        f.fb_q = reinterpret_cast<float*>(ws + L.fb_q);
+        f.fb_filter = reinterpret_cast<int32_t*>(ws + L.fb_filter);
+        f.fb_mask = reinterpret_cast<int32_t*>(ws + L.fb_mask);
+        f.counters = idx->d_cert_counts;
+        HIP_TRY(rass::launch_cert_finish(f, st));
+        // the exact fp32 flat scan of the failed queries (compacted to the front): its workgroups exit when none failed
+        ScanExt ext;
+        ext.d_q_mask = d_q_filter_mask ? f.fb_mask : nullptr;
+        ext.d_live = fail_n;
+        float* fb_s = reinterpret_cast<float*>(ws + L.fb_s);
+        int64_t* fb_i = reinterpret_cast<int64_t*>(ws + L.fb_i);
+        const int rc = scan_launch(idx->d_rows, rows, stride, d_row_tag, f.fb_q, dim, dim, b, d_q_filter ? f.fb_filter : nullptr, k,
+                                   id_map ? 0 : id_base, fb_s, fb_i, eng->d_scratch, eng->scratch_bytes, eng->n_cus, st, nullptr,
+                                   nullptr, id_map, &ext);
+        if (rc != RASS_OK) return rc;
+        HIP_TRY(rass::launch_cert_scatter(fb_s, fb_i, f.fail_idx, fail_n, k, f.out_s, f.out_i, st));
+    }
+    return RASS_OK;
+}
+
 }  // namespace
 
 // ------------------------------------------------------------------------------------ IVF (K9)
@@ -728,11 +908,14 @@ void rass_engine_destroy(rass_engine_t* eng) {
         if (idx->d_rows_bf16) (void)hipFree(idx->d_rows_bf16);
         if (idx->d_rows_i8) (void)hipFree(idx->d_rows_i8);
         if (idx->d_row_scale) (void)hipFree(idx->d_row_scale);
+        if (idx->d_cert_stats) (void)hipFree(idx->d_cert_stats);
+        if (idx->d_cert_counts) (void)hipFree(idx->d_cert_counts);
         delete idx;
     }
     eng->indices.clear();
     (void)hipFree(eng->d_scratch);
     if (eng->d_batch) (void)hipFree(eng->d_batch);
+    if (eng->d_cert) (void)hipFree(eng->d_cert);
     (void)hipFree(eng->d_qraw);
     (void)hipFree(eng->d_qfilter);
     (void)hipFree(eng->d_out_scores);
@@ -845,6 +1028,10 @@ int rass_index_drop(rass_engine_t* eng, const char* name) {
         if (idx->d_rows_bf16) (void)hipFree(idx->d_rows_bf16);
         if (idx->d_rows_i8) (void)hipFree(idx->d_rows_i8);
         if (idx->d_row_scale) (void)hipFree(idx->d_row_scale);
+        if (idx->d_cert_stats) (void)hipFree(idx->d_cert_stats);
+        if (idx->d_cert_counts) (void)hipFree(idx->d_cert_counts);
+        idx->d_cert_stats = nullptr;
+        idx->d_cert_counts = nullptr;
         idx->d_rows_i8 = nullptr;
         idx->d_row_scale = nullptr;
         idx->d_rows = nullptr;
@@ -858,7 +1045,8 @@ int rass_index_drop(rass_engine_t* eng, const char* name) {
 
 int rass_index_set_prefilter(rass_index_t* idx, int enable) {
     if (!idx) return fail(RASS_ERR_INVALID, "index is NULL");
-    if (enable < 0 || enable > 2) return fail(RASS_ERR_INVALID, "prefilter mode must be 0 (off), 1 (bf16) or 2 (int8)");
+    if (enable < 0 || enable > 3)
+        return fail(RASS_ERR_INVALID, "prefilter mode must be 0 (off), 1 (bf16), 2 (int8) or 3 (int8, certified exact)");
     rass_engine* eng = idx->eng;
     std::lock_guard<std::mutex> lk(idx->mu);
     std::lock_guard<std::mutex> elk(eng->mu);
@@ -886,7 +1074,13 @@ int rass_index_set_prefilter(rass_index_t* idx, int enable) {
                                                  st));
         HIP_TRY(hipStreamSynchronize(st));
     }
-    if (enable == 2) {
+    if (enable == 3) {   // the certificate's row maxima are recomputed from the rows; the counters start at zero
+        if (!idx->d_cert_stats) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&idx->d_cert_stats), 3 * sizeof(unsigned)));
+        if (!idx->d_cert_counts) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&idx->d_cert_counts), 3 * sizeof(unsigned long long)));
+        HIP_TRY(hipMemsetAsync(idx->d_cert_stats, 0, 3 * sizeof(unsigned), st));
+        HIP_TRY(hipMemsetAsync(idx->d_cert_counts, 0, 3 * sizeof(unsigned long long), st));
+    }
+    if (enable >= 2) {
         idx->stride_i8 = (idx->stride + 511) / 512 * 512;
         if (idx->capacity > 0) {
             HIP_TRY(hipMalloc(reinterpret_cast<void**>(&idx->d_rows_i8), (size_t)idx->capacity * idx->stride_i8));
@@ -894,9 +1088,9 @@ int rass_index_set_prefilter(rass_index_t* idx, int enable) {
             HIP_TRY(hipMemsetAsync(idx->d_rows_i8, 0, (size_t)idx->capacity * idx->stride_i8, st));
             HIP_TRY(hipMemsetAsync(idx->d_row_scale, 0, (size_t)idx->capacity * sizeof(float), st));
             HIP_TRY(rass::launch_quantize_tile16_i8(idx->d_rows, idx->d_rows_i8, idx->d_row_scale, idx->stride, idx->stride_i8, 0,
-                                                    (idx->rows + 15) >> 4, st));
-            HIP_TRY(hipStreamSynchronize(st));
+                                                    (idx->rows + 15) >> 4, st, enable == 3 ? idx->d_cert_stats : nullptr));
         }
+        HIP_TRY(hipStreamSynchronize(st));
     }
     idx->prefilter = enable;
     return RASS_OK;
@@ -977,9 +1171,10 @@ static int add_common(rass_index_t* idx, const float* vecs, const int32_t* tags,
     if (idx->prefilter == 1 && idx->dtype == RASS_F32)
         HIP_TRY(rass::launch_convert_tile16_bf16(idx->d_rows, idx->d_rows_bf16, idx->stride, idx->rows >> 4,
                                                  (idx->rows + n + 15) >> 4, st));
-    if (idx->prefilter == 2)   // whole blocks: the earlier rows of a partially filled block quantise to the same bytes again
+    if (idx->prefilter >= 2)   // whole blocks: the earlier rows of a partially filled block quantise to the same bytes again
         HIP_TRY(rass::launch_quantize_tile16_i8(idx->d_rows, idx->d_rows_i8, idx->d_row_scale, idx->stride, idx->stride_i8,
-                                                idx->rows >> 4, (idx->rows + n + 15) >> 4, st));
+                                                idx->rows >> 4, (idx->rows + n + 15) >> 4, st,
+                                                idx->prefilter == 3 ? idx->d_cert_stats : nullptr));
     // the id a search reports for these rows: their ordinal, or the caller's global ids (ascending with the
     // ordinal, so the (score desc, id asc) tie order inside the shard is the global one)
     HIP_TRY(rass::launch_iota_i64(idx->d_gid + idx->rows, n, first_global_id >= 0 ? first_global_id : idx->rows.load(), st));
@@ -1091,7 +1286,10 @@ int search_device_group(rass_index* idx, const float* d_queries, int nq, int k, 
                                 d_out_ids, need_tags ? idx->d_tags : nullptr, eng, eng->stream,
                                 gid ? idx->d_gid : nullptr, (d_q_filter_mask || d_after_score) ? &bext : nullptr);
     }
-    if (idx->prefilter && rows > 0 && k <= kPrefilterMaxK && !d_after_score)
+    if (idx->prefilter == 3 && rows > 0 && !d_after_score)
+        return cert_launch(idx, d_queries, nq, d_q_filter, d_q_filter_mask, k, id_base, d_out_scores, d_out_ids,
+                           need_tags ? idx->d_tags : nullptr, eng, eng->stream, gid ? idx->d_gid : nullptr);
+    if (idx->prefilter && idx->prefilter != 3 && rows > 0 && k <= kPrefilterMaxK && !d_after_score)
         return prefilter_launch(idx, d_queries, nq, d_q_filter, k, id_base, d_out_scores, d_out_ids,
                                 need_tags ? idx->d_tags : nullptr, eng, eng->stream, nullptr, nullptr, d_q_filter_mask,
                                 gid ? idx->d_gid : nullptr);
@@ -1446,7 +1644,7 @@ int rass_index_search_device_batch(rass_index_t* idx, const float* d_queries, in
     if (rc != RASS_OK) return rc;
     const bool fused = idx->dtype == RASS_F32 && !idx->prefilter && nq > RASS_MAX_QBATCH;
     if (fused) return scan_launch_batch(idx, d_queries, nq, k, d_q_filter, id_base, d_out_scores, d_out_ids, gs, gi);
-    if (idx->prefilter && idx->dtype == RASS_F32 && nq > RASS_MAX_QBATCH && k <= kPrefilterMaxK &&
+    if (idx->prefilter && idx->prefilter != 3 && idx->dtype == RASS_F32 && nq > RASS_MAX_QBATCH && k <= kPrefilterMaxK &&
         idx->rows.load(std::memory_order_acquire) > 0)
         return prefilter_launch_batch(idx, d_queries, nq, k, d_q_filter, id_base, d_out_scores, d_out_ids, gs, gi);
     // bf16 / prefilter corpora and single groups: the same result group by group
@@ -1474,6 +1672,8 @@ int rass_index_candidates_device(rass_index_t* idx, const float* d_queries, int 
     int rc = set_device(eng);
     if (rc != RASS_OK) return rc;
     if (!idx->prefilter || idx->dtype != RASS_F32) return fail(RASS_ERR_UNSUPPORTED, "the index is not in a prefilter mode");
+    if (idx->prefilter == 3)
+        return fail(RASS_ERR_UNSUPPORTED, "mode 3 keeps 128 candidates per query: rass_index_candidates_exact_device");
     if (idx->rows.load(std::memory_order_acquire) <= 0) return fail(RASS_ERR_INVALID, "the index is empty");
     const bool need_tags = (idx->deleted.load(std::memory_order_acquire) > 0) || (d_q_filter != nullptr);
     const ScratchLayout L = scratch_layout(RASS_MAX_QBATCH, RASS_MAX_K);
@@ -1481,6 +1681,44 @@ int rass_index_candidates_device(rass_index_t* idx, const float* d_queries, int 
     return prefilter_launch(idx, d_queries, nq, d_q_filter, 1, 0, reinterpret_cast<float*>(eng->d_scratch + L.cand_scores),
                             reinterpret_cast<int64_t*>(eng->d_scratch + L.cand_ids), need_tags ? idx->d_tags : nullptr, eng,
                             eng->stream, d_cand_scores, d_cand_rows);
+}
+
+int rass_index_certify_stats(rass_index_t* idx, int64_t* queries, int64_t* certified, int64_t* fallbacks, float* R, float* V) {
+    if (!idx) return fail(RASS_ERR_INVALID, "index is NULL");
+    rass_engine* eng = idx->eng;
+    std::lock_guard<std::mutex> lk(eng->mu);
+    int rc = set_device(eng);
+    if (rc != RASS_OK) return rc;
+    unsigned long long c[3] = {0, 0, 0};
+    unsigned st3[3] = {0, 0, 0};
+    HIP_TRY(hipStreamSynchronize(eng->stream));
+    if (idx->d_cert_counts) HIP_TRY(hipMemcpy(c, idx->d_cert_counts, sizeof(c), hipMemcpyDeviceToHost));
+    if (idx->d_cert_stats) HIP_TRY(hipMemcpy(st3, idx->d_cert_stats, sizeof(st3), hipMemcpyDeviceToHost));
+    float f[3];
+    memcpy(f, st3, sizeof(f));
+    if (queries) *queries = (int64_t)c[0];
+    if (certified) *certified = (int64_t)c[1];
+    if (fallbacks) *fallbacks = (int64_t)c[2];
+    if (R) *R = f[0];
+    if (V) *V = f[1];
+    return RASS_OK;
+}
+
+int rass_index_candidates_exact_device(rass_index_t* idx, const float* d_queries, int nq, int k, const int32_t* d_q_filter,
+                                       float* d_cand_scores, int64_t* d_cand_rows, float* d_tau, int32_t* d_certified) {
+    if (!idx || !d_queries || !d_cand_scores || !d_cand_rows || !d_tau || !d_certified) return fail(RASS_ERR_INVALID, "NULL argument");
+    if (nq < 1 || nq > RASS_MAX_QBATCH) return fail(RASS_ERR_INVALID, "nq must be in [1, RASS_MAX_QBATCH]");
+    if (k < 1 || k > RASS_MAX_K) return fail(RASS_ERR_INVALID, "k must be in [1, RASS_MAX_K]");
+    rass_engine* eng = idx->eng;
+    std::lock_guard<std::mutex> lk(eng->mu);
+    int rc = set_device(eng);
+    if (rc != RASS_OK) return rc;
+    if (idx->prefilter != 3 || idx->dtype != RASS_F32) return fail(RASS_ERR_UNSUPPORTED, "the index is not in prefilter mode 3");
+    if (idx->rows.load(std::memory_order_acquire) <= 0) return fail(RASS_ERR_INVALID, "the index is empty");
+    const bool need_tags = (idx->deleted.load(std::memory_order_acquire) > 0) || (d_q_filter != nullptr);
+    // the search's own result goes to a slot of the mode's workspace (nullptr outputs): not reported here
+    return cert_launch(idx, d_queries, nq, d_q_filter, nullptr, k, 0, nullptr, nullptr,
+                       need_tags ? idx->d_tags : nullptr, eng, eng->stream, nullptr, d_cand_scores, d_cand_rows, d_tau, d_certified);
 }
 
 namespace {
@@ -1569,6 +1807,9 @@ int rass_index_search_ex(rass_index_t* idx, const float* queries, int nq, int k,
                     rc = bf16_scan_launch(idx, eng->d_qraw, b, d_filter, kk, 0, eng->d_out_scores, eng->d_out_ids,
                                           need_tags ? idx->d_tags : nullptr, eng, st, gid ? idx->d_gid : nullptr,
                                           use_ext ? &ext : nullptr);
+                else if (idx->prefilter == 3 && rows > 0 && k <= RASS_MAX_K && !cont)
+                    rc = cert_launch(idx, eng->d_qraw, b, d_filter, ext.d_q_mask, kk, 0, eng->d_out_scores, eng->d_out_ids,
+                                     need_tags ? idx->d_tags : nullptr, eng, st, gid ? idx->d_gid : nullptr);
                 else if (idx->prefilter && rows > 0 && k <= kPrefilterMaxK && !cont)
                     rc = prefilter_launch(idx, eng->d_qraw, b, d_filter, kk, 0, eng->d_out_scores, eng->d_out_ids,
                                           need_tags ? idx->d_tags : nullptr, eng, st, nullptr, nullptr, ext.d_q_mask,
@@ -1959,9 +2200,10 @@ int rass_index_fill_synthetic(rass_index_t* idx, int64_t n, uint64_t seed, int64
     if (idx->prefilter == 1 && idx->dtype == RASS_F32)
         HIP_TRY(rass::launch_convert_tile16_bf16(idx->d_rows, idx->d_rows_bf16, idx->stride, idx->rows >> 4,
                                                  (idx->rows + n + 15) >> 4, st));
-    if (idx->prefilter == 2)   // whole blocks: the earlier rows of a partially filled block quantise to the same bytes again
+    if (idx->prefilter >= 2)   // whole blocks: the earlier rows of a partially filled block quantise to the same bytes again
         HIP_TRY(rass::launch_quantize_tile16_i8(idx->d_rows, idx->d_rows_i8, idx->d_row_scale, idx->stride, idx->stride_i8,
-                                                idx->rows >> 4, (idx->rows + n + 15) >> 4, st));
+                                                idx->rows >> 4, (idx->rows + n + 15) >> 4, st,
+                                                idx->prefilter == 3 ? idx->d_cert_stats : nullptr));
     idx->rows += n;
     idx->host_deleted.resize((size_t)((idx->rows + 7) / 8), 0);
     return RASS_OK;

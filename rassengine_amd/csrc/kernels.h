@@ -55,6 +55,9 @@ struct ScanArgs {
     // the scan is purely HBM-bound (B <= 16).  With skew s > 0 the even workgroups take s+1 items
     // for every s the odd ones take, so all of them finish together.  Needs an even grid.
     int xcd_skew = 0;
+    // device scalar (nullptr = none): when it reads 0 every workgroup exits at once — the fp32 fallback of the certified
+    // int8 mode (prefilter mode 3) is enqueued unconditionally and runs only when some query's certificate failed
+    const int32_t* live_nq = nullptr;
     // Grouped flat scan (kFlatGroups; 0 = off): workgroups [g * wgs_per_group, (g + 1) * wgs_per_group) serve launch group
     // g — its 32 (zero-padded) queries at q_padded + g * q_group_stride, its lists at part_* + g * part_group_stride
     // ([wgs_per_group][nq][k], nq = 32 for every group), its filters at q_filter + 32 g.  No sample floor, no EXT.
@@ -85,7 +88,8 @@ struct MergeGroups {
 hipError_t launch_merge_topk(const float* scores, const int64_t* ids, int n_lists, int nq, int k,
                              float* out_scores, int64_t* out_ids, hipStream_t stream,
                              const int64_t* id_map = nullptr, int64_t score_list_stride = 0,
-                             int64_t id_list_stride = 0, const MergeGroups* groups = nullptr);
+                             int64_t id_list_stride = 0, const MergeGroups* groups = nullptr,
+                             const int32_t* live_nq = nullptr);   // as ScanArgs::live_nq: 0 = every workgroup exits
 
 // ---- bf16 candidate scan + exact re-rank (scan_bf16.hip)
 struct ScanBf16Args {
@@ -161,9 +165,72 @@ struct ScanI8Args {
     const int32_t* n_work = nullptr;
 };
 hipError_t launch_scan_i8_topk(const ScanI8Args& a, int grid, hipStream_t stream);
-// fp32 tile16 blocks [block0, block1) -> tile16i blocks of dst (+ one scale per row)
+// fp32 tile16 blocks [block0, block1) -> tile16i blocks of dst (+ one scale per row).  stats (nullptr = none): the certified
+// mode's per-index maxima [R, V, Y] as float bits, raised by atomicMax with every quantised row's rho, nu and |y| (rounded up)
 hipError_t launch_quantize_tile16_i8(const float* src, void* dst, float* scale, int64_t stride, int64_t stride_i8, int64_t block0,
-                                     int64_t block1, hipStream_t stream);
+                                     int64_t block1, hipStream_t stream, unsigned* stats = nullptr);
+
+// ---- certified int8 search (prefilter mode 3, scan_i8.hip + certify.hip; DESIGN.md §3 "certified int8 search")
+constexpr int kCertQ = 16;        // queries per candidate pass (hi + lo = 32 MFMA columns)
+constexpr int kCertC = 128;       // candidates per query
+constexpr int kCertWgCap = 256;   // candidate slots per (workgroup, query) of the scan
+constexpr int kMaxGridSel = 1024;    // scan workgroups (slices) the selection takes
+constexpr int kCertSelCap = 16384;  // candidates per query the selection takes (more: the query is not certified)
+struct CertQInfo {                // one query of a pass (queries_to_i8_hilo)
+    float s_hi, s_lo;             // q ~ s_hi q_hi + s_lo q_lo
+    double qnorm, rho, qa;        // upper bounds of |q|, |q - s_hi q_hi - s_lo q_lo|, |s_hi q_hi| + |s_lo q_lo|
+};
+struct ScanI8CertArgs {
+    const signed char* corpus;    // tile16i slab
+    const float* row_scale;
+    const int32_t* row_tag;       // or nullptr
+    const signed char* q_i8;      // [32][row_stride]: rows 0..15 q_hi, rows 16..31 q_lo
+    const CertQInfo* qinfo;       // [16]
+    const int32_t* q_filter;      // [nq] or nullptr
+    const int32_t* q_filter_mask; // [nq] or nullptr
+    int64_t row_stride;
+    int n_rows;
+    int nq;                       // <= 16
+    float* sample_out;            // non-null: a SAMPLE launch — [grid][16] best candidate score per workgroup, nothing else
+    const float* sample_best;     // the floor: the floor_rank-th largest of sample_best[0 .. sample_groups)[q]; nullptr = none
+    int sample_groups = 0;
+    int floor_rank = kCertC;
+    float* list_s;                // [grid][16][kCertWgCap] candidate scores (unsorted)
+    int32_t* list_r;              // [grid][16][kCertWgCap] their rows
+    int32_t* list_n;              // [grid][16] candidates found (may exceed kCertWgCap: overflow)
+    float* list_floor;            // [grid][16] the floor if it dropped an eligible row of this workgroup, else -inf
+};
+hipError_t launch_scan_i8_cert(const ScanI8CertArgs& a, int grid, hipStream_t stream);
+hipError_t launch_queries_to_i8_hilo(const float* q_padded, signed char* q_i8, CertQInfo* info, int64_t stride, int64_t stride_i8,
+                                     hipStream_t stream);
+// per query: the kCertC best (score desc, row asc) of the scan's lists -> cand_rows [4][16][32] (the re-rank's input, -1 past
+// the end), optionally cand_s / cand_r [nq][kCertC] (sorted), and tau[q] (certify.hip)
+hipError_t launch_cert_select(const float* list_s, const int32_t* list_r, const int32_t* list_n, const float* list_floor, int grid,
+                              int nq, int64_t* cand_rows, float* cand_s, int64_t* cand_r, float* tau, hipStream_t stream);
+struct CertFinishArgs {
+    const float* rr_s;            // [4][16][32] exact scores of the four re-ranked candidate chunks
+    const int64_t* rr_i;          // [4][16][32] their reported ids (-1: none)
+    const float* tau;             // [nq]
+    const CertQInfo* qinfo;
+    const unsigned* stats;        // [R, V, Y] float bits
+    int dim, nq, k;
+    float* out_s;                 // [nq][k]
+    int64_t* out_i;
+    int32_t* certified;           // [nq] or nullptr
+    int32_t* fail_flag;           // [16] 1 = the certificate failed
+    int32_t* fail_idx;            // [16] failed queries, compacted
+    int32_t* fail_n;              // device scalar
+    const float* q_raw;           // [nq][dim] the caller's queries
+    const int32_t* q_filter;      // or nullptr
+    const int32_t* q_filter_mask; // or nullptr
+    float* fb_q;                  // [16][dim] the failed queries, compacted (zero rows after them)
+    int32_t* fb_filter;           // [16]
+    int32_t* fb_mask;             // [16]
+    unsigned long long* counters; // [queries, certified, fallbacks]
+};
+hipError_t launch_cert_finish(const CertFinishArgs& a, hipStream_t stream);
+hipError_t launch_cert_scatter(const float* fb_s, const int64_t* fb_i, const int32_t* fail_idx, const int32_t* fail_n, int k,
+                               float* out_s, int64_t* out_i, hipStream_t stream);
 hipError_t launch_queries_to_i8(const float* src, void* dst, int nq_pad, int64_t stride, int64_t stride_i8, hipStream_t stream);
 
 // ---- peer-store exchange of per-shard top-k (peer.hip)

@@ -133,7 +133,9 @@ __global__ __launch_bounds__(kMergeThreads) void merge_topk_kernel(const float* 
                                                                    int64_t* __restrict__ out_ids,
                                                                    const int64_t* __restrict__ id_map,
                                                                    int64_t score_list_stride, int64_t id_list_stride,
-                                                                   MergeGroups grp) {
+                                                                   MergeGroups grp, const int32_t* __restrict__ live_nq) {
+    // the merge behind a scan that exited on a zero live count (the certified mode's idle fallback): its lists were never written
+    if (live_nq != nullptr && __builtin_amdgcn_readfirstlane(*live_nq) == 0) return;
     __shared__ float sh_s[kMergeWaves * 32];
     __shared__ int64_t sh_i[kMergeWaves * 32];
     // Grouped form (grp.size > 0): blockIdx.x counts the queries of SEVERAL launch groups; group g's lists start
@@ -215,7 +217,8 @@ __global__ __launch_bounds__(kMergeThreads) void merge_topk_kernel(const float* 
 
 hipError_t launch_merge_topk(const float* scores, const int64_t* ids, int n_lists, int nq, int k,
                              float* out_scores, int64_t* out_ids, hipStream_t stream, const int64_t* id_map,
-                             int64_t score_list_stride, int64_t id_list_stride, const MergeGroups* groups) {
+                             int64_t score_list_stride, int64_t id_list_stride, const MergeGroups* groups,
+                             const int32_t* live_nq) {
     const int64_t n = (int64_t)n_lists * k;
     if (n_lists < 1 || nq < 1 || k < 1 || k > 32 || n > kMergeMaxCandidates) return hipErrorInvalidValue;
     if (score_list_stride <= 0) score_list_stride = (int64_t)nq * k;
@@ -226,7 +229,7 @@ hipError_t launch_merge_topk(const float* scores, const int64_t* ids, int n_list
         if (grp.size < 1 || grp.nq_total != nq) return hipErrorInvalidValue;
     }
     hipLaunchKernelGGL(merge_topk_kernel, dim3(nq), dim3(kMergeThreads), 0, stream, scores, ids, n_lists, nq, k,
-                       out_scores, out_ids, id_map, score_list_stride, id_list_stride, grp);
+                       out_scores, out_ids, id_map, score_list_stride, id_list_stride, grp, live_nq);
     return hipGetLastError();
 }
 

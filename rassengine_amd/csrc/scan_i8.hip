@@ -312,11 +312,19 @@ hipError_t launch_scan_i8_topk(const ScanI8Args& a, int grid, hipStream_t stream
 #undef RASS_I8_CASE
 }
 
+// A non-negative double (a norm summed in double: relative error < 2.3e-13 for <= 2 048 terms) -> a float that is not below it.
+__device__ __forceinline__ float cert_up(double x) {
+    x *= 1.0 + 1e-12;
+    float f = (float)x;
+    if ((double)f < x) f = nextafterf(f, INFINITY);
+    return f;
+}
+
 // fp32 tile16 blocks [b0, b1) -> tile16i blocks + one scale per row; one wave per 16-row block.  Lane (m, g) owns, of row m,
 // the 16 columns 64jb + 16g .. +15 of every 64-column chunk jb = fp32 chunk 4jb + g (four f32x4 at lane groups 0..3).
 __global__ __launch_bounds__(256) void quantize_tile16_i8_kernel(const float* __restrict__ src, signed char* __restrict__ dst,
                                                                  float* __restrict__ scale, int64_t stride, int64_t stride_i8,
-                                                                 int64_t b0, int64_t b1) {
+                                                                 int64_t b0, int64_t b1, unsigned* __restrict__ stats) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int m = lane & 15, g = lane >> 4;
     const int nch = (int)(stride >> 6);   // 64-column chunks that hold data (stride is a multiple of 128)
@@ -335,7 +343,9 @@ __global__ __launch_bounds__(256) void quantize_tile16_i8_kernel(const float* __
         mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
         mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
         const float inv = mx > 0.f ? 127.f / mx : 0.f;
-        if (g == 0) scale[b * 16 + m] = mx / 127.f;
+        const float sy = mx / 127.f;
+        if (g == 0) scale[b * 16 + m] = sy;
+        double rho2 = 0.0, nu2 = 0.0, y2 = 0.0;   // the certified mode's row terms (exact products in double)
         for (int jb = 0; jb < nch; ++jb) {
             const float* sc = sb + (int64_t)(4 * jb + g) * 256;
             unsigned o[4];
@@ -343,21 +353,45 @@ __global__ __launch_bounds__(256) void quantize_tile16_i8_kernel(const float* __
             for (int gg = 0; gg < 4; ++gg) {
                 const f32x4 v = *reinterpret_cast<const f32x4*>(sc + (gg * 16 + m) * 4);
                 const int q0 = (int)rintf(v.x * inv), q1 = (int)rintf(v.y * inv), q2 = (int)rintf(v.z * inv), q3 = (int)rintf(v.w * inv);
+                if (stats) {
+                    const float vv[4] = {v.x, v.y, v.z, v.w};
+                    const int qq[4] = {q0, q1, q2, q3};
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        const double yh = (double)sy * qq[e], d = (double)vv[e] - yh;
+                        rho2 += d * d;
+                        nu2 += yh * yh;
+                        y2 += (double)vv[e] * vv[e];
+                    }
+                }
                 o[gg] = (unsigned)(q0 & 0xff) | ((unsigned)(q1 & 0xff) << 8) | ((unsigned)(q2 & 0xff) << 16) | ((unsigned)(q3 & 0xff) << 24);
             }
             *reinterpret_cast<uint4*>(db + (int64_t)jb * 1024 + lane * 16) = uint4{o[0], o[1], o[2], o[3]};
+        }
+        if (stats) {
+#pragma unroll
+            for (int o = 16; o <= 32; o <<= 1) {
+                rho2 += __shfl_xor(rho2, o, 64);
+                nu2 += __shfl_xor(nu2, o, 64);
+                y2 += __shfl_xor(y2, o, 64);
+            }
+            if (g == 0) {
+                atomicMax(stats + 0, __float_as_uint(cert_up(sqrt(rho2))));
+                atomicMax(stats + 1, __float_as_uint(cert_up(sqrt(nu2))));
+                atomicMax(stats + 2, __float_as_uint(cert_up(sqrt(y2))));
+            }
         }
     }
 }
 
 hipError_t launch_quantize_tile16_i8(const float* src, void* dst, float* scale, int64_t stride, int64_t stride_i8, int64_t block0,
-                                     int64_t block1, hipStream_t stream) {
+                                     int64_t block1, hipStream_t stream, unsigned* stats) {
     if (block1 <= block0) return hipSuccess;
     if (stride % 128 != 0 || stride_i8 % 512 != 0 || stride_i8 < stride) return hipErrorInvalidValue;
     int64_t blocks = (block1 - block0 + 3) / 4;
     if (blocks > 256 * 16) blocks = 256 * 16;
     hipLaunchKernelGGL(quantize_tile16_i8_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, src, static_cast<signed char*>(dst),
-                       scale, stride, stride_i8, block0, block1);
+                       scale, stride, stride_i8, block0, block1, stats);
     return hipGetLastError();
 }
 
@@ -379,6 +413,282 @@ hipError_t launch_queries_to_i8(const float* src, void* dst, int nq_pad, int64_t
     if (nq_pad <= 0) return hipSuccess;
     hipLaunchKernelGGL(queries_to_i8_kernel, dim3(nq_pad), dim3(64), 0, stream, src, static_cast<signed char*>(dst), stride, stride_i8);
     return hipGetLastError();
+}
+
+// ---- certified int8 search (prefilter mode 3; DESIGN.md §3 "certified int8 search") --------------------------------------------
+// Queries as hi + lo int8 vectors: q ~ s_hi q_hi + s_lo q_lo, q_lo the int8 quantisation of the fp32 residual r = q - s_hi q_hi
+// (each rounded exactly as a corpus row).  One wave per query of a 16-query pass; rows 0..15 of q_i8 get q_hi, rows 16..31 q_lo.
+// qinfo: the scales and, in double, upper bounds of |q|, of the remainder rho_q and of |s_hi q_hi| + |s_lo q_lo|.
+__global__ __launch_bounds__(64) void queries_to_i8_hilo_kernel(const float* __restrict__ src, signed char* __restrict__ dst,
+                                                                CertQInfo* __restrict__ info, int64_t stride, int64_t stride_i8) {
+#pragma clang fp contract(off)
+    const int q = blockIdx.x, lane = threadIdx.x;
+    const float* s = src + (int64_t)q * stride;
+    float mx = 0.f;
+    for (int64_t c = lane; c < stride; c += 64) mx = fmaxf(mx, fabsf(s[c]));
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
+    const float inv = mx > 0.f ? 127.f / mx : 0.f, s_hi = mx / 127.f;
+    float mr = 0.f;
+    for (int64_t c = lane; c < stride; c += 64) {
+        const float qh = rintf(s[c] * inv);
+        mr = fmaxf(mr, fabsf(__fsub_rn(s[c], __fmul_rn(s_hi, qh))));
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) mr = fmaxf(mr, __shfl_xor(mr, o, 64));
+    const float inv_lo = mr > 0.f ? 127.f / mr : 0.f, s_lo = mr / 127.f;
+    double qn2 = 0.0, rho2 = 0.0, h2 = 0.0, l2 = 0.0;
+    signed char* dh = dst + (int64_t)q * stride_i8;
+    signed char* dl = dst + (int64_t)(kCertQ + q) * stride_i8;
+    for (int64_t c = lane; c < stride_i8; c += 64) {
+        int qh = 0, ql = 0;
+        if (c < stride) {
+            const float v = s[c];
+            qh = (int)rintf(v * inv);
+            const float r = __fsub_rn(v, __fmul_rn(s_hi, (float)qh));
+            ql = (int)rintf(r * inv_lo);
+            const double ph = (double)s_hi * qh, pl = (double)s_lo * ql, rem = ((double)v - ph) - pl;
+            qn2 += (double)v * v;
+            rho2 += rem * rem;
+            h2 += ph * ph;
+            l2 += pl * pl;
+        }
+        dh[c] = (signed char)qh;
+        dl[c] = (signed char)ql;
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {
+        qn2 += __shfl_xor(qn2, o, 64);
+        rho2 += __shfl_xor(rho2, o, 64);
+        h2 += __shfl_xor(h2, o, 64);
+        l2 += __shfl_xor(l2, o, 64);
+    }
+    if (lane == 0) {
+        CertQInfo ci;
+        ci.s_hi = s_hi;
+        ci.s_lo = s_lo;
+        ci.qnorm = sqrt(qn2) * (1.0 + 1e-12);
+        ci.rho = sqrt(rho2) * (1.0 + 1e-12) + 1e-30;   // + the double rounding of the remainder itself
+        ci.qa = (sqrt(h2) + sqrt(l2)) * (1.0 + 1e-12);
+        info[q] = ci;
+    }
+}
+
+hipError_t launch_queries_to_i8_hilo(const float* q_padded, signed char* q_i8, CertQInfo* info, int64_t stride, int64_t stride_i8,
+                                     hipStream_t stream) {
+    hipLaunchKernelGGL(queries_to_i8_hilo_kernel, dim3(kCertQ), dim3(64), 0, stream, q_padded, q_i8, info, stride, stride_i8);
+    return hipGetLastError();
+}
+
+// The candidate scan of mode 3: the main loop of scan_i8_topk_kernel with NT = 2, the 32 MFMA columns being q_hi (0..15) and q_lo
+// (16..31) of 16 queries.  Wave w's half h ranks query q = 8h + w:
+//     a(y) = s_y * (s_hi * (float)dot(y8, q_hi) + s_lo * (float)dot(y8, q_lo))     (separate correctly rounded fp32 operations)
+// and, instead of a sorted list, APPENDS every eligible row with a(y) >= floor_q to its slice list_* [bid][q][0 .. kCertWgCap):
+// no list is truncated here (a slice that fills keeps counting: overflow, the query is not certified), so the selection
+// (certify.hip) sees every eligible row above the floor.  The floor is the floor_rank-th largest of the per-workgroup maxima of
+// a SAMPLE launch (this kernel, sample_out set) over disjoint rows: floor_rank rows reach it, so it never drops a row of the
+// exact top-floor_rank; whether it dropped any row at all is reported (list_floor) — it then bounds every dropped row's score.
+template <int CHI>
+__global__ __launch_bounds__(kIThreads, 1) void scan_i8_cert_kernel(ScanI8CertArgs p) {
+#pragma clang fp contract(off)
+    constexpr int NT = 2, NQ = 32;
+    extern __shared__ __attribute__((aligned(16))) int lds_i[];  // [kINBuf][kIWaves][NQ][kIPitch]
+    const int lane = threadIdx.x & 63;
+    const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int m = lane & 15, g = lane >> 4;
+    const int n_tiles = (p.n_rows + kITileRows - 1) / kITileRows;
+    const int G = (int)gridDim.x, bid = (int)blockIdx.x;
+    const bool sample = p.sample_out != nullptr;
+
+    i32x4 qf[NT][CHI];
+    {
+        const signed char* qb = p.q_i8 + (int64_t)m * p.row_stride + wid * 64 * CHI + 16 * g;
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt)
+#pragma unroll
+            for (int j = 0; j < CHI; ++j)
+                qf[nt][j] = *reinterpret_cast<const i32x4*>(qb + (int64_t)nt * 16 * p.row_stride + 64 * j);
+    }
+    const int voff_lane = wid * CHI * 1024 + lane * 16;
+    const int blk_step = 16 * (int)p.row_stride;
+
+    const int q = (lane >> 5) * 8 + wid;   // this half-wave's query
+    const bool q_ok = q < p.nq;
+    const int qfilt = (p.q_filter != nullptr && q_ok) ? p.q_filter[q] : -1;
+    const int qmask = (p.q_filter_mask != nullptr && q_ok) ? p.q_filter_mask[q] : -1;
+    const float s_hi = p.qinfo[q].s_hi, s_lo = p.qinfo[q].s_lo;
+
+    float floor_q = -INFINITY;
+    if (!sample && p.sample_best != nullptr) {
+        constexpr int kSlots = kMaxSampleGroups / 64;
+        unsigned key[2][kSlots];
+#pragma unroll
+        for (int half = 0; half < 2; ++half)
+#pragma unroll
+            for (int j = 0; j < kSlots; ++j) {
+                const int sg = lane + 64 * j, qq = half * 8 + wid;
+                const float v = (sg < p.sample_groups && qq < p.nq) ? p.sample_best[(int64_t)sg * kCertQ + qq] : -INFINITY;
+                key[half][j] = v == -INFINITY ? 0u : score_key(v);
+            }
+        constexpr int kFloorBits = 20;   // the truncation only lowers the floor
+        unsigned T[2] = {0u, 0u};
+#pragma unroll 1
+        for (int b = 31; b >= 32 - kFloorBits; --b)
+#pragma unroll
+            for (int half = 0; half < 2; ++half) {
+                const unsigned cand = T[half] | (1u << b);
+                int c = 0;
+#pragma unroll
+                for (int j = 0; j < kSlots; ++j) c += __popcll(__ballot(key[half][j] >= cand));
+                T[half] = c >= p.floor_rank ? cand : T[half];
+            }
+        const unsigned t = (lane & 32) ? T[1] : T[0];
+        floor_q = t ? key_score(t) : -INFINITY;
+    }
+
+    int n_found = 0;          // uniform over the half-wave
+    bool dropped = false;     // per lane: an eligible row fell below the floor
+    float best = -INFINITY;   // the sample launch's running maximum (per lane)
+    const int64_t slot0 = ((int64_t)bid * kCertQ + q) * kCertWgCap;
+
+    auto item_rows = [&](int t) {
+        const int rows = p.n_rows - t * kITileRows;
+        return t < n_tiles ? (rows > kITileRows ? kITileRows : rows) : 0;
+    };
+    auto desc = [&](int t) {
+        ScanI8Args da;
+        da.corpus = p.corpus;
+        da.row_scale = p.row_scale;
+        da.row_tag = p.row_tag;
+        da.row_stride = p.row_stride;
+        const int rows = item_rows(t);
+        return make_idesc(da, rows > 0 ? t : 0, rows);
+    };
+    auto issue = [&](ITile<CHI>& r, const IDesc& d) {
+        r.tag = (int)__builtin_amdgcn_raw_buffer_load_b32(d.tags, lane * 4, 0, 0);
+        r.scale = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(d.scales, lane * 4, 0, 0));
+#pragma unroll
+        for (int j = 0; j < CHI; ++j)
+#pragma unroll
+            for (int b = 0; b < 4; ++b)
+                r.a[b][j] = __builtin_bit_cast(i32x4, __builtin_amdgcn_raw_buffer_load_b128(d.rows, voff_lane + b * blk_step + j * 1024, 0, 2));
+    };
+    auto mul_refill = [&](ITile<CHI>& r, i32x4 (&acc)[4][NT], const IDesc& next) {
+#pragma unroll
+        for (int b = 0; b < 4; ++b)
+#pragma unroll
+            for (int nt = 0; nt < NT; ++nt) acc[b][nt] = i32x4{0, 0, 0, 0};
+        r.tag = (int)__builtin_amdgcn_raw_buffer_load_b32(next.tags, lane * 4, 0, 0);
+        r.scale = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(next.scales, lane * 4, 0, 0));
+#pragma unroll
+        for (int j = 0; j < CHI; ++j) {
+#pragma unroll
+            for (int b = 0; b < 4; ++b) {
+                const i32x4 a = r.a[b][j];
+#pragma unroll
+                for (int nt = 0; nt < NT; ++nt)
+                    acc[b][nt] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a, qf[nt][j], acc[b][nt], 0, 0, 0);
+                r.a[b][j] = __builtin_bit_cast(i32x4, __builtin_amdgcn_raw_buffer_load_b128(next.rows, voff_lane + b * blk_step + j * 1024, 0, 2));
+            }
+            __builtin_amdgcn_sched_barrier(0);
+        }
+    };
+    auto finish = [&](const i32x4 (&acc)[4][NT], int tile, int rows, int tag, float scale, int buf) {
+        int* P = lds_i + (kINBuf == 2 ? buf : 0) * (kIWaves * NQ * kIPitch);
+#pragma unroll
+        for (int b = 0; b < 4; ++b)
+#pragma unroll
+            for (int nt = 0; nt < NT; ++nt)
+                *reinterpret_cast<i32x4*>(P + (wid * NQ + nt * 16 + m) * kIPitch + b * 16 + 4 * g) = acc[b][nt];
+        __syncthreads();
+#pragma unroll
+        for (int half = 0; half < 2; ++half) {
+            const int r = (lane & 31) + 32 * half;
+            const int row = tile * kITileRows + r;
+            const int rtag = __shfl(tag, r, 64);
+            const float rscale = __shfl(scale, r, 64);
+            const int* src = P + q * kIPitch + r;
+            int sh = src[0], sl = src[16 * kIPitch];
+#pragma unroll
+            for (int wv = 1; wv < kIWaves; ++wv) {
+                sh += src[wv * NQ * kIPitch];
+                sl += src[wv * NQ * kIPitch + 16 * kIPitch];
+            }
+            const float a = __fmul_rn(rscale, __fadd_rn(__fmul_rn(s_hi, (float)sh), __fmul_rn(s_lo, (float)sl)));
+            const bool elig = q_ok && (r < rows) && (rtag != -1) && (qfilt < 0 || qfilt == (rtag & qmask));
+            if (sample) {
+                best = elig ? fmaxf(best, a) : best;
+            } else {
+                const bool keep = elig && a >= floor_q;
+                dropped = dropped || (elig && !keep);
+                const unsigned long long bal = __ballot(keep);
+                const unsigned hm = (lane & 32) ? (unsigned)(bal >> 32) : (unsigned)bal;
+                const int pos = n_found + __popc(hm & ((1u << (lane & 31)) - 1u));
+                if (keep && pos < kCertWgCap) {
+                    p.list_s[slot0 + pos] = a;
+                    p.list_r[slot0 + pos] = row;
+                }
+                n_found += __popc(hm);
+            }
+        }
+        if (kINBuf == 1) __syncthreads();
+    };
+
+    ITile<CHI> R0, R1;
+    int t = bid;
+    issue(R0, desc(t));
+    issue(R1, desc(t + G));
+    __builtin_amdgcn_sched_barrier(0);
+    for (; t < n_tiles; t += 2 * G) {
+        i32x4 acc[4][NT];
+        int tag = R0.tag;
+        float scale = R0.scale;
+        mul_refill(R0, acc, desc(t + 2 * G));
+        finish(acc, t, item_rows(t), tag, scale, 0);
+        tag = R1.tag;
+        scale = R1.scale;
+        mul_refill(R1, acc, desc(t + 3 * G));
+        finish(acc, t + G, item_rows(t + G), tag, scale, 1);
+    }
+    if (sample) {
+#pragma unroll
+        for (int o = 16; o >= 1; o >>= 1) best = fmaxf(best, __shfl_xor(best, o, 64));
+        if ((lane & 31) == 0 && q_ok) p.sample_out[(int64_t)bid * kCertQ + q] = best;
+    } else {
+        const bool any_drop = ((lane & 32) ? (unsigned)(__ballot(dropped) >> 32) : (unsigned)__ballot(dropped)) != 0u;
+        if ((lane & 31) == 0 && q_ok) {
+            p.list_n[(int64_t)bid * kCertQ + q] = n_found;
+            p.list_floor[(int64_t)bid * kCertQ + q] = any_drop ? floor_q : -INFINITY;
+        }
+    }
+}
+
+template <int CHI>
+static hipError_t launch_cert_variant(const ScanI8CertArgs& a, int grid, hipStream_t stream) {
+    constexpr size_t lds_bytes = (size_t)kINBuf * kIWaves * 32 * kIPitch * sizeof(int);
+    static bool attr_set = false;
+    if (!attr_set) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&scan_i8_cert_kernel<CHI>),
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+        if (e != hipSuccess) return e;
+        attr_set = true;
+    }
+    hipLaunchKernelGGL((scan_i8_cert_kernel<CHI>), dim3(grid), dim3(kIThreads), lds_bytes, stream, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_scan_i8_cert(const ScanI8CertArgs& a, int grid, hipStream_t stream) {
+    if (a.row_stride % 512 != 0 || a.row_stride < 512 || a.row_stride > 2048) return hipErrorInvalidValue;
+    if (a.nq < 1 || a.nq > kCertQ || a.n_rows < 0 || grid < 1 || !a.qinfo) return hipErrorInvalidValue;
+    if (!a.sample_out && (!a.list_s || !a.list_r || !a.list_n || !a.list_floor)) return hipErrorInvalidValue;
+    if (a.sample_best && (a.sample_groups < 1 || a.sample_groups > kMaxSampleGroups || a.floor_rank < 1)) return hipErrorInvalidValue;
+    if (a.q_filter_mask && !a.q_filter) return hipErrorInvalidValue;
+    switch ((int)(a.row_stride / 512)) {
+        case 1: return launch_cert_variant<1>(a, grid, stream);
+        case 2: return launch_cert_variant<2>(a, grid, stream);
+        case 3: return launch_cert_variant<3>(a, grid, stream);
+        default: return launch_cert_variant<4>(a, grid, stream);
+    }
 }
 
 }  // namespace rass

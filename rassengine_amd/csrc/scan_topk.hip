@@ -120,6 +120,7 @@ __global__ __launch_bounds__(kThreads, 2) void scan_topk_f32_kernel(ScanArgs p) 
     const int lane = lane_id();
     const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int m = lane & 15, g = lane >> 4;
+    if (p.live_nq != nullptr && __builtin_amdgcn_readfirstlane(*p.live_nq) == 0) return;
     // number of work items: tiles of the slab (flat) or entries of the probe plan (IVF; written
     // by plan_probe_kernel earlier on this stream)
     int G = gridDim.x;
@@ -434,6 +435,7 @@ __global__ __launch_bounds__(kThreads, 2) void scan_topk_f32_wide_kernel(ScanArg
     const int lane = lane_id();
     const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int m = lane & 15, g = lane >> 4;
+    if (p.live_nq != nullptr && __builtin_amdgcn_readfirstlane(*p.live_nq) == 0) return;
     const int n_tiles = (p.n_rows + kTileRows - 1) / kTileRows;
     const int G = gridDim.x;
 

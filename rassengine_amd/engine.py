@@ -233,15 +233,16 @@ class FlatIndex:
         N.check("rass_index_get_rows", self._L.rass_index_get_rows(self._h, int(first_row), int(n), _np_ptr(out)))
         return out
 
-    PREFILTER_MODES = {False: 0, None: 0, 0: 0, "off": 0, True: 1, 1: 1, "bf16": 1, 2: 2, "int8": 2}
+    PREFILTER_MODES = {False: 0, None: 0, 0: 0, "off": 0, True: 1, 1: 1, "bf16": 1, 2: 2, "int8": 2, 3: 3, "int8_exact": 3}
 
     def set_prefilter(self, enable=True) -> None:
         """Candidate scan over a reduced copy of the slab + exact fp32 re-rank; off by default.
-        ``enable``: False / "off", True / "bf16" (half the bytes per pass) or "int8" (a quarter)."""
+        ``enable``: False / "off", True / "bf16" (half the bytes per pass), "int8" (a quarter) or "int8_exact" (the int8 scan
+        with a per-query certificate and an exact fp32 fallback: the flat scan's answers bit for bit, k <= 32)."""
         try:
             mode = self.PREFILTER_MODES[enable]
         except (KeyError, TypeError):
-            raise ValueError(f"prefilter mode must be one of off / bf16 / int8, not {enable!r}") from None
+            raise ValueError(f"prefilter mode must be one of off / bf16 / int8 / int8_exact, not {enable!r}") from None
         N.check("rass_index_set_prefilter", self._L.rass_index_set_prefilter(self._h, mode))
 
     @property
@@ -250,7 +251,40 @@ class FlatIndex:
 
     @property
     def prefilter_mode(self) -> str:
-        return ("off", "bf16", "int8")[int(self._L.rass_index_get_prefilter(self._h))]
+        return ("off", "bf16", "int8", "int8_exact")[int(self._L.rass_index_get_prefilter(self._h))]
+
+    def certify_stats(self) -> dict:
+        """Mode 3 (int8_exact): queries searched, certified and sent to the fp32 fallback since the mode was set, and the
+        certificate's row maxima R and V (synchronises)."""
+        q, c, f = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int64(0)
+        R, V = ctypes.c_float(0.0), ctypes.c_float(0.0)
+        N.check("rass_index_certify_stats",
+                self._L.rass_index_certify_stats(self._h, ctypes.byref(q), ctypes.byref(c), ctypes.byref(f),
+                                                 ctypes.byref(R), ctypes.byref(V)))
+        return {"queries": q.value, "certified": c.value, "fallbacks": f.value, "R": R.value, "V": V.value}
+
+    def candidates_exact_device(self, d_queries, k: int, q_filter=None):
+        """Mode 3's parity hook for <= 32 queries on the device (a torch CUDA fp32 tensor [nq, dim]): (candidate scores f32
+        [nq, 128], LOCAL rows i64 [nq, 128], tau f32 [nq], certified i32 [nq]) as torch tensors (include/rass_engine.h)."""
+        import torch
+        nq = int(d_queries.shape[0])
+        assert d_queries.is_cuda and d_queries.dtype == torch.float32 and d_queries.is_contiguous() and d_queries.shape[1] == self.dim
+        dev = d_queries.device
+        s = torch.empty((nq, 128), dtype=torch.float32, device=dev)
+        r = torch.empty((nq, 128), dtype=torch.int64, device=dev)
+        tau = torch.empty((nq,), dtype=torch.float32, device=dev)
+        cert = torch.empty((nq,), dtype=torch.int32, device=dev)
+        f = None
+        if q_filter is not None:
+            f = torch.as_tensor(np.ascontiguousarray(q_filter, dtype=np.int32)).to(dev)
+        torch.cuda.current_stream().synchronize()     # the engine works on its own stream
+        N.check("rass_index_candidates_exact_device",
+                self._L.rass_index_candidates_exact_device(self._h, ctypes.c_void_p(d_queries.data_ptr()), nq, int(k),
+                                                           ctypes.c_void_p(f.data_ptr()) if f is not None else None,
+                                                           ctypes.c_void_p(s.data_ptr()), ctypes.c_void_p(r.data_ptr()),
+                                                           ctypes.c_void_p(tau.data_ptr()), ctypes.c_void_p(cert.data_ptr())))
+        self.engine.synchronize()
+        return s, r, tau, cert
 
     def candidates_device(self, d_queries, q_filter=None):
         """The active prefilter mode's candidate lists BEFORE the exact re-rank, for <= 32 queries on the device (a torch

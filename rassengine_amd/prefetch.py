@@ -145,7 +145,9 @@ async def run(st) -> None:
         epoch = index_epoch(index)
         # an index in a prefilter mode: the shared scan is the candidate scan too (the top-k of a query's 32 re-ranked candidates
         # is a prefix of their top-16, so what the inline search would return for k <= 16 is in the parked list, bit for bit)
-        approx = bool(getattr(index, "prefilter", False)) and not hasattr(index, "ivf")
+        # (mode 3, "int8_exact", is exact: its answers are the flat scan's for every k <= 32, so it parks a top-32 like mode 0)
+        approx = (bool(getattr(index, "prefilter", False)) and not hasattr(index, "ivf")
+                  and getattr(index, "prefilter_mode", None) != "int8_exact")
         k_pref = K_PREFETCH_APPROX if approx else K_PREFETCH
         batcher, cross = _batcher_for(st)
         with _lock:
