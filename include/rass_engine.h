@@ -558,6 +558,51 @@ int rass_attention_bf16(const void* d_qkv, const int32_t* d_cu_seqlens, int nseq
 int rass_attention_out_bf16(const void* d_qkv, const int32_t* d_cu_seqlens, int nseq, int total_tokens, int hidden,
                             int heads, const void* d_w, const float* d_bias, const void* d_residual, void* d_y, int n,
                             void* stream);
+/* The encoder's other kernels on their own (tests): each is one launch, or the pair of launches, a forward makes, with the
+ * forward's own dispatch and A/B switches (RASS_LN_*, RASS_GEMM_*, read at every call).  Activations are bf16 row-major,
+ * LayerNorm parameters, biases and statistics fp32; row kernels take hidden % 8 == 0, hidden <= 2048 (else
+ * RASS_ERR_UNSUPPORTED).  A launcher's refusal of a shape is RASS_ERR_INVALID. */
+/* Embedding + LayerNorm: out[t] = LayerNorm(word[ids[t]] + pos[p] + type0) for the total_tokens tokens packed by
+ * d_cu_seqlens[nseq + 1], p = t's position in its sequence.  An id < 0 or >= vocab reads row 0; p >= max_pos reads row
+ * max_pos - 1.  word [vocab][hidden], pos [max_pos][hidden], type0 [hidden] bf16; out [total_tokens][hidden]. */
+int rass_embed_layernorm_bf16(const int32_t* d_ids, const int32_t* d_cu_seqlens, int nseq, int total_tokens, const void* d_word,
+                              const void* d_pos, const void* d_type0, const float* d_gamma, const float* d_beta, float eps,
+                              int hidden, int vocab, int max_pos, void* d_out, void* stream);
+/* LayerNorm of `rows` rows: out = (x - mean) * rsqrt(var + eps) * gamma + beta, fp32 two-pass statistics, bf16 out.
+ * From 4 096 rows on the loads are nontemporal (RASS_LN_NT: bit 0 loads, bit 1 stores); the bits do not depend on it. */
+int rass_layernorm_bf16(const void* d_in, const float* d_gamma, const float* d_beta, float eps, int rows, int hidden,
+                        void* d_out, void* stream);
+/* out = LayerNorm(bf16(x w^T + bias + residual)), the attention-output / FFN-down step: x [m_pad][k], w [n][k], residual,
+ * y, out [m_pad][n].  d_ws == NULL: the GEMM (epilogue 1) into y, then rass_layernorm_bf16 of y.  With an fp32 scratch the
+ * encoder's own choice for m: few rows take the one-launch GEMM (K of 4 096: four K slices and one reduce + residual +
+ * LayerNorm launch), mid-size ones split K with the reduction fused into the LayerNorm (y is then not written).
+ * `residual` may be `out`.  Rows m .. m_pad - 1 of y and out are not written. */
+int rass_gemm_bf16_residual_layernorm(const void* d_x, const void* d_w, const float* d_bias, const void* d_residual, void* d_y,
+                                      const float* d_gamma, const float* d_beta, float eps, void* d_out, int m, int m_pad, int n,
+                                      int k, void* d_ws, size_t ws_bytes, void* stream);
+/* A query's FFN-up: y = epi(LayerNorm(yin) w^T + bias), epilogue 0 bias / 2 bias + GELU(erf), with the LayerNorm's rows
+ * (the bits rass_layernorm_bf16 writes) also stored to x_out.  1 <= m <= 32, k = 1024, n % 16 == 0, n >= 1024, else
+ * RASS_ERR_UNSUPPORTED.  yin, x_out [m][1024], y [m][n]. */
+int rass_gemm_bf16_ln_input(const void* d_yin, const float* d_gamma, const float* d_beta, float eps, void* d_x_out, const void* d_w,
+                            const float* d_bias, void* d_y, int m, int n, int k, int epilogue, void* stream);
+/* LayerNorm folded into its consumer's weights: w2[n][k] = bf16(w[n][k] * gamma[k]), colsum[n] = sum_k w2[n][k] (fp32),
+ * bias2[n] = bias[n] + sum_k beta[k] * w[n][k]. */
+int rass_fold_gamma_bf16(const void* d_w, const float* d_gamma, const float* d_beta, const float* d_bias, int n, int k, void* d_w2,
+                         float* d_colsum, float* d_bias2, void* stream);
+/* The GEMMs of the folded-LayerNorm forward (big batches).  mr [m][2] holds a (mean, rstd) per row.  Epilogue 3:
+ * y = bf16(x w^T + bias + LN(residual_raw)), LN rebuilt from (mr, gamma, beta), and stats [m][n / 128][2] receives each
+ * 128-column chunk's (sum, sum of squares) of the stored y.  Epilogue 4 / 5: y = rstd * (x w2^T - mean * colsum) + bias2
+ * [+ GELU], from rass_fold_gamma_bf16's outputs.  m >= 1024, m_pad % 256 == 0, n % 256 == 0, k % 64 == 0, k >= 128 and
+ * >= 192 tiles of 256 x 256, else RASS_ERR_UNSUPPORTED.  Rows m .. m_pad - 1 of y are not written. */
+int rass_gemm_bf16_fold(const void* d_x, const void* d_w, const float* d_bias, const void* d_residual_raw, void* d_y, int m,
+                        int m_pad, int n, int k, int epilogue, const float* d_mr, const float* d_gamma, const float* d_beta,
+                        float* d_stats, const float* d_colsum, void* stream);
+/* stats [rows][n / 128][2] of epilogue 3 -> mr [rows][2] = (mean, rsqrt(var + eps)), summed in chunk order. */
+int rass_ln_stats_finalize(const float* d_stats, int rows, int n, float eps, float* d_mr, void* stream);
+/* Pooling: out[s] = the mean over sequence s's tokens (mode_mean) or its first token, fp32 [nseq][hidden]; normalize:
+ * e / (||e|| + 1e-9).  An empty sequence gives zeros. */
+int rass_pool_bf16(const void* d_x, const int32_t* d_cu_seqlens, int nseq, int hidden, int mode_mean, int normalize,
+                   float* d_out, void* stream);
 
 /* -------------------------------------------------------------- tokenizer
  * BERT (uncased) BasicTokenizer + WordPiece on the host (C++), replacing the

@@ -35,6 +35,15 @@ int efail(int code, const std::string& msg) {
     return code;
 }
 
+// the stand-alone launchers' result: a launcher refuses what it cannot run with hipErrorInvalidValue
+int launch_rc(hipError_t err, const char* what) {
+    if (err == hipSuccess) return RASS_OK;
+    return efail(RASS_ERR_INVALID, std::string(what) + ": " + hipGetErrorString(err));
+}
+
+// the row kernels' range (encoder_misc.hip): one wave per row, 8 columns per lane and step, up to 4 steps
+bool row_width_ok(int hidden) { return hidden > 0 && hidden % 8 == 0 && hidden <= 2048; }
+
 #define EHIP_TRY(expr)                                                                                  \
     do {                                                                                                \
         hipError_t _e = (expr);                                                                         \
@@ -574,6 +583,99 @@ int rass_attention_out_bf16(const void* d_qkv, const int32_t* d_cu_seqlens, int 
                                                  d_y, n, reinterpret_cast<hipStream_t>(stream));
     if (err != hipSuccess) return efail(RASS_ERR_INVALID, std::string("fused attention launch: ") + hipGetErrorString(err));
     return RASS_OK;
+}
+
+/* The encoder's row kernels and LayerNorm-bearing GEMM launches on their own (tests): each maps to one launcher of
+ * encoder_kernels.h with the same arguments and the same dispatch the encoder's forward takes. */
+int rass_embed_layernorm_bf16(const int32_t* d_ids, const int32_t* d_cu_seqlens, int nseq, int total_tokens, const void* d_word,
+                              const void* d_pos, const void* d_type0, const float* d_gamma, const float* d_beta, float eps,
+                              int hidden, int vocab, int max_pos, void* d_out, void* stream) {
+    rass::rass_env_new_scope();
+    if (!d_ids || !d_cu_seqlens || !d_word || !d_pos || !d_type0 || !d_gamma || !d_beta || !d_out)
+        return efail(RASS_ERR_INVALID, "NULL argument");
+    if (nseq < 1 || total_tokens < 0 || vocab < 1 || max_pos < 1) return efail(RASS_ERR_INVALID, "nseq, vocab, max_pos >= 1");
+    if (!row_width_ok(hidden)) return efail(RASS_ERR_UNSUPPORTED, "embedding LayerNorm: hidden % 8 == 0, <= 2048");
+    return launch_rc(rass::launch_embed_layernorm(d_ids, d_cu_seqlens, nseq, total_tokens, d_word, d_pos, d_type0, d_gamma, d_beta,
+                                                  eps, hidden, vocab, max_pos, d_out, reinterpret_cast<hipStream_t>(stream)),
+                     "embedding LayerNorm launch");
+}
+
+int rass_layernorm_bf16(const void* d_in, const float* d_gamma, const float* d_beta, float eps, int rows, int hidden, void* d_out,
+                        void* stream) {
+    rass::rass_env_new_scope();
+    if (!d_in || !d_gamma || !d_beta || !d_out) return efail(RASS_ERR_INVALID, "NULL argument");
+    if (rows < 0) return efail(RASS_ERR_INVALID, "rows < 0");
+    if (!row_width_ok(hidden)) return efail(RASS_ERR_UNSUPPORTED, "LayerNorm: hidden % 8 == 0, <= 2048");
+    return launch_rc(rass::launch_layernorm(d_in, d_gamma, d_beta, eps, rows, hidden, d_out, reinterpret_cast<hipStream_t>(stream)),
+                     "LayerNorm launch");
+}
+
+int rass_gemm_bf16_residual_layernorm(const void* d_x, const void* d_w, const float* d_bias, const void* d_residual, void* d_y,
+                                      const float* d_gamma, const float* d_beta, float eps, void* d_out, int m, int m_pad, int n,
+                                      int k, void* d_ws, size_t ws_bytes, void* stream) {
+    rass::rass_env_new_scope();
+    if (!d_x || !d_w || !d_bias || !d_residual || !d_y || !d_gamma || !d_beta || !d_out)
+        return efail(RASS_ERR_INVALID, "NULL argument");
+    if (!row_width_ok(n)) return efail(RASS_ERR_UNSUPPORTED, "residual + LayerNorm: n % 8 == 0, <= 2048");
+    return launch_rc(rass::launch_gemm_bf16_residual_layernorm(d_x, d_w, d_bias, d_residual, d_y, d_gamma, d_beta, eps, d_out, m,
+                                                               m_pad, n, k, reinterpret_cast<hipStream_t>(stream),
+                                                               d_ws ? static_cast<float*>(d_ws) : nullptr, d_ws ? ws_bytes : 0),
+                     "GEMM + residual + LayerNorm launch");
+}
+
+int rass_gemm_bf16_ln_input(const void* d_yin, const float* d_gamma, const float* d_beta, float eps, void* d_x_out, const void* d_w,
+                            const float* d_bias, void* d_y, int m, int n, int k, int epilogue, void* stream) {
+    rass::rass_env_new_scope();
+    if (!d_yin || !d_gamma || !d_beta || !d_x_out || !d_w || !d_bias || !d_y) return efail(RASS_ERR_INVALID, "NULL argument");
+    if (epilogue != 0 && epilogue != 2) return efail(RASS_ERR_INVALID, "epilogue 0 or 2");
+    if (!rass::gemm_bf16_ln_input_ok(m, n, k))
+        return efail(RASS_ERR_UNSUPPORTED, "LayerNorm-input GEMM: 1..32 rows, k = 1024, n % 16 == 0, n >= 1024 (and RASS_GEMM_FEWROWS != 0)");
+    return launch_rc(rass::launch_gemm_bf16_ln_input(d_yin, d_gamma, d_beta, eps, d_x_out, d_w, d_bias, d_y, m, n, k, epilogue,
+                                                     reinterpret_cast<hipStream_t>(stream)),
+                     "LayerNorm-input GEMM launch");
+}
+
+int rass_fold_gamma_bf16(const void* d_w, const float* d_gamma, const float* d_beta, const float* d_bias, int n, int k, void* d_w2,
+                         float* d_colsum, float* d_bias2, void* stream) {
+    rass::rass_env_new_scope();
+    if (!d_w || !d_gamma || !d_beta || !d_bias || !d_w2 || !d_colsum || !d_bias2) return efail(RASS_ERR_INVALID, "NULL argument");
+    if (n < 1 || k < 1) return efail(RASS_ERR_INVALID, "n, k >= 1");
+    return launch_rc(rass::launch_fold_gamma(d_w, d_gamma, d_beta, d_bias, n, k, d_w2, d_colsum, d_bias2,
+                                             reinterpret_cast<hipStream_t>(stream)),
+                     "gamma fold launch");
+}
+
+int rass_gemm_bf16_fold(const void* d_x, const void* d_w, const float* d_bias, const void* d_residual_raw, void* d_y, int m,
+                        int m_pad, int n, int k, int epilogue, const float* d_mr, const float* d_gamma, const float* d_beta,
+                        float* d_stats, const float* d_colsum, void* stream) {
+    rass::rass_env_new_scope();
+    if (!d_x || !d_w || !d_bias || !d_y || !d_mr) return efail(RASS_ERR_INVALID, "NULL argument");
+    if (epilogue == 3 ? (!d_residual_raw || !d_gamma || !d_beta || !d_stats) : epilogue == 4 || epilogue == 5 ? !d_colsum : true)
+        return efail(RASS_ERR_INVALID, "epilogue 3 (residual_raw, gamma, beta, stats) or 4 / 5 (colsum)");
+    if (!rass::gemm_bf16_fold_shape_ok(m, m_pad, n, k))
+        return efail(RASS_ERR_UNSUPPORTED, "folded-LayerNorm GEMM: m >= 1024, n % 256 == 0, m_pad % 256 == 0, k % 64 == 0, k >= 128, >= 192 tiles of 256^2");
+    return launch_rc(rass::launch_gemm_bf16_fold(d_x, d_w, d_bias, d_residual_raw, d_y, m, m_pad, n, k, epilogue, d_mr, d_gamma, d_beta,
+                                                 d_stats, d_colsum, reinterpret_cast<hipStream_t>(stream)),
+                     "folded-LayerNorm GEMM launch");
+}
+
+int rass_ln_stats_finalize(const float* d_stats, int rows, int n, float eps, float* d_mr, void* stream) {
+    rass::rass_env_new_scope();
+    if (!d_stats || !d_mr) return efail(RASS_ERR_INVALID, "NULL argument");
+    if (rows < 0 || n < 128 || n % 128 != 0) return efail(RASS_ERR_INVALID, "rows >= 0, n % 128 == 0");
+    return launch_rc(rass::launch_ln_stats_finalize(d_stats, rows, n, eps, d_mr, reinterpret_cast<hipStream_t>(stream)),
+                     "LayerNorm statistics launch");
+}
+
+int rass_pool_bf16(const void* d_x, const int32_t* d_cu_seqlens, int nseq, int hidden, int mode_mean, int normalize, float* d_out,
+                   void* stream) {
+    rass::rass_env_new_scope();
+    if (!d_x || !d_cu_seqlens || !d_out) return efail(RASS_ERR_INVALID, "NULL argument");
+    if (nseq < 0) return efail(RASS_ERR_INVALID, "nseq < 0");
+    if (!row_width_ok(hidden)) return efail(RASS_ERR_UNSUPPORTED, "pooling: hidden % 8 == 0, <= 2048");
+    return launch_rc(rass::launch_pool(d_x, d_cu_seqlens, nseq, hidden, mode_mean ? 1 : 0, normalize ? 1 : 0, d_out,
+                                       reinterpret_cast<hipStream_t>(stream)),
+                     "pooling launch");
 }
 
 }  // extern "C"

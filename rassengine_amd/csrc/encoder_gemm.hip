@@ -1824,6 +1824,8 @@ static bool p5_eligible(int M, int M_pad, int N, int K) {
     return N % RBN == 0 && M_pad % RBM == 0 && K % 64 == 0 && K >= 128 && M >= 1024 && (int64_t)(N / RBN) * (M_pad / RBM) >= 192;
 }
 
+bool gemm_bf16_fold_shape_ok(int M, int M_pad, int N, int K) { return p5_eligible(M, M_pad, N, K); }
+
 bool gemm_bf16_fold_ok(int M, int M_pad, int hidden, int intermediate) {
     if (const char* v = rass_env("RASS_ENCODER_LN_FOLD"))
         if (atoi(v) == 0) return false;

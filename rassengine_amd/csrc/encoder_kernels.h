@@ -49,6 +49,7 @@ hipError_t launch_splitk_residual_layernorm(const float* partial, int S, int row
 // epilogue 4 / 5: Y = rstd * (X W'^T - mean * colsum) + bias'  [ + GELU ], X raw rows with (mean, rstd) in `mr`, W' / colsum /
 //   bias' from launch_fold_gamma.  launch_ln_stats_finalize: stats -> mr [M][2] (mean, rstd), fixed summation order.
 bool gemm_bf16_fold_ok(int M, int M_pad, int hidden, int intermediate);
+bool gemm_bf16_fold_shape_ok(int M, int M_pad, int N, int K);   // one GEMM of the fold: the shapes launch_gemm_bf16_fold takes
 hipError_t launch_gemm_bf16_fold(const void* X, const void* W, const float* bias, const void* residual_raw, void* Y, int M,
                                  int M_pad, int N, int K, int epilogue, const float* mr, const float* gamma, const float* beta,
                                  float* stats, const float* colsum, hipStream_t stream);
