@@ -224,6 +224,7 @@ int rass_index_search_device_after(rass_index_t* idx, const float* d_queries, in
  * that of rass_index_search_device on consecutive groups of RASS_MAX_QBATCH queries, but on an fp32 index the
  * batch shares ONE normalise launch and ONE merge launch and runs the groups' score-floor sample passes back to
  * back ahead of the big scans, so the serial tail a lone group pays after its scan is paid once.
+ * Consecutive full groups are scanned two per corpus pass (64 queries per launch; RASS_SCAN_BATCH_PAIR=0: one launch per group).
  * This is the shape of the reference's load: embed_texts_in_batches / ask() under concurrent users hand the
  * engine many queries at once (app/main.py:1536-1560 is called per request; the micro-batcher coalesces them).
  * Group g's results go to d_out_scores + g * out_scores_group_stride (floats) and d_out_ids + g *
@@ -638,7 +639,9 @@ int rass_timer_elapsed_ms(rass_timer_t* t, float* ms);
 
 /* Bracket every scan-kernel launch the engine makes with a hipEvent pair on
  * the engine stream (up to max_launches launches), then read back the summed
- * kernel time: bench.py's live per-kernel duration for the roofline figure. */
+ * kernel time: bench.py's live per-kernel duration for the roofline figure.
+ * `launches` counts launch GROUPS of <= RASS_MAX_QBATCH queries: a batch call's 64-query corpus pass, which serves
+ * two groups in one kernel launch, counts as two (its time is summed once). */
 int rass_engine_kernel_timing_begin(rass_engine_t* eng, int max_launches);
 int rass_engine_kernel_timing_end(rass_engine_t* eng, double* total_ms,
                                   int* launches);

@@ -185,6 +185,7 @@ struct rass_engine {
     // optional HIP-event bracket around every scan kernel launch (bench.py's roofline leg)
     std::vector<hipEvent_t> ev_pool;  // pairs: [2i] before, [2i+1] after
     int ev_used = 0;                  // pairs recorded since timing_begin
+    int ev_extra = 0;                 // launch groups beyond one that recorded launches served (a 64-query pair pass: +1)
     bool ev_on = false;
 };
 
@@ -1333,6 +1334,14 @@ static bool scan_batch_one_sample() {
     return !(e && e[0] == 'g');
 }
 
+static bool scan_batch_pair() {
+    static const bool on = [] {   // read once
+        const char* e = getenv("RASS_SCAN_BATCH_PAIR");
+        return !(e && e[0] == '0');
+    }();
+    return on;
+}
+
 // The fused batch of rass_index_search_device_batch on an fp32 flat index: the per-group steps of scan_launch, but
 // ONE normalise launch and ONE merge launch for the whole batch, and the groups' sample passes back to back (their
 // 64 * grid rows stay in the Infinity Cache between them) ahead of the big scans.  Per 32 queries the serial tail
@@ -1437,15 +1446,31 @@ int scan_launch_batch(rass_index* idx, const float* d_queries, int nq, int k, co
             s.part_ids = nullptr;
             HIP_TRY(rass::launch_scan_topk_f32(s, grid, st));
         }
+    // Consecutive FULL groups go two per corpus pass (scan_topk_f32_pair_kernel: 64 queries per launch, the lists of both
+    // groups written where the two launches would write them, bit for bit the same); an odd last full group and a ragged
+    // last group keep the 32-query kernel.  RASS_SCAN_BATCH_PAIR=0: one launch per group (the A/B).
+    const bool pairs = scan_batch_pair() && rass::scan_pair_supported_stride(stride);
     for (int g = 0; g < groups; ++g) {
         rass::ScanArgs a = group_args(g);
         if (sample && a.nq > 16) {
             a.sample_best = sample_best + (int64_t)g * 32 * rass::kMaxSampleGroups;
             a.sample_groups = sample_wgs;
         }
+        const bool pair = pairs && a.nq == RASS_MAX_QBATCH && (g + 2) * RASS_MAX_QBATCH <= nq;
+        if (pair) {
+            a.nq = 2 * RASS_MAX_QBATCH;
+            a.q_group_stride = 32 * stride;
+            a.part_group_stride = (int64_t)L.part_per_group;
+            a.xcd_skew = (grid == eng->n_cus && grid % 8 == 0) ? scan_xcd_skew(a.nq) : 0;
+        }
         const bool timed = eng->ev_on && (size_t)(2 * eng->ev_used + 1) < eng->ev_pool.size();
         if (timed) HIP_TRY(hipEventRecord(eng->ev_pool[2 * eng->ev_used], st));
-        HIP_TRY(rass::launch_scan_topk_f32(a, grid, st));
+        if (pair) {
+            HIP_TRY(rass::launch_scan_topk_f32_pair(a, grid, st));
+            ++g;
+            if (timed) eng->ev_extra += 1;   // kernel_timing_end counts launch GROUPS: this pass served two
+        } else
+            HIP_TRY(rass::launch_scan_topk_f32(a, grid, st));
         if (timed) {
             HIP_TRY(hipEventRecord(eng->ev_pool[2 * eng->ev_used + 1], st));
             eng->ev_used += 1;
@@ -2372,6 +2397,7 @@ int rass_engine_kernel_timing_begin(rass_engine_t* eng, int max_launches) {
         eng->ev_pool.push_back(e);
     }
     eng->ev_used = 0;
+    eng->ev_extra = 0;
     eng->ev_on = true;
     return RASS_OK;
 }
@@ -2389,8 +2415,9 @@ int rass_engine_kernel_timing_end(rass_engine_t* eng, double* total_ms, int* lau
         sum += ms;
     }
     *total_ms = sum;
-    *launches = eng->ev_used;
+    *launches = eng->ev_used + eng->ev_extra;
     eng->ev_used = 0;
+    eng->ev_extra = 0;
     return RASS_OK;
 }
 

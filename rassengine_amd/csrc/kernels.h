@@ -72,6 +72,12 @@ struct ScanArgs {
 
 bool scan_supported_stride(int64_t row_stride);
 hipError_t launch_scan_topk_f32(const ScanArgs& a, int grid, hipStream_t stream);
+// Two consecutive FULL launch groups of a flat fp32 scan in one corpus pass (scan_topk_f32_pair_kernel): a.nq = 64; queries
+// 0..31 are addressed as launch_scan_topk_f32 would address group g's (q_padded, q_filter, sample_best, part_*: lists
+// [grid][32][k]), queries 32..63 at q_padded + q_group_stride, q_filter + 32, sample_best + 32 * kMaxSampleGroups and
+// part_* + part_group_stride.  Same scores and lists, bit for bit, as the two launches it replaces.  No EXT, no work list.
+bool scan_pair_supported_stride(int64_t row_stride);
+hipError_t launch_scan_topk_f32_pair(const ScanArgs& a, int grid, hipStream_t stream);
 
 // [n_lists][nq][k] sorted candidate lists -> [nq][k]; n_lists * k <= kMergeMaxCandidates.
 constexpr int kMergeMaxCandidates = 8192;

@@ -161,6 +161,55 @@ __device__ __forceinline__ void multiply_and_refill(TileRegs<CH>& r, const f32x4
     }
 }
 
+// ---- the 64-query pair kernel's half-tile blocks (scan_topk.hip, scan_topk_f32_pair_kernel) ---------------------------------
+// One 16-row block (half a tile) of A fragments for one wave: CH chunks of 16 B per lane.  The pair kernel multiplies a tile
+// as two such blocks, each against 4 N-tiles of queries, where TileRegs / multiply_and_refill multiply two blocks against 2.
+template <int CH>
+struct HalfRegs {
+    f32x4 a[CH];
+};
+
+// `soff0`: byte offset of the block inside its tile (0, or mt_step for the second block).  The sched_barrier per load keeps
+// the prologue's loads in the order the main loop re-issues them: hipcc reorders them otherwise, and its s_waitcnt counts in
+// the loop — merged over the loop entry and the back edge — then wait for nearly every load in flight at the first chunks
+// of every iteration (vmcnt(3) of 17 where vmcnt(16) serves).
+template <int CH>
+__device__ __forceinline__ void issue_half_loads(HalfRegs<CH>& r, const TileDesc& d, int voff_lane, int soff0) {
+#pragma unroll
+    for (int j = 0; j < CH; ++j) {
+        r.a[j] = load_chunk(d, voff_lane, soff0 + j * 1024);
+        __builtin_amdgcn_sched_barrier(0);
+    }
+}
+
+// multiply_and_refill for one block: the same k-ordered v_mfma_f32_16x16x4_f32 chain per (row, query) from zero — so the same
+// partial, bit for bit — with the NT accumulators advanced round-robin (NT - 1 >= 2 independent MFMAs between a producer and
+// its consumer), each consumed register re-loaded from the same block of the `next` tile, and between(j) after chunk j.
+template <int CH, int NT, typename Between>
+__device__ __forceinline__ void multiply_and_refill_half(HalfRegs<CH>& r, const f32x4 (&qf)[NT][CH], f32x4 (&acc)[NT],
+                                                         const TileDesc& next, int voff_lane, int soff0,
+                                                         Between&& between) {
+    static_assert(NT >= 3, "a dependent MFMA issues 40 cycles after its producer: keep two others between them");
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt) acc[nt] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int j = 0; j < CH; ++j) {
+        const f32x4 a0 = r.a[j];
+#define RASS_KSTEP(comp)                                                                                              \
+    _Pragma("unroll") for (int nt = 0; nt < NT; ++nt)                                                                 \
+        acc[nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.comp, qf[nt][j].comp, acc[nt], 0, 0, 0);
+        RASS_KSTEP(x)
+        RASS_KSTEP(y)
+        RASS_KSTEP(z)
+        RASS_KSTEP(w)
+#undef RASS_KSTEP
+        r.a[j] = load_chunk(next, voff_lane, soff0 + j * 1024);
+        __builtin_amdgcn_sched_barrier(0);
+        between(j);
+        __builtin_amdgcn_sched_barrier(0);
+    }
+}
+
 // Order-preserving u32 key of a finite float score (larger score <-> larger key; every finite score's key is
 // >= 0x00800000, so 0 can stand for "no score"): the sample floor's selection counts keys by ballot.
 __device__ __forceinline__ unsigned score_key(float s) {

@@ -313,7 +313,8 @@ __global__ __launch_bounds__(kThreads, 2) void scan_topk_f32_kernel(ScanArgs p) 
     // iteration: it orders this iteration's dumps before the next iteration's reads, and the next iteration's
     // dumps (into the images read now) behind this iteration's reads.
     constexpr int kParts = 2 * NT;
-    auto slot_of = [](int part) { return ((part + 1) * 2 * CH) / kParts - 1; };
+    // (max: at CH = 1, NT = 2 there are 2 slots for 4 parts and part 0 would land in slot -1 — never ranked, its rows lost)
+    auto slot_of = [](int part) { return max(((part + 1) * 2 * CH) / kParts - 1, 0); };
     WorkItem Pa{0, 0, 0u}, Pb{0, 0, 0u};  // the previous pair (rows = 0: nothing ranks in the first iteration)
     int pair = 0;  // 0 / 2: which two LDS images this iteration dumps into
     while (t < n_tiles) {
@@ -393,6 +394,197 @@ __global__ __launch_bounds__(kThreads, 2) void scan_topk_f32_kernel(ScanArgs p) 
         const int q = pq * 16 + (lane >> 5) * 8 + wid;
         if (q < p.nq && lpos < p.k) {
             const int64_t o = ((int64_t)bid * p.nq + q) * p.k + lpos;
+            const bool filled = L[pq].i != 0x7fffffff;
+            p.part_scores[o] = filled ? L[pq].s : -INFINITY;
+            p.part_ids[o] = filled ? (p.id_base + (int64_t)L[pq].i) : (int64_t)-1;
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------
+// 64 queries per corpus pass: TWO consecutive full launch groups of a batch call in one launch (api.hip,
+// scan_launch_batch).  At 32 queries per pass the kernel above sits in the corner of the HBM rate and the fp32 MFMA
+// rate; a step of 1 024 queries streams the corpus 32 times.  This sibling streams it 16 times: the same 512 threads,
+// the same K split over the 8 waves and the same v_mfma_f32_16x16x4_f32 chain per (row, query) in k order from zero,
+// the same p0 + ... + p7 sum of the partials — so every score is the kernel above's, bit for bit — but a tile is
+// multiplied as two 16-row blocks against 4 N-tiles of queries (HalfRegs / multiply_and_refill_half, scan_core.h)
+// instead of two blocks together against 2.  Registers at CH = 8: 128 for the query fragments (64 above), 2 x 32 for
+// the two blocks of ONE tile in flight (2 x 64 above: half the bytes per MFMA want half the bytes in flight), 16
+// accumulators.  The LDS image of a tile is [kWaves][64][kPitch]: block 0's rows in columns 0..15, block 1's in
+// 16..31, so the dump and the ranking address it exactly as above (same pitch, same bank pattern), and a half-wave
+// still ranks the 32 rows of a tile for one query in ascending row order.  One tile and one barrier per iteration
+// (256 MFMAs per wave, as above), two images; the previous tile's ranking is cut into 4 parts (one per N-tile: a wave
+// owns queries pq * 16 + {0, 8} + wid, 8 of them) placed between the MFMA chunks.
+// Queries 0..31 are group g's (q_padded, q_filter, sample_best, part_*), 32..63 group g + 1's: q_padded +
+// q_group_stride, q_filter + 32, sample_best + 32 * kMaxSampleGroups, part_* + part_group_stride — where the two
+// launches it replaces read and write.  Flat scans without EXT only.
+template <int CH>
+__global__ __launch_bounds__(kThreads, 2) void scan_topk_f32_pair_kernel(ScanArgs p) {
+    constexpr int NT = 4, NQ = 64;
+    extern __shared__ __attribute__((aligned(16))) float lds[];  // [2][kWaves][NQ][kPitch]
+
+    const int lane = lane_id();
+    const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int m = lane & 15, g = lane >> 4;
+    const int G = gridDim.x, bid = blockIdx.x;
+    const int n_tiles = (p.n_rows + kTileRows - 1) / kTileRows;
+
+    // Query fragments: lane (n = m, g) holds Qn[nt*16 + n][slice + 16j + 4g .. +3]; N-tiles 2, 3 are the second group's.
+    f32x4 qf[NT][CH];
+    {
+        const float* qbase = p.q_padded + (int64_t)m * p.row_stride + wid * 16 * CH + 4 * g;
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) {
+            const float* qn = qbase + (int64_t)(nt >> 1) * p.q_group_stride + (int64_t)(nt & 1) * 16 * p.row_stride;
+#pragma unroll
+            for (int j = 0; j < CH; ++j) qf[nt][j] = *reinterpret_cast<const f32x4*>(qn + 16 * j);
+        }
+    }
+    const int voff_lane = wid * CH * 1024 + lane * 16;
+
+    // Top-k state: pass pq handles query pq*16 + (lane>>5)*8 + wid for row lane&31.
+    TopList L[NT];
+    float tau[NT];
+#pragma unroll
+    for (int pq = 0; pq < NT; ++pq) {
+        L[pq].s = -INFINITY;
+        L[pq].i = 0x7fffffff;
+        tau[pq] = -INFINITY;
+    }
+    __shared__ int sh_qfilt[NQ];
+    __shared__ float sh_floor[NQ];
+    __shared__ int sh_tags[2][32];
+    if (threadIdx.x < NQ) {
+        sh_qfilt[threadIdx.x] = p.q_filter != nullptr ? p.q_filter[threadIdx.x] : -1;
+        sh_floor[threadIdx.x] = -INFINITY;
+    }
+    __syncthreads();
+
+    const int mt_step = 16 * (int)p.row_stride * 4;
+    HalfRegs<CH> R0, R1;  // the two 16-row blocks of the tile being multiplied; each register is refilled from the next tile
+    int tag;
+    ItemSeq seq(bid, G, (G & 1) ? 0 : p.xcd_skew);
+    int t = seq.next();
+    WorkItem W0 = get_work<kFlat>(p, t, n_tiles);
+    {
+        const TileDesc d = make_tile_desc(p.corpus, p.row_stride, p.row_tag, W0);
+        tag = load_tag(d);
+        __builtin_amdgcn_sched_barrier(0);
+        issue_half_loads<CH>(R0, d, voff_lane, 0);
+        issue_half_loads<CH>(R1, d, voff_lane, mt_step);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+
+    // The sample floors of this wave's 8 queries, as in the kernel above (same keys, same selection, same floors), one
+    // launch group after the other: the keys of 4 queries take 16 registers next to the 128 of the query fragments.
+    if (p.sample_best != nullptr) {
+        constexpr int kFloorBits = 20;
+#pragma unroll 1
+        for (int h = 0; h < 2; ++h) {
+            unsigned best_key[2][2][kMaxSampleGroups / 64];
+#pragma unroll
+            for (int pq = 0; pq < 2; ++pq)
+#pragma unroll
+                for (int half = 0; half < 2; ++half)
+#pragma unroll
+                    for (int j = 0; j < kMaxSampleGroups / 64; ++j) {
+                        const int grp = lane + 64 * j;
+                        const int q = h * 32 + pq * 16 + half * 8 + wid;
+                        const float v = grp < p.sample_groups ? p.sample_best[q * kMaxSampleGroups + grp] : -INFINITY;
+                        best_key[pq][half][j] = v == -INFINITY ? 0u : score_key(v);
+                    }
+            unsigned T[2][2] = {};
+#pragma unroll 1
+            for (int b = 31; b >= 32 - kFloorBits; --b) {
+#pragma unroll
+                for (int pq = 0; pq < 2; ++pq)
+#pragma unroll
+                    for (int half = 0; half < 2; ++half) {
+                        const unsigned cand = T[pq][half] | (1u << b);
+                        int c = 0;
+#pragma unroll
+                        for (int j = 0; j < kMaxSampleGroups / 64; ++j) c += __popcll(__ballot(best_key[pq][half][j] >= cand));
+                        T[pq][half] = c >= p.k ? cand : T[pq][half];
+                    }
+            }
+#pragma unroll
+            for (int pq = 0; pq < 2; ++pq)
+#pragma unroll
+                for (int half = 0; half < 2; ++half)
+                    if (lane == 0) sh_floor[h * 32 + pq * 16 + half * 8 + wid] = T[pq][half] ? key_score(T[pq][half]) : -INFINITY;
+        }
+    }
+
+    auto dump_half = [&](const f32x4 (&acc)[NT], int buf, int blk) {
+        float* P = lds + buf * (kWaves * NQ * kPitch);
+        // lane (n=m, g) holds rows 4g..4g+3 of block blk for query nt*16+n
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt)
+            *reinterpret_cast<f32x4*>(P + (wid * NQ + nt * 16 + m) * kPitch + blk * 16 + 4 * g) = acc[nt];
+    };
+    // Rank one (tile, N-tile pq) of a dumped tile: sum the 8 K-partials in fixed order, filter, insert.
+    auto rank_part = [&](const WorkItem& w, int buf, int pq) {
+#ifndef RASS_SCAN_PAIR_NORANK  // the timing-only build of the go / no-go experiment (profiles/r05_scan_pair_experiment.txt)
+        const float* P = lds + buf * (kWaves * NQ * kPitch);
+        const int r = lane & 31;
+        const int row = w.tile * kTileRows + r;
+        const int tag_r = sh_tags[buf][r];
+        const int q = pq * 16 + (lane >> 5) * 8 + wid;
+        const int qf1 = sh_qfilt[q];
+        const float* src = P + q * kPitch + r;
+        float s = src[0];
+#pragma unroll
+        for (int wv = 1; wv < kWaves; ++wv) s += src[wv * NQ * kPitch];
+        // the sample floor: k rows of the corpus already score >= floor_q (ties are kept: the id order decides them in the merge)
+        const bool ok = (r < w.rows) && (tag_r != -1) && (qf1 < 0 || qf1 == tag_r) && (s >= sh_floor[q]);
+        s = ok ? s : -INFINITY;
+        insert_candidates(L[pq], tau[pq], s, row, p.k);
+#endif
+    };
+
+    // Main loop.  Iteration i multiplies tile i's two blocks and, between the MFMA chunks, ranks tile i-1 out of the
+    // image iteration i-1 dumped (4 parts over the 2 x CH chunk slots).  One barrier per iteration: it orders this
+    // iteration's dumps before the next iteration's reads, and the next iteration's dumps (into the image read now)
+    // behind this iteration's reads.
+    auto slot_of = [](int part) { return ((part + 1) * 2 * CH + NT - 1) / NT - 1; };
+    WorkItem Pw{0, 0, 0u};  // the previous tile (rows = 0: nothing ranks in the first iteration)
+    int cur = 0;            // which LDS image this iteration dumps into
+    while (t < n_tiles) {
+        f32x4 acc[NT];
+        if (wid == 0 && lane < 32) sh_tags[cur][lane] = tag;
+        const WorkItem Wc = W0;
+        t = seq.next();
+        const WorkItem Wn = get_work<kFlat>(p, t, n_tiles);
+        const TileDesc dn = make_tile_desc(p.corpus, p.row_stride, p.row_tag, Wn);
+        tag = load_tag(dn);
+        auto rank_prev = [&](int slot) {
+#pragma unroll
+            for (int part = 0; part < NT; ++part)
+                if (slot_of(part) == slot) rank_part(Pw, cur ^ 1, part);
+        };
+        multiply_and_refill_half<CH, NT>(R0, qf, acc, dn, voff_lane, 0, [&](int j) { rank_prev(j); });
+        dump_half(acc, cur, 0);
+        multiply_and_refill_half<CH, NT>(R1, qf, acc, dn, voff_lane, mt_step, [&](int j) { rank_prev(CH + j); });
+        dump_half(acc, cur, 1);
+        W0 = Wn;
+        Pw = Wc;
+        __syncthreads();
+        cur ^= 1;
+    }
+    // the last tile
+#pragma unroll
+    for (int pq = 0; pq < NT; ++pq) rank_part(Pw, cur ^ 1, pq);
+#ifdef RASS_SCAN_PAIR_NORANK
+    L[0].s = lds[threadIdx.x];  // keeps the dumps alive
+#endif
+
+    // Per-workgroup sorted lists -> [gridDim.x][32][k] of each of the two groups
+    const int lpos = lane & 31;
+#pragma unroll
+    for (int pq = 0; pq < NT; ++pq) {
+        const int ql = (pq & 1) * 16 + (lane >> 5) * 8 + wid;
+        if (lpos < p.k) {
+            const int64_t o = (int64_t)(pq >> 1) * p.part_group_stride + ((int64_t)bid * 32 + ql) * p.k + lpos;
             const bool filled = L[pq].i != 0x7fffffff;
             p.part_scores[o] = filled ? L[pq].s : -INFINITY;
             p.part_ids[o] = filled ? (p.id_base + (int64_t)L[pq].i) : (int64_t)-1;
@@ -598,6 +790,43 @@ static hipError_t launch_ch(int ch, const ScanArgs& a, int grid, hipStream_t str
         case 6: return launch_variant<6, NT, MODE, EXT>(a, grid, stream);
         case 7: return launch_variant<7, NT, MODE, EXT>(a, grid, stream);
         case 8: return launch_variant<8, NT, MODE, EXT>(a, grid, stream);
+        default: return hipErrorInvalidValue;
+    }
+}
+
+template <int CH>
+static hipError_t launch_pair_variant(const ScanArgs& a, int grid, hipStream_t stream) {
+    constexpr size_t lds_bytes = (size_t)2 * kWaves * 64 * kPitch * sizeof(float);  // 144 KiB
+    static bool attr_set = false;
+    if (!attr_set) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&scan_topk_f32_pair_kernel<CH>),
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+        if (e != hipSuccess) return e;
+        attr_set = true;
+    }
+    hipLaunchKernelGGL((scan_topk_f32_pair_kernel<CH>), dim3(grid), dim3(kThreads), lds_bytes, stream, a);
+    return hipGetLastError();
+}
+
+bool scan_pair_supported_stride(int64_t row_stride) {
+    return row_stride % 128 == 0 && row_stride >= 128 && row_stride <= 1024;  // every CH compiles without scratch
+}
+
+hipError_t launch_scan_topk_f32_pair(const ScanArgs& a, int grid, hipStream_t stream) {
+    if (!scan_pair_supported_stride(a.row_stride)) return hipErrorInvalidValue;
+    if (a.nq != 64 || a.q_group_stride <= 0 || a.part_group_stride <= 0 || grid < 1) return hipErrorInvalidValue;
+    if (a.q_filter_mask || a.q_after_score || a.q_after_id || a.work_tile || a.work_base || a.sample_pass || a.live_nq ||
+        a.wgs_per_group)
+        return hipErrorInvalidValue;
+    switch ((int)(a.row_stride / 128)) {
+        case 1: return launch_pair_variant<1>(a, grid, stream);
+        case 2: return launch_pair_variant<2>(a, grid, stream);
+        case 3: return launch_pair_variant<3>(a, grid, stream);
+        case 4: return launch_pair_variant<4>(a, grid, stream);
+        case 5: return launch_pair_variant<5>(a, grid, stream);
+        case 6: return launch_pair_variant<6>(a, grid, stream);
+        case 7: return launch_pair_variant<7>(a, grid, stream);
+        case 8: return launch_pair_variant<8>(a, grid, stream);
         default: return hipErrorInvalidValue;
     }
 }
