@@ -118,7 +118,7 @@ static double score_f64(const float* x, const float* q, int dim) {
  * slices of 16*CH columns; inside a slice chunk j (16 columns), component i (0..3) and
  * lane group g (0..3) address column 16j + 4g + i, and one v_mfma_f32_16x16x4_f32 is the
  * fmaf chain over g = 0..3; the 8 slice partials are added in slice order. */
-/* The row stride the engine gives an index of `dim` columns (api.hip pad_stride): whole 128-column units up to 1 024
+/* The row stride the engine gives an index of `dim` columns (api_internal.h pad_stride): whole 128-column units up to 1 024
  * columns, whole 256-column units above (the wide-row kernel walks a wave's slice in panels of whole chunks). */
 static int oracle_row_stride(int dim) { return dim <= 1024 ? (dim + 127) / 128 * 128 : (dim + 255) / 256 * 256; }
 

@@ -1,0 +1,453 @@
+// api_internal.h — what the host-side translation units of the C ABI (include/rass_engine.h) share: the engine / index /
+// IVF objects, the error plumbing, the limits, and the building blocks every launch path is made of.  Host C++ only; the
+// kernels live behind kernels.h.  Not part of the public ABI.
+//
+//   api.hip          errors; the engine and the flat index: create / grow / add / delete / persist / destroy; timers, the
+//                    stateless wrappers, k-means, peer buffers
+//   api_scan.hip     the tuning switches, the shared launch helpers declared below, and the four flat launch paths
+//   api_search.hip   flat search entry points: one group, the fused batches, the host API with its pinned slots, search_multi
+//   api_ivf.hip      IVF build, persistence, probe, delta and batch
+//
+// Ownership model: the engine singleton of a process owns the corpus slabs
+// for process lifetime; callers own every host buffer they pass in or get filled.
+// Threading: add/delete/grow take the index mutex; searches take the engine mutex only
+// while ENQUEUING (all GPU work of an engine is ordered on one stream, so the shared device
+// scratch and staging are safe by stream order) and wait for their results on a per-call
+// event outside of it, on a pinned host slot taken from a small pool: searches on different
+// indices (users) overlap their host round trips instead of serialising on a stream sync.
+// rows / deleted / has_tags are atomics: searches read them without the index mutex.
+#pragma once
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+#include <unistd.h>
+
+#include <algorithm>
+#include <atomic>
+#include <condition_variable>
+#include <map>
+#include <mutex>
+#include <new>
+#include <string>
+#include <vector>
+
+#include "../../include/rass_engine.h"
+#include "kernels.h"
+
+namespace rass {
+namespace host {
+
+// Stores the calling thread's error text (rass_last_error) and returns `code`.  ONE thread_local object, in api.hip.
+int fail(int code, const std::string& msg);
+
+// RASS_OK, or fail() with the failed call, the HIP error's text and the place: HIP_RC(expr) as a value, HIP_TRY(expr)
+// returning it from the enclosing function.
+int hip_fail(hipError_t e, const char* expr, const char* file, int line);
+inline int hip_rc(hipError_t e, const char* expr, const char* file, int line) {
+    return e == hipSuccess ? (int)RASS_OK : hip_fail(e, expr, file, line);
+}
+#define HIP_RC(expr) ::rass::host::hip_rc((expr), #expr, __FILE__, __LINE__)
+#define HIP_TRY(expr) do { const int _rc = HIP_RC(expr); if (_rc != RASS_OK) return _rc; } while (0)
+
+constexpr int kPrefilterMaxK = 16;     // prefilter keeps 32 bf16 candidates: only k <= 16 uses it, wider k scans fp32
+constexpr int kMaxGrid = 1024;        // upper bound on scan workgroups (sizing of scratch)
+constexpr int kMaxStride = 2048;      // dim_padded limit of the fused scan (128 * {1..8}; wide rows: 256 * {5..8})
+constexpr int kNarrowStride = 1024;   // above it a row is "wide": flat fp32 scans of <= 16 queries per launch only
+constexpr int64_t kStageRows = 8192;  // host -> device staging granule for add()
+constexpr int kHostSlots = 8;
+constexpr int kMultiMaxItems = 65536;  // 32-row tiles per cross-index batch (2 M rows over all its indices)
+
+inline int64_t pad128(int64_t d) { return (d + 127) / 128 * 128; }
+// The row stride of an index of `dim` columns: whole 128-column units (8 waves x one 16-column chunk); above 1 024
+// columns whole 256-column units (the wide-row scan walks a wave's slice in an even number of chunks per panel).
+inline int64_t pad_stride(int64_t d) { return d <= kNarrowStride ? pad128(d) : (d + 255) / 256 * 256; }
+constexpr const char* kStrideMsg = "row_stride must be 128*{1..8} elements (dim <= 1024) or 256*{5..8} (dim <= 2048)";
+inline int pad_nq(int nq) { return nq <= 16 ? 16 : 32; }   // query rows a launch group's kernels read: whole 16-wide MFMA N tiles
+
+int device_cus(int device);   // compute units of a device, asked once per device (one cache, api.hip)
+
+// The shared range checks of a launch group: RASS_OK, or RASS_ERR_INVALID with the message every entry point gives.
+int check_nq(int nq);   // [1, RASS_MAX_QBATCH]
+int check_k(int k);     // [1, RASS_MAX_K]
+
+// An IVF probe's work list (ScanArgs::work_*); max_tiles sizes the grid, the item count is only known on the device.
+struct IvfPlan {
+    const int32_t* work_tile;
+    const int32_t* work_rows;
+    const uint32_t* work_mask;
+    const int32_t* n_work;
+    int64_t max_tiles;
+};
+template <class Args>
+void set_plan(Args& a, const IvfPlan& p) {
+    a.work_tile = p.work_tile;
+    a.work_rows = p.work_rows;
+    a.work_mask = p.work_mask;
+    a.n_work = p.n_work;
+}
+
+// Extended per-query filters of a scan (kernels.h ScanArgs): all-null = the plain kernel variant.
+struct ScanExt {
+    const int32_t* d_q_mask = nullptr;
+    const float* d_after_s = nullptr;
+    const int64_t* d_after_i = nullptr;
+    const int32_t* d_live = nullptr;   // device scalar: 0 = every workgroup exits (the certified mode's fallback)
+};
+
+// ---- workspace views: typed pointers into a block at `base`; base = nullptr to learn `total` only.  Every area starts on
+// a 256-byte boundary.
+struct Carver {
+    unsigned char* base;
+    size_t off = 0;
+    template <class T>
+    T* take(size_t bytes) {
+        T* p = reinterpret_cast<T*>(reinterpret_cast<uintptr_t>(base) + off);
+        off = (off + bytes + 255) / 256 * 256;
+        return p;
+    }
+};
+
+// The engine scratch of one launch group (and the caller's workspace of rass_scan_topk_f32: rass_scan_workspace_bytes).
+struct ScratchView {
+    float* q_padded;               // [32][kMaxStride] normalised, zero-padded queries
+    float* part_scores;            // [kMaxGrid][nq][k] per-workgroup lists
+    int64_t* part_ids;
+    unsigned short* q_bf16;        // prefilter mode: bf16 queries (int8 queries live here too: half the bytes)
+    float* cand_scores;            // ... and the 32 candidates per query handed to the exact re-rank
+    int64_t* cand_ids;
+    float* sample_best;            // the sample pass's per-workgroup best scores [32][kMaxSampleGroups]
+    size_t total;
+};
+ScratchView scratch_layout(unsigned char* base, int nq, int k);
+
+// The block of a fused batch (eng->d_batch): every group's queries, lists and sample bests; with `candidates` (the prefilter
+// batch) also the converted queries and the merged candidates.
+struct BatchView {
+    float* q_padded;               // [groups][32][stride]
+    float* part_scores;            // [groups] x part_per_group
+    int64_t* part_ids;
+    float* sample_best;            // [groups][32][kMaxSampleGroups]
+    unsigned char* q_small;        // [groups][32] bf16 / int8 queries
+    float* cand_scores;            // [groups][32][32]
+    int64_t* cand_rows;
+    size_t total;
+    size_t part_per_group;         // elements of one group's [grid][32][k] lists
+    float* group_sample(int g) const { return sample_best + (int64_t)g * 32 * rass::kMaxSampleGroups; }
+};
+BatchView batch_layout(unsigned char* base, int groups, int grid, int k, int64_t stride, bool candidates = false);
+
+// The workspace of the certified int8 search (eng->d_cert): one pass of kCertQ queries.
+struct CertView {
+    float* q_padded;               // x 4: one copy per re-ranked chunk of 32 candidates
+    signed char* q8;
+    rass::CertQInfo* qinfo;
+    float* sample;
+    float* list_s;
+    int32_t* list_r;
+    int32_t* list_n;
+    float* list_floor;
+    int64_t* cand_rows;
+    float* rr_s;
+    int64_t* rr_i;
+    float* tau;
+    int32_t *fail_idx, *fail_flag, *fail_n;
+    float* fb_q;
+    int32_t *fb_filter, *fb_mask;
+    float* fb_s;
+    int64_t* fb_i;
+    float* hook_s;                 // the parity hook's own search result
+    int64_t* hook_i;
+    size_t total;
+};
+CertView cert_layout(unsigned char* base, int grid, int64_t stride, int64_t stride_i8, int dim);
+
+// A grow-on-demand device block (eng->d_batch, eng->d_cert, rass_ivf::d_batch): at least `need` bytes afterwards.  Growth
+// waits for the stream first: an earlier call on it may still read the old block.
+int grow_block(unsigned char** block, size_t* bytes, size_t need, hipStream_t st);
+
+// One host search call in flight: pinned staging for a batch of <= 32 queries and its results, and
+// the event recorded behind the batch's last copy.
+struct HostSlot {
+    float* h_q = nullptr;          // [32][dim]
+    int32_t* h_filter = nullptr;   // [32]
+    int32_t* h_mask = nullptr;     // [32]
+    float* h_after_s = nullptr;    // [32]
+    int64_t* h_after_i = nullptr;  // [32]
+    float* h_out_s = nullptr;      // [32][32]
+    int64_t* h_out_i = nullptr;    // [32][32]
+    int64_t* h_scanned = nullptr;  // [1]
+    void* base = nullptr;          // the one hipHostMalloc behind all of the above
+    void* h_items = nullptr;       // pinned work list of a cross-index batch (lazily allocated, kMultiMaxItems)
+    hipEvent_t done = nullptr;
+    bool busy = false;
+};
+
+}  // namespace host
+}  // namespace rass
+
+struct rass_engine {
+    int device = 0;
+    int dim = 0;
+    int n_cus = 256;
+    hipStream_t own_stream = nullptr;
+    hipStream_t stream = nullptr;
+    std::mutex mu;
+    std::map<std::string, rass_index*> indices;
+    // scratch for searches (sized for nq = RASS_MAX_QBATCH, k = RASS_MAX_K)
+    unsigned char* d_scratch = nullptr;
+    size_t scratch_bytes = 0;
+    // scratch of rass_index_search_device_batch (every launch group's queries, lists and sample bests), grown on demand
+    unsigned char* d_batch = nullptr;
+    size_t batch_bytes = 0;
+    // workspace of the certified int8 search (prefilter mode 3): one pass of kCertQ queries, grown on demand
+    unsigned char* d_cert = nullptr;
+    size_t cert_bytes = 0;
+    // host-API staging
+    float* d_qraw = nullptr;        // [32][dim]
+    int32_t* d_qfilter = nullptr;   // [32]
+    float* d_out_scores = nullptr;  // [32][32]
+    int64_t* d_out_ids = nullptr;   // [32][32]
+    float* d_stage = nullptr;       // [kStageRows][dim]
+    int32_t* d_stage_tags = nullptr;
+    // cross-index batches (rass_index_search_multi): device work list, lazily allocated
+    int32_t *d_mw_tile = nullptr, *d_mw_rows = nullptr, *d_mw_n = nullptr;
+    uint32_t* d_mw_mask = nullptr;
+    const float** d_mw_base = nullptr;
+    const int32_t** d_mw_tags = nullptr;
+    float* d_stage_t16 = nullptr;   // bf16 indices: (kStageRows + 32) x kMaxStride fp32 tile16 staging, lazily allocated
+    int32_t* d_qmask = nullptr;     // [32] masked-filter masks
+    float* d_after_s = nullptr;     // [32] continuation bound of a multi-pass top-k (k > 32)
+    int64_t* d_after_i = nullptr;   // [32]
+    // pinned host slots of the host search API (one per call in flight)
+    std::vector<rass::host::HostSlot> slots;
+    std::mutex slot_mu;
+    std::condition_variable slot_cv;
+    // optional HIP-event bracket around every scan kernel launch (bench.py's roofline leg)
+    std::vector<hipEvent_t> ev_pool;  // pairs: [2i] before, [2i+1] after
+    int ev_used = 0;                  // pairs recorded since timing_begin
+    int ev_extra = 0;                 // launch groups beyond one that recorded launches served (a 64-query pair pass: +1)
+    bool ev_on = false;
+};
+
+struct rass_index {
+    rass_engine* eng = nullptr;
+    std::string name;
+    rass_dtype dtype = RASS_F32;
+    int dim = 0;
+    int64_t stride = 0;
+    std::atomic<int64_t> rows{0};      // published after the rows' pack kernels are enqueued
+    int64_t capacity = 0;
+    std::atomic<int64_t> deleted{0};
+    std::atomic<bool> has_tags{false};  // any non-zero tag ever stored
+    float* d_rows = nullptr;
+    int32_t* d_tags = nullptr;
+    int64_t* d_gid = nullptr;               // [capacity] id reported for a row: its ordinal, or the caller's
+                                            // GLOBAL id (rass_index_add_ex: a shard of a multi-GPU index)
+    std::atomic<bool> has_gid{false};       // any row carries a caller-assigned id
+    unsigned short* d_rows_bf16 = nullptr;  // tile16b copy for the prefilter mode (nullptr = off)
+    int prefilter = 0;                      // 0 off | 1 bf16 candidate copy | 2 int8 candidate copy (+ a scale per row)
+    signed char* d_rows_i8 = nullptr;       // tile16i copy (prefilter mode 2), rows of stride_i8 bytes
+    float* d_row_scale = nullptr;           // [capacity] max|x| / 127 of every row (prefilter mode 2)
+    int64_t stride_i8 = 0;                  // stride rounded up to 512
+    // prefilter mode 3 (certified int8 search): [R, V, Y] as float bits (monotone maxima over every row ever quantised) and
+    // the counters [queries, certified, fallbacks]; allocated when the mode is first set
+    unsigned* d_cert_stats = nullptr;
+    unsigned long long* d_cert_counts = nullptr;
+    std::vector<uint8_t> host_deleted;  // tombstone bitmap mirror (host)
+    std::mutex mu;
+};
+
+// ------------------------------------------------------------------------------------ IVF (K9)
+struct rass_ivf {
+    rass_engine* eng = nullptr;
+    int dim = 0, nlist = 0;
+    int64_t stride = 0, rows = 0, slab_rows = 0, total_tiles = 0;
+    int dtype = RASS_F32;           // RASS_F32: d_slab (tile16, 32-row tiles) | RASS_BF16: d_slab_b16 (tile16b, 64-row tiles)
+    int tile_rows = 32;             // rows per plan tile = the fine scan kernel's tile
+    float* d_slab = nullptr;        // tile16, lists contiguous, each starting on a 32-row tile
+    unsigned short* d_slab_b16 = nullptr;  // bf16 slab: the rows rounded to bf16, lists starting on 64-row tiles
+    // RASS_I8: d_slab (fp32, lists on 64-row tiles: read by the exact re-rank only) + its int8 copy (tile16i) and row scales:
+    // the fine scan keeps 32 int8 candidates per query, the re-rank rescores them exactly and returns the best k <= 16
+    signed char* d_slab_i8 = nullptr;
+    float* d_slab_scale = nullptr;
+    int64_t stride_i8 = 0;
+    float* d_cand_scores = nullptr;        // [32][32] candidates of one launch group (RASS_I8)
+    int64_t* d_cand_rows = nullptr;
+    int32_t* d_tags = nullptr;      // [slab_rows] permuted row tags (0 on padding)
+    int64_t* d_ids = nullptr;       // [slab_rows] source row id, -1 on padding
+    float* d_centroids = nullptr;   // tile16 slab of nlist normalised centroids
+    int32_t *d_list_tile0 = nullptr, *d_list_len = nullptr;
+    int32_t *d_work_tile = nullptr, *d_work_rows = nullptr, *d_n_work = nullptr;
+    uint32_t* d_work_mask = nullptr;
+    int64_t* d_scanned = nullptr;   // rows touched by the last fine scan
+    float* d_probe_scores = nullptr;  // [32][32]
+    int64_t* d_probe_ids = nullptr;   // [32][32]
+    uint32_t* d_tau = nullptr;        // [32] nprobe > 32: per-query threshold keys
+    uint32_t* d_list_mask = nullptr;  // [nlist] nprobe > 32: probe masks from the score matrix
+    bool any_tags = false;
+    // IVF + flat delta (rass_ivf_search_delta*): the IVF covers source rows [0, src_rows); rows the source index took
+    // afterwards are scanned exactly from its own slab and merged with the probe's list
+    int64_t src_rows = 0;
+    std::vector<int32_t> pos_of;      // host: slab position of source row r (< src_rows), -1 = not in the slab (tombstoned)
+    float* d_pair_scores = nullptr;   // [2][32][32] the probe's list and the delta scan's list of one launch group
+    int64_t* d_pair_ids = nullptr;
+    unsigned char* d_batch = nullptr; // rass_ivf_search_device_batch: queries, coarse / fine lists and work lists of <= 32 groups
+    size_t batch_bytes = 0;
+};
+
+namespace rass {
+namespace host {
+
+int set_device(const rass_engine* eng);
+int index_reserve(rass_index* idx, int64_t need_rows);   // api.hip; the caller holds idx->mu and eng->mu
+void index_free_slabs(rass_index* idx);                  // every device array of the index, freed and nulled
+
+// ---- the tuning switches (api_scan.hip: the only place of the host layer that reads the environment)
+int scan_xcd_skew(int nq, int grid, int n_cus);   // ScanArgs::xcd_skew of a launch; RASS_SCAN_XCD_SKEW, read once
+int64_t scan_sample_floor_min_share();            // RASS_SCAN_SAMPLE_FLOOR, read per call
+bool i8_sample_floor(int64_t rows, int grid);     // RASS_I8_SAMPLE_FLOOR, read per call
+bool scan_batch_one_sample();                     // RASS_SCAN_BATCH_SAMPLE, read per call
+bool scan_batch_pair();                           // RASS_SCAN_BATCH_PAIR, read once
+bool ivf_batch_one_launch();                      // RASS_IVF_BATCH_FINE, read per call
+
+// Workgroups of a scan over `tiles` tiles whose merge takes `lists_kept_per_wg` entries per query from each of them: one per
+// CU, at most kMaxGrid, and no more lists than one merge launch takes (kMergeMaxCandidates).  (The certified scan sizes its
+// own grid: its selection kernel takes kMaxGridSel slices.)
+int scan_grid(int64_t tiles, int lists_kept_per_wg, int n_cus);
+
+// The optional event bracket of rass_engine_kernel_timing_*: records the before / after events around `launch` (which
+// returns a status: HIP_RC of the launcher's) and counts it; extra_groups = launch groups beyond one that it served (a pair pass: 1).
+// eng = nullptr: no bracket.
+template <class F>
+int timed_launch(rass_engine* eng, hipStream_t st, F&& launch, int extra_groups = 0) {
+    const bool timed = eng && eng->ev_on && (size_t)(2 * eng->ev_used + 1) < eng->ev_pool.size();
+    if (timed) HIP_TRY(hipEventRecord(eng->ev_pool[2 * eng->ev_used], st));
+    const int rc = launch();
+    if (rc != RASS_OK) return rc;
+    if (timed) {
+        HIP_TRY(hipEventRecord(eng->ev_pool[2 * eng->ev_used + 1], st));
+        eng->ev_used += 1;
+        eng->ev_extra += extra_groups;   // kernel_timing_end counts launch GROUPS
+    }
+    return RASS_OK;
+}
+
+// The sample pre-launch of a scan (ScanArgs / ScanBf16Args / ScanI8Args ::sample_best): the launch `a` describes, over the
+// slab's first 64 * grid rows only, keeping each workgroup's best score per query in `best`; `a` then takes the k-th
+// largest of those as its floor.  The int8 and bf16 kernels sample with k = 1, the fp32 kernel as its own variant.
+// launch_grid (a grouped sample: `a` carries wgs_per_group and the group strides): workgroups of the sample launch.
+inline void as_sample(rass::ScanArgs& s) { s.xcd_skew = 0, s.sample_pass = true; }
+inline void as_sample(rass::ScanBf16Args& s) { s.k = 1; }
+inline void as_sample(rass::ScanI8Args& s) { s.k = 1; }
+template <class Args>
+int sample_prelaunch(Args& a, int grid, float* best, hipError_t (*launch)(const Args&, int, hipStream_t), hipStream_t st,
+                     int launch_grid = 0) {
+    Args s = a;   // same queries, filters, continuation bound and id space: only the row count differs
+    s.n_rows = 64 * grid;
+    as_sample(s);
+    s.part_scores = best;
+    s.part_ids = nullptr;
+    HIP_TRY(launch(s, launch_grid ? launch_grid : grid, st));
+    a.sample_best = best;
+    a.sample_groups = grid;
+    return RASS_OK;
+}
+
+// What one search call reads of a flat index, taken once (the atomics without the index mutex, in this order).
+// (The bf16, prefilter and certified launch paths read the row count again themselves, as before: it only grows.)
+struct IndexView {
+    int64_t rows;
+    const int32_t* row_tag;   // the tags where some row is deleted or the call filters, else nullptr
+    const int64_t* id_map;    // the caller-assigned ids where any row has one, else nullptr
+    int64_t id_base;          // 0 under an id map or a continuation bound (which names ROWS): ids are translated in the merge
+    const float* corpus;      // the fp32 slab; an empty index scans zero rows of the engine scratch
+};
+IndexView index_view(const rass_index* idx, bool filtered, int64_t id_base = 0, bool continued = false);
+
+// The fields a bf16 / int8 candidate scan takes from its corpus — a flat index, or an IVF slab.  The caller adds what
+// differs per launch: queries, filters, lists, nq (and the work list of a probe).
+rass::ScanBf16Args bf16_args(const rass_index* idx, int64_t rows, const int32_t* row_tag, int k);
+rass::ScanBf16Args bf16_args(const rass_ivf* v, const int32_t* row_tag, int k);
+rass::ScanI8Args i8_args(const rass_index* idx, int64_t rows, const int32_t* row_tag, int k);
+rass::ScanI8Args i8_args(const rass_ivf* v, const int32_t* row_tag, int k);
+
+// The grouped merge of a fused batch: dense per-workgroup lists of `part_per_group` elements per group.
+rass::MergeGroups dense_groups(int nq_total, int64_t part_per_group, int64_t out_score_stride, int64_t out_id_stride);
+
+// ---- the flat launch paths (api_scan.hip).  The caller holds eng->mu and has set the device.
+// The exact fp32 scan of one launch group: normalise -> (sample) -> scan -> merge.  Stateless: any slab, any workspace.
+struct ScanRequest {
+    const float* corpus = nullptr;     // tile16 slab, 16-byte aligned
+    int64_t n_rows = 0;
+    int64_t stride = 0;
+    const int32_t* row_tag = nullptr;
+    const float* queries = nullptr;    // [nq] rows of q_dim columns, q_stride apart
+    int q_dim = 0;
+    int64_t q_stride = 0;
+    int nq = 0;
+    const int32_t* q_filter = nullptr;
+    int k = 0;
+    int64_t id_base = 0;
+    float* out_scores = nullptr;
+    int64_t* out_ids = nullptr;
+    unsigned char* ws = nullptr;       // scratch_layout(nq, k)
+    size_t ws_bytes = 0;
+    int n_cus = 0;
+    hipStream_t st = nullptr;
+    rass_engine* timing = nullptr;     // the engine whose kernel timing counts this scan, if any
+    const IvfPlan* plan = nullptr;     // the fine scan of a probe
+    const int64_t* id_map = nullptr;   // id reported for row r, instead of id_base + r
+    ScanExt ext;
+    bool queries_prepared = false;     // see scan_launch
+};
+ScanRequest scan_request(rass_engine* eng);   // on the engine's scratch and stream (timing stays off)
+int scan_launch(const ScanRequest& r);
+
+// One launch group on a flat index, for the three paths that need the index: the bf16 corpus, the prefilter modes 1 / 2
+// and the certified mode 3.
+struct FlatRequest {
+    const float* queries = nullptr;    // [nq][dim]
+    int nq = 0;
+    int k = 0;
+    const int32_t* q_filter = nullptr;
+    const int32_t* q_filter_mask = nullptr;   // masked tag compare ((tag & mask) == filter)
+    const float* after_score = nullptr;       // continuation bound of a k > 32 pass (bf16 corpus and fp32 scan only)
+    const int64_t* after_row = nullptr;
+    float* out_scores = nullptr;
+    int64_t* out_ids = nullptr;
+    const int32_t* row_tag = nullptr;         // from the call's IndexView
+    const int64_t* id_map = nullptr;          // ascending with the row: the tie order is unchanged
+    int64_t id_base = 0;
+    // optional extra outputs (the candidates hooks): the merged candidate lists [nq][32] (modes 1 / 2) or [nq][128] with
+    // tau [nq] and the certificate flags [nq] (mode 3)
+    float* cand_scores = nullptr;
+    int64_t* cand_rows = nullptr;
+    float* tau = nullptr;
+    int32_t* certified = nullptr;
+    void use(const IndexView& iv) { row_tag = iv.row_tag, id_map = iv.id_map, id_base = iv.id_base; }
+};
+int bf16_scan_launch(rass_index* idx, const FlatRequest& r);
+int prefilter_launch(rass_index* idx, const FlatRequest& r);
+int cert_launch(rass_index* idx, const FlatRequest& r);
+
+// A pinned host slot for one search call in flight (blocks while all kHostSlots are taken); api_search.hip.
+HostSlot* slot_acquire(rass_engine* eng);
+void slot_release(rass_engine* eng, HostSlot* sl);
+struct SlotGuard {
+    rass_engine* eng;
+    HostSlot* sl;
+    SlotGuard(rass_engine* e) : eng(e), sl(slot_acquire(e)) {}
+    ~SlotGuard() { slot_release(eng, sl); }
+};
+// The host API's round trip of one launch group through the slot `sl`: the caller's queries (and filters / masks, where
+// given) to the slot and on to the engine's device staging; the group's k results per query back to the slot, with the
+// slot's event recorded behind them.  The caller holds eng->mu for both enqueues.
+void slot_fill(HostSlot* sl, int dim, const float* queries, const int32_t* q_filter, const int32_t* q_filter_mask, int b);
+int slot_upload(rass_engine* eng, HostSlot* sl, int dim, bool filter, bool mask, int b);
+int slot_download(rass_engine* eng, HostSlot* sl, int b, int k, const int64_t* d_scanned = nullptr);
+
+}  // namespace host
+}  // namespace rass

@@ -1,0 +1,811 @@
+// api_ivf.hip — the C ABI of include/rass_engine.h: the IVF index over a flat fp32 source.  Build (fp32, bf16 and
+// int8 slabs), persistence, tombstones, the probe of one launch group (coarse scan or threshold path, plan, fine scan),
+// the probe + flat delta, the batch of many groups, and the host search API.  Host-side C++ only; the launch helpers
+// come from api_scan.hip, the objects and the threading rules from api_internal.h.
+
+#include "api_internal.h"
+
+using namespace rass::host;
+
+extern "C" {
+
+static void ivf_free(rass_ivf* v) {
+    if (!v) return;
+    for (void* p : {(void*)v->d_slab, (void*)v->d_slab_b16, (void*)v->d_slab_i8, (void*)v->d_slab_scale, (void*)v->d_cand_scores, (void*)v->d_cand_rows, (void*)v->d_tags, (void*)v->d_ids, (void*)v->d_centroids, (void*)v->d_list_tile0,
+                    (void*)v->d_list_len, (void*)v->d_work_tile, (void*)v->d_work_rows, (void*)v->d_n_work,
+                    (void*)v->d_work_mask, (void*)v->d_scanned, (void*)v->d_probe_scores, (void*)v->d_probe_ids,
+                    (void*)v->d_tau, (void*)v->d_list_mask, (void*)v->d_pair_scores, (void*)v->d_pair_ids, (void*)v->d_batch})
+        if (p) (void)hipFree(p);
+    delete v;
+}
+
+// Every device array of an IVF whose shape fields (dtype, strides, slab_rows, nlist, total_tiles) are set.  On a failure the
+// caller frees what was allocated (ivf_free); *failed names the array that could not be had.
+static hipError_t ivf_alloc(rass_ivf* v, const char** failed) {
+    const size_t slab = (size_t)v->slab_rows, nl = (size_t)v->nlist, tiles = (size_t)v->total_tiles;
+    const size_t cent_rows = (nl + 15) / 16 * 16, QK = RASS_MAX_QBATCH * RASS_MAX_K;
+    const bool b16 = v->dtype == RASS_BF16, i8 = v->dtype == RASS_I8;
+    const struct { const char* name; void** p; size_t bytes; } want[] = {
+        {"d_slab_b16", (void**)&v->d_slab_b16, b16 ? slab * v->stride * 2 : 0}, {"d_slab", (void**)&v->d_slab, b16 ? 0 : slab * v->stride * 4},
+        {"d_slab_i8", (void**)&v->d_slab_i8, i8 ? slab * v->stride_i8 : 0}, {"d_slab_scale", (void**)&v->d_slab_scale, i8 ? slab * 4 : 0},
+        {"d_cand_scores", (void**)&v->d_cand_scores, i8 ? QK * 4 : 0}, {"d_cand_rows", (void**)&v->d_cand_rows, i8 ? QK * 8 : 0},
+        {"d_tags", (void**)&v->d_tags, slab * 4}, {"d_ids", (void**)&v->d_ids, slab * 8}, {"d_centroids", (void**)&v->d_centroids, cent_rows * v->stride * 4},
+        {"d_list_tile0", (void**)&v->d_list_tile0, nl * 4}, {"d_list_len", (void**)&v->d_list_len, nl * 4}, {"d_work_tile", (void**)&v->d_work_tile, tiles * 4},
+        {"d_work_rows", (void**)&v->d_work_rows, tiles * 4}, {"d_work_mask", (void**)&v->d_work_mask, tiles * 4}, {"d_n_work", (void**)&v->d_n_work, 4},
+        {"d_scanned", (void**)&v->d_scanned, 8}, {"d_probe_scores", (void**)&v->d_probe_scores, QK * 4}, {"d_probe_ids", (void**)&v->d_probe_ids, QK * 8},
+        {"d_tau", (void**)&v->d_tau, RASS_MAX_QBATCH * 4}, {"d_list_mask", (void**)&v->d_list_mask, nl * 4}, {"d_pair_scores", (void**)&v->d_pair_scores, 2 * QK * 4},
+        {"d_pair_ids", (void**)&v->d_pair_ids, 2 * QK * 8}};
+    for (const auto& w : want)
+        if (w.bytes) {
+            const hipError_t e = hipMalloc(w.p, w.bytes);
+            if (e != hipSuccess) return *failed = w.name, e;
+        }
+    return hipSuccess;
+}
+
+int rass_ivf_build(rass_index_t* src, const float* centroids, int nlist, const int32_t* assign, rass_ivf_t** out) {
+    return rass_ivf_build_ex(src, centroids, nlist, assign, RASS_F32, out);
+}
+
+int rass_ivf_build_ex(rass_index_t* src, const float* centroids, int nlist, const int32_t* assign, rass_dtype slab_dtype,
+                      rass_ivf_t** out) {
+    return rass_ivf_build_prefix(src, centroids, nlist, assign, slab_dtype, -1, out);
+}
+
+int rass_ivf_build_prefix(rass_index_t* src, const float* centroids, int nlist, const int32_t* assign,
+                          rass_dtype slab_dtype, int64_t n_rows, rass_ivf_t** out) {
+    if (!src || !centroids || !assign || !out) return fail(RASS_ERR_INVALID, "NULL argument");
+    *out = nullptr;
+    if (nlist < 1 || nlist > 32768) return fail(RASS_ERR_INVALID, "nlist must be in [1, 32768]");
+    if (src->dtype != RASS_F32) return fail(RASS_ERR_UNSUPPORTED, "the IVF build needs an fp32 source index");
+    if (src->stride > kNarrowStride) return fail(RASS_ERR_UNSUPPORTED, "IVF needs dim <= 1024 (wide rows: flat scan only)");
+    if (slab_dtype != RASS_F32 && slab_dtype != RASS_BF16 && slab_dtype != RASS_I8) return fail(RASS_ERR_INVALID, "unknown slab dtype");
+    if (slab_dtype == RASS_BF16 && src->stride % 256 != 0)
+        return fail(RASS_ERR_UNSUPPORTED, "a bf16 slab needs dim padded to a multiple of 256 (the bf16 scan's K split)");
+    const int tile_rows = slab_dtype == RASS_F32 ? 32 : 64;
+    rass_engine* eng = src->eng;
+    std::lock_guard<std::mutex> lk(src->mu);
+    int rc = set_device(eng);
+    if (rc != RASS_OK) return rc;
+    if (n_rows > src->rows) return fail(RASS_ERR_INVALID, "n_rows exceeds the rows of the source index");
+    const int64_t n = n_rows < 0 ? src->rows.load() : n_rows;
+    // list lengths over live rows, tile-aligned offsets
+    std::vector<int32_t> len((size_t)nlist, 0), tile0((size_t)nlist, 0);
+    for (int64_t r = 0; r < n; ++r) {
+        if (src->host_deleted[(size_t)(r >> 3)] & (1u << (r & 7))) continue;
+        const int32_t l = assign[r];
+        if (l < 0 || l >= nlist) return fail(RASS_ERR_INVALID, "assign[] holds a list id outside [0, nlist)");
+        len[(size_t)l] += 1;
+    }
+    int64_t tiles = 0;
+    for (int l = 0; l < nlist; ++l) {
+        tile0[(size_t)l] = (int32_t)tiles;
+        tiles += (len[(size_t)l] + tile_rows - 1) / tile_rows;
+    }
+    if (tiles * tile_rows > 0x7fffffc0LL) return fail(RASS_ERR_UNSUPPORTED, "slab too large for one IVF shard");
+    const int64_t slab_rows = std::max<int64_t>(tiles, 1) * tile_rows;
+    std::vector<int64_t> src_of((size_t)slab_rows, -1);
+    std::vector<int32_t> fill((size_t)nlist, 0);
+    for (int64_t r = 0; r < n; ++r) {  // ascending source id inside every list
+        if (src->host_deleted[(size_t)(r >> 3)] & (1u << (r & 7))) continue;
+        const int32_t l = assign[r];
+        src_of[(size_t)((int64_t)tile0[(size_t)l] * tile_rows + fill[(size_t)l]++)] = r;
+    }
+    rass_ivf* v = new (std::nothrow) rass_ivf();
+    if (!v) return fail(RASS_ERR_OOM, "host allocation failed");
+    v->eng = eng;
+    v->dtype = slab_dtype;
+    v->tile_rows = tile_rows;
+    v->dim = src->dim;
+    v->stride = src->stride;
+    v->nlist = nlist;
+    v->rows = 0;
+    for (int l = 0; l < nlist; ++l) v->rows += len[(size_t)l];
+    v->src_rows = n;
+    v->pos_of.assign((size_t)n, -1);
+    for (int64_t d = 0; d < slab_rows; ++d)
+        if (src_of[(size_t)d] >= 0) v->pos_of[(size_t)src_of[(size_t)d]] = (int32_t)d;
+    v->slab_rows = slab_rows;
+    v->total_tiles = std::max<int64_t>(tiles, 1);
+    v->any_tags = src->has_tags;
+    hipStream_t st = eng->stream;
+    const int64_t cent_rows = ((int64_t)nlist + 15) / 16 * 16;
+#define IVF_TRY(expr)                                                                                       \
+    do {                                                                                                    \
+        hipError_t _e = (expr);                                                                             \
+        if (_e != hipSuccess) {                                                                             \
+            ivf_free(v);                                                                                    \
+            return fail(_e == hipErrorOutOfMemory ? RASS_ERR_OOM : RASS_ERR_HIP,                            \
+                        std::string("ivf build: ") + #expr + ": " + hipGetErrorString(_e));                 \
+        }                                                                                                   \
+    } while (0)
+    if (slab_dtype == RASS_I8) v->stride_i8 = (v->stride + 511) / 512 * 512;
+    const char* what = "";
+    const hipError_t ae = ivf_alloc(v, &what);
+    if (ae != hipSuccess) {
+        ivf_free(v);
+        return fail(ae == hipErrorOutOfMemory ? RASS_ERR_OOM : RASS_ERR_HIP, std::string("ivf build: hipMalloc of ") + what + ": " + hipGetErrorString(ae));
+    }
+    if (slab_dtype == RASS_I8) IVF_TRY(hipMemsetAsync(v->d_slab_i8, 0, (size_t)slab_rows * v->stride_i8, st));
+    IVF_TRY(hipMemcpyAsync(v->d_ids, src_of.data(), (size_t)slab_rows * 8, hipMemcpyHostToDevice, st));
+    IVF_TRY(hipMemcpyAsync(v->d_list_tile0, tile0.data(), (size_t)nlist * 4, hipMemcpyHostToDevice, st));
+    IVF_TRY(hipMemcpyAsync(v->d_list_len, len.data(), (size_t)nlist * 4, hipMemcpyHostToDevice, st));
+    if (slab_dtype == RASS_BF16)
+        IVF_TRY(rass::launch_permute_rows_tile16_bf16(src->d_rows, v->d_slab_b16, v->stride, v->d_ids, slab_rows, st));
+    else
+        IVF_TRY(rass::launch_permute_rows_tile16(src->d_rows, v->d_slab, v->stride, v->d_ids, slab_rows, st));
+    if (slab_dtype == RASS_I8)
+        IVF_TRY(rass::launch_quantize_tile16_i8(v->d_slab, v->d_slab_i8, v->d_slab_scale, v->stride, v->stride_i8, 0, slab_rows / 16, st));
+    // tags: permuted on the host (small), padding rows get 0
+    {
+        std::vector<int32_t> tags((size_t)std::max<int64_t>(n, 1), 0), ptags((size_t)slab_rows, 0);
+        if (n > 0) {
+            IVF_TRY(hipMemcpyAsync(tags.data(), src->d_tags, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+            IVF_TRY(hipStreamSynchronize(st));
+        }
+        for (int64_t d = 0; d < slab_rows; ++d)
+            if (src_of[(size_t)d] >= 0) ptags[(size_t)d] = tags[(size_t)src_of[(size_t)d]];
+        IVF_TRY(hipMemcpyAsync(v->d_tags, ptags.data(), (size_t)slab_rows * 4, hipMemcpyHostToDevice, st));
+        IVF_TRY(hipStreamSynchronize(st));
+    }
+    // centroids: normalise + pack through the engine's staging buffer
+    IVF_TRY(hipMemsetAsync(v->d_centroids, 0, (size_t)cent_rows * v->stride * 4, st));
+    {
+        std::lock_guard<std::mutex> elk(eng->mu);
+        for (int64_t done = 0; done < nlist; done += kStageRows) {
+            const int64_t m = std::min<int64_t>(kStageRows, nlist - done);
+            IVF_TRY(hipMemcpyAsync(eng->d_stage, centroids + done * v->dim, (size_t)m * v->dim * 4,
+                                   hipMemcpyHostToDevice, st));
+            IVF_TRY(rass::launch_pack_rows_tile16(eng->d_stage, v->dim, v->d_centroids, v->stride, done, m, v->dim, 1, st));
+            IVF_TRY(hipStreamSynchronize(st));
+        }
+    }
+#undef IVF_TRY
+    *out = v;
+    return RASS_OK;
+}
+
+void rass_ivf_destroy(rass_ivf_t* v) {
+    if (!v) return;
+    (void)hipSetDevice(v->eng->device);
+    (void)hipStreamSynchronize(v->eng->stream);
+    ivf_free(v);
+}
+
+// ---- IVF persistence: header + list table + slab ids + tags + centroid slab + row slab (raw tile16)
+struct IvfSaveHeader {
+    char magic[8];
+    int32_t version, dim, nlist, any_tags;
+    int64_t stride, rows, slab_rows, total_tiles, cent_rows;
+};
+
+static bool dev_to_file(FILE* f, const void* d_src, size_t bytes, hipStream_t st, std::vector<unsigned char>& buf) {
+    const unsigned char* p = static_cast<const unsigned char*>(d_src);
+    for (size_t done = 0; done < bytes;) {
+        const size_t m = std::min(buf.size(), bytes - done);
+        if (hipMemcpyAsync(buf.data(), p + done, m, hipMemcpyDeviceToHost, st) != hipSuccess) return false;
+        if (hipStreamSynchronize(st) != hipSuccess) return false;
+        if (fwrite(buf.data(), 1, m, f) != m) return false;
+        done += m;
+    }
+    return true;
+}
+
+static bool file_to_dev(FILE* f, void* d_dst, size_t bytes, hipStream_t st, std::vector<unsigned char>& buf) {
+    unsigned char* p = static_cast<unsigned char*>(d_dst);
+    for (size_t done = 0; done < bytes;) {
+        const size_t m = std::min(buf.size(), bytes - done);
+        if (fread(buf.data(), 1, m, f) != m) return false;
+        if (hipMemcpyAsync(p + done, buf.data(), m, hipMemcpyHostToDevice, st) != hipSuccess) return false;
+        if (hipStreamSynchronize(st) != hipSuccess) return false;
+        done += m;
+    }
+    return true;
+}
+
+int rass_ivf_save(rass_ivf_t* v, const char* path) {
+    if (!v || !path) return fail(RASS_ERR_INVALID, "NULL argument");
+    rass_engine* eng = v->eng;
+    int rc = set_device(eng);
+    if (rc != RASS_OK) return rc;
+    std::lock_guard<std::mutex> lk(eng->mu);
+    hipStream_t st = eng->stream;
+    FILE* f = fopen(path, "wb");
+    if (!f) return fail(RASS_ERR_IO, std::string("cannot open for write: ") + path);
+    IvfSaveHeader h;
+    memset(&h, 0, sizeof(h));
+    memcpy(h.magic, "RASSIVF1", 8);
+    // 3 / 4 (since round 4) = 1 / 2 followed by one int64: the source rows the IVF covers (rass_ivf_covered_rows).
+    // 2, 4: the row slab is bf16 (tile16b) with lists on 64-row tiles
+    // 5: the fp32 slab with lists on 64-row tiles of an int8 IVF (the int8 copy and its scales are rebuilt by the load)
+    h.version = v->dtype == RASS_BF16 ? 4 : v->dtype == RASS_I8 ? 5 : 3;
+    h.dim = v->dim;
+    h.nlist = v->nlist;
+    h.any_tags = v->any_tags ? 1 : 0;
+    h.stride = v->stride;
+    h.rows = v->rows;
+    h.slab_rows = v->slab_rows;
+    h.total_tiles = v->total_tiles;
+    h.cent_rows = ((int64_t)v->nlist + 15) / 16 * 16;
+    std::vector<unsigned char> buf((size_t)32 << 20);
+    bool ok = fwrite(&h, sizeof(h), 1, f) == 1;
+    ok = ok && fwrite(&v->src_rows, sizeof(int64_t), 1, f) == 1;
+    ok = ok && dev_to_file(f, v->d_list_tile0, (size_t)v->nlist * 4, st, buf);
+    ok = ok && dev_to_file(f, v->d_list_len, (size_t)v->nlist * 4, st, buf);
+    ok = ok && dev_to_file(f, v->d_ids, (size_t)v->slab_rows * 8, st, buf);
+    ok = ok && dev_to_file(f, v->d_tags, (size_t)v->slab_rows * 4, st, buf);
+    ok = ok && dev_to_file(f, v->d_centroids, (size_t)h.cent_rows * v->stride * 4, st, buf);
+    ok = ok && (v->dtype == RASS_BF16 ? dev_to_file(f, v->d_slab_b16, (size_t)v->slab_rows * v->stride * 2, st, buf)
+                                       : dev_to_file(f, v->d_slab, (size_t)v->slab_rows * v->stride * 4, st, buf));
+    ok = ok && fflush(f) == 0 && fsync(fileno(f)) == 0;
+    ok = (fclose(f) == 0) && ok;
+    return ok ? RASS_OK : fail(RASS_ERR_IO, std::string("ivf save failed (short write or device read): ") + path);
+}
+
+int rass_ivf_load(rass_engine_t* eng, const char* path, rass_ivf_t** out) {
+    if (!eng || !path || !out) return fail(RASS_ERR_INVALID, "NULL argument");
+    *out = nullptr;
+    int rc = set_device(eng);
+    if (rc != RASS_OK) return rc;
+    FILE* f = fopen(path, "rb");
+    if (!f) return fail(RASS_ERR_IO, std::string("cannot open for read: ") + path);
+    IvfSaveHeader h;
+    if (fread(&h, sizeof(h), 1, f) != 1 || memcmp(h.magic, "RASSIVF1", 8) != 0 || h.version < 1 || h.version > 5) {
+        fclose(f);
+        return fail(RASS_ERR_IO, "not a rass IVF file");
+    }
+    int64_t src_rows = -1;   // versions 1 / 2 do not carry it: taken from the slab's ids below
+    const int64_t extra = h.version >= 3 ? (int64_t)sizeof(int64_t) : 0;
+    if (extra && (fread(&src_rows, sizeof(int64_t), 1, f) != 1 || src_rows < 0)) {
+        fclose(f);
+        return fail(RASS_ERR_IO, "IVF file is truncated / corrupt");
+    }
+    const bool b16 = h.version == 2 || h.version == 4;
+    const bool i8 = h.version == 5;
+    const int tile_rows = (b16 || i8) ? 64 : 32;
+    const int64_t esize = b16 ? 2 : 4;
+    const int64_t cent_rows = ((int64_t)h.nlist + 15) / 16 * 16;
+    bool sane = h.dim == eng->dim && h.stride == pad128(h.dim) && h.nlist >= 1 && h.nlist <= 32768 && h.rows >= 0 &&
+                h.slab_rows >= tile_rows && h.slab_rows % tile_rows == 0 && h.slab_rows <= 0x7fffffc0LL &&
+                h.total_tiles == h.slab_rows / tile_rows && h.cent_rows == cent_rows && h.rows <= h.slab_rows &&
+                (!b16 || h.stride % 256 == 0) && h.stride <= kNarrowStride;
+    if (sane) {  // the header must agree with the file length before anything is allocated from it
+        const long body = ftell(f);
+        int64_t len = -1;
+        if (body >= 0 && fseek(f, 0, SEEK_END) == 0) len = (int64_t)ftell(f);
+        const int64_t need = (int64_t)sizeof(h) + extra + (int64_t)h.nlist * 8 + h.slab_rows * 12 + cent_rows * h.stride * 4 +
+                             h.slab_rows * h.stride * esize;
+        sane = body >= 0 && len == need && fseek(f, body, SEEK_SET) == 0;
+    }
+    if (!sane) {
+        fclose(f);
+        return fail(RASS_ERR_IO, "IVF file does not match the engine (dim) or is truncated / corrupt");
+    }
+    rass_ivf* v = new (std::nothrow) rass_ivf();
+    if (!v) {
+        fclose(f);
+        return fail(RASS_ERR_OOM, "host allocation failed");
+    }
+    v->eng = eng;
+    v->dim = h.dim;
+    v->stride = h.stride;
+    v->nlist = h.nlist;
+    v->rows = h.rows;
+    v->slab_rows = h.slab_rows;
+    v->total_tiles = h.total_tiles;
+    v->any_tags = h.any_tags != 0;
+    v->dtype = b16 ? RASS_BF16 : i8 ? RASS_I8 : RASS_F32;
+    v->tile_rows = tile_rows;
+    v->stride_i8 = (h.stride + 511) / 512 * 512;
+    std::lock_guard<std::mutex> lk(eng->mu);
+    hipStream_t st = eng->stream;
+    const char* what = "";
+    if (ivf_alloc(v, &what) != hipSuccess) {
+        fclose(f);
+        ivf_free(v);
+        return fail(RASS_ERR_OOM, std::string("ivf load: device allocation failed (") + what + ")");
+    }
+    std::vector<unsigned char> buf((size_t)32 << 20);
+    bool ok = file_to_dev(f, v->d_list_tile0, (size_t)h.nlist * 4, st, buf) && file_to_dev(f, v->d_list_len, (size_t)h.nlist * 4, st, buf) &&
+         file_to_dev(f, v->d_ids, (size_t)h.slab_rows * 8, st, buf) && file_to_dev(f, v->d_tags, (size_t)h.slab_rows * 4, st, buf) &&
+         file_to_dev(f, v->d_centroids, (size_t)cent_rows * h.stride * 4, st, buf) &&
+         (b16 ? file_to_dev(f, v->d_slab_b16, (size_t)h.slab_rows * h.stride * 2, st, buf)
+              : file_to_dev(f, v->d_slab, (size_t)h.slab_rows * h.stride * 4, st, buf));
+    fclose(f);
+    if (ok && i8)   // the int8 copy is a function of the fp32 slab: rebuilt, not stored
+        ok = hipMemsetAsync(v->d_slab_i8, 0, (size_t)h.slab_rows * v->stride_i8, st) == hipSuccess &&
+             rass::launch_quantize_tile16_i8(v->d_slab, v->d_slab_i8, v->d_slab_scale, v->stride, v->stride_i8, 0, h.slab_rows / 16, st) == hipSuccess &&
+             hipStreamSynchronize(st) == hipSuccess;
+    if (!ok) {
+        ivf_free(v);
+        return fail(RASS_ERR_IO, "ivf load: short read or upload failure");
+    }
+    // the list table must index inside the slab: a corrupt table would send the probe out of bounds
+    {
+        std::vector<int32_t> t0((size_t)h.nlist), len((size_t)h.nlist);
+        bool good = hipMemcpy(t0.data(), v->d_list_tile0, (size_t)h.nlist * 4, hipMemcpyDeviceToHost) == hipSuccess &&
+                    hipMemcpy(len.data(), v->d_list_len, (size_t)h.nlist * 4, hipMemcpyDeviceToHost) == hipSuccess;
+        int64_t tiles = 0;
+        for (int l = 0; good && l < h.nlist; ++l) {
+            good = len[(size_t)l] >= 0 && t0[(size_t)l] == tiles;
+            tiles += (len[(size_t)l] + tile_rows - 1) / tile_rows;
+        }
+        if (!good || std::max<int64_t>(tiles, 1) != h.total_tiles) {
+            ivf_free(v);
+            return fail(RASS_ERR_IO, "ivf load: inconsistent list table");
+        }
+    }
+    // source row -> slab position (rass_ivf_delete), from the slab's ids and tags (-1 tag = tombstoned after the build)
+    {
+        std::vector<int64_t> ids((size_t)h.slab_rows);
+        std::vector<int32_t> tags((size_t)h.slab_rows);
+        if (hipMemcpy(ids.data(), v->d_ids, (size_t)h.slab_rows * 8, hipMemcpyDeviceToHost) != hipSuccess ||
+            hipMemcpy(tags.data(), v->d_tags, (size_t)h.slab_rows * 4, hipMemcpyDeviceToHost) != hipSuccess) {
+            ivf_free(v);
+            return fail(RASS_ERR_HIP, "ivf load: reading back the slab ids failed");
+        }
+        int64_t max_id = -1;
+        for (int64_t d = 0; d < h.slab_rows; ++d) max_id = std::max(max_id, ids[(size_t)d]);
+        if (src_rows < 0) src_rows = max_id + 1;
+        if (max_id >= src_rows) {
+            ivf_free(v);
+            return fail(RASS_ERR_IO, "ivf load: a slab id lies outside the covered source rows");
+        }
+        v->src_rows = src_rows;
+        v->pos_of.assign((size_t)src_rows, -1);
+        for (int64_t d = 0; d < h.slab_rows; ++d)
+            if (ids[(size_t)d] >= 0 && tags[(size_t)d] != -1) v->pos_of[(size_t)ids[(size_t)d]] = (int32_t)d;
+    }
+    *out = v;
+    return RASS_OK;
+}
+
+int64_t rass_ivf_rows(const rass_ivf_t* v) { return v ? v->rows : 0; }
+int rass_ivf_nlist(const rass_ivf_t* v) { return v ? v->nlist : 0; }
+int rass_ivf_dtype(const rass_ivf_t* v) { return v ? v->dtype : -1; }
+int64_t rass_ivf_covered_rows(const rass_ivf_t* v) { return v ? v->src_rows : 0; }
+
+int rass_ivf_delete(rass_ivf_t* v, int64_t src_row) {
+    if (!v) return fail(RASS_ERR_INVALID, "NULL argument");
+    rass_engine* eng = v->eng;
+    int rc = set_device(eng);
+    if (rc != RASS_OK) return rc;
+    // the engine mutex: a search holds it for its whole enqueue sequence, so the fill cannot land between a probe's
+    // plan and its fine scan (as rass_index_delete)
+    std::lock_guard<std::mutex> lk(eng->mu);
+    if (src_row < 0 || src_row >= v->src_rows) return RASS_OK;   // not covered: the row lives in the flat delta only
+    const int32_t pos = v->pos_of[(size_t)src_row];
+    if (pos < 0) return RASS_OK;                                  // already gone
+    const int32_t dead = -1;
+    HIP_TRY(hipMemcpyAsync(v->d_tags + pos, &dead, 4, hipMemcpyHostToDevice, eng->stream));
+    HIP_TRY(hipStreamSynchronize(eng->stream));                   // `dead` is a stack variable
+    v->pos_of[(size_t)src_row] = -1;
+    v->any_tags = true;
+    v->rows -= 1;
+    return RASS_OK;
+}
+
+// Caller holds eng->mu (the probe scratch of the IVF object and the engine scratch are shared).
+static int ivf_search_locked(rass_ivf_t* v, const float* d_queries, int nq, int k, int nprobe,
+                             const int32_t* d_q_filter, float* d_out_scores, int64_t* d_out_ids,
+                             const int32_t* d_q_filter_mask = nullptr) {
+    if (!v || !d_queries || !d_out_scores || !d_out_ids) return fail(RASS_ERR_INVALID, "NULL argument");
+    if (nprobe < 1) return fail(RASS_ERR_INVALID, "nprobe must be >= 1");
+    if (int rc = check_nq(nq)) return rc;
+    rass_engine* eng = v->eng;
+    int rc = set_device(eng);
+    if (rc != RASS_OK) return rc;
+    hipStream_t st = eng->stream;
+    const int np = std::min(nprobe, v->nlist);
+    const int n_ctiles = (v->nlist + 31) / 32;
+    // what the coarse and the fine scan share: the caller's queries, one launch group, the engine's scratch and stream
+    ScanRequest s = scan_request(eng);
+    s.stride = v->stride, s.queries = d_queries, s.q_dim = v->dim, s.q_stride = v->dim, s.nq = nq;
+    if (np <= RASS_MAX_K || n_ctiles > kMaxGrid) {
+        // (i) coarse: top-nprobe centroids per query with the flat fused scan
+        ScanRequest c = s;
+        c.corpus = v->d_centroids, c.n_rows = v->nlist, c.k = std::min(np, RASS_MAX_K);
+        c.out_scores = v->d_probe_scores, c.out_ids = v->d_probe_ids;
+        rc = scan_launch(c);
+        if (rc != RASS_OK) return rc;
+        // (ii) plan: union of probed lists -> work tiles with per-tile query masks
+        HIP_TRY(rass::launch_plan_probe(v->d_probe_ids, nq, std::min(np, RASS_MAX_K), v->nlist, v->d_list_tile0,
+                                        v->d_list_len, v->d_work_tile, v->d_work_rows, v->d_work_mask, v->d_n_work,
+                                        v->d_scanned, st, nullptr, v->tile_rows));
+    } else {
+        // nprobe > 32: one workgroup per 32-centroid tile with k = 32 leaves EVERY centroid score in
+        // the per-workgroup lists; radix-select the nprobe-th best per query, mask by threshold
+        const ScratchView L = scratch_layout(eng->d_scratch, nq, RASS_MAX_K);
+        HIP_TRY(rass::launch_normalize_rows_f32(d_queries, v->dim, L.q_padded, v->stride, nq, v->dim, st, pad_nq(nq)));
+        rass::ScanArgs a;
+        a.corpus = v->d_centroids;
+        a.row_tag = nullptr;
+        a.q_padded = L.q_padded;
+        a.q_filter = nullptr;
+        a.part_scores = L.part_scores;
+        a.part_ids = L.part_ids;
+        a.row_stride = v->stride;
+        a.id_base = 0;
+        a.n_rows = v->nlist;
+        a.nq = nq;
+        a.k = RASS_MAX_K;
+        HIP_TRY(rass::launch_scan_topk_f32(a, n_ctiles, st));
+        HIP_TRY(rass::launch_ivf_threshold(L.part_scores, L.part_ids, n_ctiles, nq, np, v->d_tau, st));
+        HIP_TRY(rass::launch_ivf_mask_from_scores(L.part_scores, L.part_ids, n_ctiles, nq, v->nlist, v->d_tau,
+                                                  v->d_list_mask, st));
+        HIP_TRY(rass::launch_plan_probe(v->d_probe_ids, nq, 1, v->nlist, v->d_list_tile0, v->d_list_len, v->d_work_tile,
+                                        v->d_work_rows, v->d_work_mask, v->d_n_work, v->d_scanned, st, v->d_list_mask,
+                                        v->tile_rows));
+    }
+    // (iii) fine: the same fused scan over the planned tiles; slab positions -> source ids in the merge
+    const IvfPlan plan{v->d_work_tile, v->d_work_rows, v->d_work_mask, v->d_n_work, v->total_tiles};
+    const int32_t* row_tag = (v->any_tags || d_q_filter != nullptr) ? v->d_tags : nullptr;
+    // (both branches above left the batch's normalised queries at the head of the engine scratch, at this stride)
+    if (v->dtype == RASS_F32) {
+        s.corpus = v->d_slab, s.n_rows = v->slab_rows, s.row_tag = row_tag, s.q_filter = d_q_filter, s.k = k;
+        s.out_scores = d_out_scores, s.out_ids = d_out_ids, s.timing = eng, s.plan = &plan, s.id_map = v->d_ids;
+        s.ext.d_q_mask = d_q_filter_mask;
+        s.queries_prepared = true;
+        return scan_launch(s);
+    }
+    const ScratchView L = scratch_layout(eng->d_scratch, RASS_MAX_QBATCH, RASS_MAX_K);
+    if (v->dtype == RASS_BF16) {
+        // the bf16 scan over the planned 64-row tiles: queries rounded to bf16, fp32 accumulation, slab positions -> source
+        // ids in the merge.  Scores are those of a flat bf16 index holding the same rows.
+        HIP_TRY(rass::launch_queries_to_bf16(L.q_padded, L.q_bf16, (int64_t)pad_nq(nq) * v->stride, st));
+        const int grid = scan_grid(v->total_tiles, k, eng->n_cus);
+        rass::ScanBf16Args a = bf16_args(v, row_tag, k);
+        a.q_bf16 = L.q_bf16;
+        a.q_filter = d_q_filter;
+        a.q_filter_mask = d_q_filter_mask;
+        a.part_scores = L.part_scores;
+        a.part_ids = L.part_ids;
+        a.nq = nq;
+        set_plan(a, plan);
+        rc = timed_launch(eng, st, [&] { return HIP_RC(rass::launch_scan_bf16_topk(a, grid, st)); });
+        if (rc != RASS_OK) return rc;
+        HIP_TRY(rass::launch_merge_topk(L.part_scores, L.part_ids, grid, nq, k, d_out_scores, d_out_ids, st, v->d_ids));
+        return RASS_OK;
+    }
+    // RASS_I8: the int8 scan over the planned 64-row tiles keeps 32 candidates per query (slab positions); the re-rank rescores
+    // them exactly from the fp32 slab in the flat kernel's order and returns the best k under (score desc, source id asc)
+    if (k > kPrefilterMaxK) return fail(RASS_ERR_UNSUPPORTED, "an int8 IVF slab serves k <= 16 (32 candidates per query)");
+    signed char* q_i8 = reinterpret_cast<signed char*>(L.q_bf16);
+    const int kc = RASS_MAX_K;
+    HIP_TRY(rass::launch_queries_to_i8(L.q_padded, q_i8, pad_nq(nq), v->stride, v->stride_i8, st));
+    const int grid = scan_grid(v->total_tiles, kc, eng->n_cus);
+    rass::ScanI8Args a = i8_args(v, row_tag, kc);
+    a.q_i8 = q_i8;
+    a.q_filter = d_q_filter;
+    a.q_filter_mask = d_q_filter_mask;
+    a.part_scores = L.part_scores;
+    a.part_ids = L.part_ids;
+    a.nq = nq;
+    set_plan(a, plan);
+    rc = timed_launch(eng, st, [&] { return HIP_RC(rass::launch_scan_i8_topk(a, grid, st)); });
+    if (rc != RASS_OK) return rc;
+    HIP_TRY(rass::launch_merge_topk(L.part_scores, L.part_ids, grid, nq, kc, v->d_cand_scores, v->d_cand_rows, st));
+    HIP_TRY(rass::launch_rerank_f32(v->d_slab, v->stride, L.q_padded, v->d_cand_rows, nq, kc, k, 0, d_out_scores, d_out_ids, st,
+                                    0, 0, v->d_ids));
+    return RASS_OK;
+}
+
+// One launch group of an IVF + delta search; the caller holds eng->mu.  List 0 = the probe (source ordinals through the
+// slab's id map), list 1 = the exact scan of the source rows the IVF does not cover (ordinals through id_base); the
+// final merge orders them by (score desc, ordinal asc) and maps ordinals to the source's caller-assigned ids, if any.
+static int ivf_delta_group_locked(rass_ivf_t* v, rass_index* flat, const float* d_queries, int nq, int k, int nprobe,
+                                  const int32_t* d_q_filter, const int32_t* d_q_filter_mask, float* d_out_scores,
+                                  int64_t* d_out_ids) {
+    rass_engine* eng = v->eng;
+    if (!flat || flat->eng != eng) return fail(RASS_ERR_INVALID, "the delta index must live on the IVF's engine");
+    if (flat->dtype != RASS_F32 || flat->stride != v->stride || flat->dim != v->dim)
+        return fail(RASS_ERR_UNSUPPORTED, "the delta index must be the fp32 index the IVF was built from");
+    if (int rc = check_k(k)) return rc;
+    if (d_q_filter_mask && !d_q_filter) return fail(RASS_ERR_INVALID, "q_filter_mask without q_filter");
+    const int64_t rows = flat->rows.load(std::memory_order_acquire);
+    const int64_t covered = v->src_rows;
+    if (covered > rows) return fail(RASS_ERR_INVALID, "the IVF covers more rows than the delta index holds");
+    const int64_t delta = rows - covered;
+    if (delta > 0 && covered % 32 != 0)
+        return fail(RASS_ERR_UNSUPPORTED, "an IVF with a delta must cover a multiple of 32 source rows (rass_ivf_build_prefix)");
+    const bool gid = flat->has_gid.load(std::memory_order_acquire);
+    hipStream_t st = eng->stream;
+    float* ps = v->d_pair_scores;
+    int64_t* pi = v->d_pair_ids;
+    int rc = ivf_search_locked(v, d_queries, nq, k, nprobe, d_q_filter, ps, pi, d_q_filter_mask);
+    if (rc != RASS_OK) return rc;
+    int n_lists = 1;
+    if (delta > 0) {
+        const bool need_tags = (flat->deleted.load(std::memory_order_acquire) > 0) || (d_q_filter != nullptr);
+        ScanRequest s = scan_request(eng);
+        s.corpus = flat->d_rows + covered * flat->stride, s.n_rows = delta, s.stride = flat->stride;
+        s.row_tag = need_tags ? flat->d_tags + covered : nullptr;
+        s.queries = d_queries, s.q_dim = flat->dim, s.q_stride = flat->dim, s.nq = nq, s.q_filter = d_q_filter;
+        s.k = k, s.id_base = covered, s.out_scores = ps + (int64_t)nq * k, s.out_ids = pi + (int64_t)nq * k;
+        s.timing = eng;
+        s.ext.d_q_mask = d_q_filter_mask;
+        rc = scan_launch(s);
+        if (rc != RASS_OK) return rc;
+        n_lists = 2;
+    }
+    HIP_TRY(rass::launch_merge_topk(ps, pi, n_lists, nq, k, d_out_scores, d_out_ids, st, gid ? flat->d_gid : nullptr));
+    return RASS_OK;
+}
+
+int rass_ivf_search_delta_device(rass_ivf_t* v, rass_index_t* flat, const float* d_queries, int nq, int k, int nprobe,
+                                 const int32_t* d_q_filter, const int32_t* d_q_filter_mask, float* d_out_scores,
+                                 int64_t* d_out_ids) {
+    if (!v || !flat || !d_queries || !d_out_scores || !d_out_ids) return fail(RASS_ERR_INVALID, "NULL argument");
+    if (int rc = check_nq(nq)) return rc;
+    int rc = set_device(v->eng);
+    if (rc != RASS_OK) return rc;
+    std::lock_guard<std::mutex> lk(v->eng->mu);
+    return ivf_delta_group_locked(v, flat, d_queries, nq, k, nprobe, d_q_filter, d_q_filter_mask, d_out_scores, d_out_ids);
+}
+
+// The host round trip of rass_ivf_search and rass_ivf_search_delta (flat = nullptr: no delta): launch groups of <= 32
+// queries through a pinned slot; the engine lock is held while enqueuing only (shared device staging is safe by stream order).
+struct IvfHostCall {   // the caller's HOST arrays of a whole call: any nq
+    const float* queries;
+    int nq, k;
+    const int32_t *q_filter, *q_filter_mask;
+    float* out_scores;
+    int64_t* out_ids;
+};
+static int ivf_search_host(rass_ivf_t* v, rass_index_t* flat, const IvfHostCall& r, int nprobe, int64_t* scanned_rows) {
+    const int nq = r.nq, k = r.k;
+    rass_engine* eng = v->eng;
+    int rc = set_device(eng);
+    if (rc != RASS_OK) return rc;
+    int64_t scanned_total = 0;
+    SlotGuard guard(eng);
+    HostSlot* sl = guard.sl;
+    for (int done = 0; done < nq;) {
+        const int b = std::min(RASS_MAX_QBATCH, nq - done);
+        slot_fill(sl, v->dim, r.queries + (int64_t)done * v->dim, r.q_filter ? r.q_filter + done : nullptr,
+                  r.q_filter_mask ? r.q_filter_mask + done : nullptr, b);
+        {
+            std::lock_guard<std::mutex> lk(eng->mu);
+            rc = slot_upload(eng, sl, v->dim, r.q_filter != nullptr, r.q_filter_mask != nullptr, b);
+            if (rc != RASS_OK) return rc;
+            const int32_t* d_filter = r.q_filter ? eng->d_qfilter : nullptr;
+            if (flat)
+                rc = ivf_delta_group_locked(v, flat, eng->d_qraw, b, k, nprobe, d_filter, r.q_filter_mask ? eng->d_qmask : nullptr,
+                                            eng->d_out_scores, eng->d_out_ids);
+            else
+                rc = ivf_search_locked(v, eng->d_qraw, b, k, nprobe, d_filter, eng->d_out_scores, eng->d_out_ids);
+            if (rc != RASS_OK) return rc;
+            rc = slot_download(eng, sl, b, k, v->d_scanned);
+            if (rc != RASS_OK) return rc;
+        }
+        HIP_TRY(hipEventSynchronize(sl->done));
+        memcpy(r.out_scores + (int64_t)done * k, sl->h_out_s, (size_t)b * k * 4);
+        memcpy(r.out_ids + (int64_t)done * k, sl->h_out_i, (size_t)b * k * 8);
+        scanned_total += *sl->h_scanned;
+        if (flat) scanned_total += std::max<int64_t>(0, flat->rows.load() - v->src_rows);
+        done += b;
+    }
+    if (scanned_rows) *scanned_rows = scanned_total;
+    return RASS_OK;
+}
+
+int rass_ivf_search_delta(rass_ivf_t* v, rass_index_t* flat, const float* queries, int nq, int k, int nprobe,
+                          const int32_t* q_filter, const int32_t* q_filter_mask, float* out_scores, int64_t* out_ids,
+                          int64_t* scanned_rows) {
+    if (!v || !flat || !out_scores || !out_ids) return fail(RASS_ERR_INVALID, "NULL argument");
+    if (nq < 0 || (nq > 0 && !queries)) return fail(RASS_ERR_INVALID, "bad queries / nq");
+    if (int rc = check_k(k)) return rc;
+    if (q_filter_mask && !q_filter) return fail(RASS_ERR_INVALID, "q_filter_mask without q_filter");
+    return ivf_search_host(v, flat, {queries, nq, k, q_filter, q_filter_mask, out_scores, out_ids}, nprobe, scanned_rows);
+}
+
+// The block of rass_ivf_search_device_batch (rass_ivf::d_batch) for G groups.
+struct IvfBatchView {
+    float* q_all;            // [G][32][stride] normalised queries
+    unsigned short* qb_all;  // bf16 / int8 slabs: the converted queries
+    float* cs;               // coarse lists, cper elements per group
+    int64_t* ci;
+    float* fs;               // fine lists, fper elements per group
+    int64_t* fi;
+    int32_t *wt, *wr;        // work lists, `cap` items per group
+    uint32_t* wm;
+    int32_t* nw;             // [G] items per group
+    int64_t* sc;             // [G] rows scanned per group
+    float* cds;              // int8: the merged candidates [G][32][32]
+    int64_t* cdr;
+    size_t total;
+};
+
+static IvfBatchView ivf_batch_layout(unsigned char* base, const rass_ivf* v, int G, int64_t cper, int64_t fper) {
+    Carver c{base};
+    IvfBatchView L;
+    const bool i8 = v->dtype == RASS_I8;
+    const size_t cap = (size_t)v->total_tiles;
+    L.q_all = c.take<float>((size_t)G * 32 * v->stride * 4);
+    L.qb_all = c.take<unsigned short>(v->dtype != RASS_F32 ? (size_t)G * 32 * kMaxStride * 2 : 0);
+    L.cs = c.take<float>((size_t)G * cper * 4);
+    L.ci = c.take<int64_t>((size_t)G * cper * 8);
+    L.fs = c.take<float>((size_t)G * fper * 4);
+    L.fi = c.take<int64_t>((size_t)G * fper * 8);
+    L.wt = c.take<int32_t>(G * cap * 4);
+    L.wr = c.take<int32_t>(G * cap * 4);
+    L.wm = c.take<uint32_t>(G * cap * 4);
+    L.nw = c.take<int32_t>((size_t)G * 4);
+    L.sc = c.take<int64_t>((size_t)G * 8);
+    L.cds = c.take<float>(i8 ? (size_t)G * 32 * RASS_MAX_K * 4 : 0);
+    L.cdr = c.take<int64_t>(i8 ? (size_t)G * 32 * RASS_MAX_K * 8 : 0);
+    L.total = c.off;
+    return L;
+}
+
+// A whole batch of launch groups (nq <= 1 024 queries) of an IVF probe with 4 + G launches instead of 5 G: ONE normalise,
+// ONE grouped coarse scan (kFlatGroups: every group's 32 queries over the centroid slab, 8 workgroups per group), ONE plan
+// launch (a workgroup per group; the coarse lists are merged inside it), the G fine scans over their groups' work lists,
+// ONE grouped merge.  Same lists probed, same scores, same (score desc, id asc) order as rass_ivf_search_device group by
+// group (tests/test_gpu_ivf.py).  nprobe <= 32 (deeper probes go group by group through the threshold path).
+static int ivf_search_batch_locked(rass_ivf_t* v, const float* d_queries, int nq, int k, int nprobe,
+                                   const int32_t* d_q_filter, float* d_out_scores, int64_t* d_out_ids,
+                                   int64_t* d_scanned_per_group) {
+    rass_engine* eng = v->eng;
+    hipStream_t st = eng->stream;
+    const int np = std::min(nprobe, v->nlist);
+    const int G = (nq + RASS_MAX_QBATCH - 1) / RASS_MAX_QBATCH;
+    const int n_ctiles = (v->nlist + 31) / 32;
+    const int wpg = std::max(1, std::min(8, std::min(n_ctiles, 256 / np)));      // coarse workgroups per group
+    const int64_t stride = v->stride;
+    // fine-scan workgroups per group.  fp32 slab: ALL groups' fine scans are one launch (kIvfGroups) — the more groups, the
+    // fewer workgroups each (32 at 32 groups: 1 024 in all, dispatched in group order, no launch boundary between groups);
+    // bf16 slab: one launch per group over the whole chip.
+    const bool one_fine_launch = v->dtype == RASS_F32 && ivf_batch_one_launch();
+    const bool i8 = v->dtype == RASS_I8;
+    if (i8 && k > kPrefilterMaxK) return fail(RASS_ERR_UNSUPPORTED, "an int8 IVF slab serves k <= 16 (32 candidates per query)");
+    const int kf = i8 ? RASS_MAX_K : k;   // entries per fine list: the int8 scan keeps 32 candidates whatever k is
+    int fgrid = scan_grid(v->total_tiles, kf, eng->n_cus);
+    if (one_fine_launch) fgrid = std::max(1, std::min(fgrid, std::max(32, 1024 / G)));   // (both clamps are minima: their order does not matter)
+    const int64_t cper = (int64_t)wpg * 32 * np;                                   // coarse list elements per group
+    const int64_t fper = (int64_t)fgrid * 32 * kf;                                 // fine list elements per group
+    const int64_t cap = v->total_tiles;
+    int rc = grow_block(&v->d_batch, &v->batch_bytes, ivf_batch_layout(nullptr, v, G, cper, fper).total, st);
+    if (rc != RASS_OK) return rc;
+    const IvfBatchView L = ivf_batch_layout(v->d_batch, v, G, cper, fper);
+
+    // (1) every query normalised and zero-padded, the groups' 32-row blocks back to back
+    HIP_TRY(rass::launch_normalize_rows_f32(d_queries, v->dim, L.q_all, stride, nq, v->dim, st, (int64_t)G * 32));
+    // (2) coarse: all groups in one launch
+    {
+        rass::ScanArgs a;
+        a.corpus = v->d_centroids;
+        a.row_tag = nullptr;
+        a.q_padded = L.q_all;
+        a.q_filter = nullptr;
+        a.part_scores = L.cs;
+        a.part_ids = L.ci;
+        a.row_stride = stride;
+        a.id_base = 0;
+        a.n_rows = v->nlist;
+        a.nq = 32;
+        a.k = np;
+        a.wgs_per_group = wpg;
+        a.q_group_stride = 32 * stride;
+        a.part_group_stride = cper;
+        HIP_TRY(rass::launch_scan_topk_f32(a, G * wpg, st));
+    }
+    // (3) plan: one workgroup per group, the coarse lists merged inside
+    HIP_TRY(rass::launch_plan_probe_groups(L.cs, L.ci, wpg, np, G, nq, cper, v->nlist, v->d_list_tile0, v->d_list_len, L.wt, L.wr,
+                                           L.wm, cap, L.nw, L.sc, st, v->tile_rows));
+    // (4) the fine scans, one per group, over the group's work list
+    const int32_t* row_tag = (v->any_tags || d_q_filter != nullptr) ? v->d_tags : nullptr;
+    if (v->dtype == RASS_BF16) HIP_TRY(rass::launch_queries_to_bf16(L.q_all, L.qb_all, (int64_t)G * 32 * stride, st));
+    if (i8) HIP_TRY(rass::launch_queries_to_i8(L.q_all, L.qb_all, G * 32, stride, v->stride_i8, st));
+    // the fp32 fine scan of group g (g = 0 with the grouped fields added: all groups)
+    auto f32_args = [&](int g) {
+        rass::ScanArgs a;
+        a.corpus = v->d_slab;
+        a.row_tag = row_tag;
+        a.q_padded = L.q_all + (int64_t)g * 32 * stride;
+        a.q_filter = d_q_filter ? d_q_filter + g * 32 : nullptr;
+        a.part_scores = L.fs + g * fper;
+        a.part_ids = L.fi + g * fper;
+        a.row_stride = stride;
+        a.id_base = 0;
+        a.n_rows = (int)v->slab_rows;
+        a.k = k;
+        return a;
+    };
+    if (one_fine_launch) {
+        rass::ScanArgs a = f32_args(0);
+        a.q_filter = d_q_filter;
+        a.nq = 32;
+        set_plan(a, IvfPlan{L.wt, L.wr, L.wm, L.nw, cap});
+        a.wgs_per_group = fgrid;
+        a.q_group_stride = 32 * stride;
+        a.part_group_stride = fper;
+        a.work_group_stride = cap;
+        a.nq_total = nq;
+        rc = timed_launch(eng, st, [&] { return HIP_RC(rass::launch_scan_topk_f32(a, G * fgrid, st)); });
+        if (rc != RASS_OK) return rc;
+    }
+    for (int g = 0; g < G && !one_fine_launch; ++g) {
+        const int b = std::min(RASS_MAX_QBATCH, nq - g * 32);
+        const IvfPlan plan{L.wt + g * cap, L.wr + g * cap, L.wm + g * cap, L.nw + g, cap};
+        rc = timed_launch(eng, st, [&] {
+            if (v->dtype == RASS_BF16) {
+                rass::ScanBf16Args a = bf16_args(v, row_tag, k);
+                a.q_bf16 = L.qb_all + (int64_t)g * 32 * stride;
+                a.q_filter = d_q_filter ? d_q_filter + g * 32 : nullptr;
+                a.part_scores = L.fs + g * fper;
+                a.part_ids = L.fi + g * fper;
+                a.nq = b;
+                set_plan(a, plan);
+                return HIP_RC(rass::launch_scan_bf16_topk(a, fgrid, st));
+            }
+            if (i8) {
+                rass::ScanI8Args a = i8_args(v, row_tag, kf);
+                a.q_i8 = reinterpret_cast<const signed char*>(L.qb_all) + (int64_t)g * 32 * v->stride_i8;
+                a.q_filter = d_q_filter ? d_q_filter + g * 32 : nullptr;
+                a.part_scores = L.fs + g * fper;
+                a.part_ids = L.fi + g * fper;
+                a.nq = b;
+                set_plan(a, plan);
+                return HIP_RC(rass::launch_scan_i8_topk(a, fgrid, st));
+            }
+            rass::ScanArgs a = f32_args(g);
+            a.nq = b;
+            set_plan(a, plan);
+            return HIP_RC(rass::launch_scan_topk_f32(a, fgrid, st));
+        });
+        if (rc != RASS_OK) return rc;
+    }
+    // (5) one grouped merge: slab positions -> source row ids
+    const rass::MergeGroups mg = dense_groups(nq, fper, (int64_t)RASS_MAX_QBATCH * kf, (int64_t)RASS_MAX_QBATCH * kf);
+    if (i8) {   // candidates (slab positions) of every group, then ONE exact re-rank over all queries
+        HIP_TRY(rass::launch_merge_topk(L.fs, L.fi, fgrid, nq, kf, L.cds, L.cdr, st, nullptr, 0, 0, &mg));
+        HIP_TRY(rass::launch_rerank_f32(v->d_slab, stride, L.q_all, L.cdr, nq, kf, k, 0, d_out_scores, d_out_ids, st, 0, 0, v->d_ids));
+    } else
+    HIP_TRY(rass::launch_merge_topk(L.fs, L.fi, fgrid, nq, k, d_out_scores, d_out_ids, st, v->d_ids, 0, 0, &mg));
+    if (d_scanned_per_group) HIP_TRY(hipMemcpyAsync(d_scanned_per_group, L.sc, (size_t)G * 8, hipMemcpyDeviceToDevice, st));
+    return RASS_OK;
+}
+
+int rass_ivf_search_device_batch(rass_ivf_t* v, const float* d_queries, int nq, int k, int nprobe,
+                                 const int32_t* d_q_filter, float* d_out_scores, int64_t* d_out_ids,
+                                 int64_t* d_scanned_per_group) {
+    if (!v || !d_queries || !d_out_scores || !d_out_ids) return fail(RASS_ERR_INVALID, "NULL argument");
+    if (nq < 1 || nq > 32 * RASS_MAX_QBATCH) return fail(RASS_ERR_INVALID, "nq must be in [1, 1024]");
+    if (int rc = check_k(k)) return rc;
+    if (nprobe < 1) return fail(RASS_ERR_INVALID, "nprobe must be >= 1");
+    int rc = set_device(v->eng);
+    if (rc != RASS_OK) return rc;
+    std::lock_guard<std::mutex> lk(v->eng->mu);
+    if (std::min(nprobe, v->nlist) > RASS_MAX_K) {
+        // deep probes: the threshold path, group by group
+        for (int g = 0; g * RASS_MAX_QBATCH < nq; ++g) {
+            const int b = std::min(RASS_MAX_QBATCH, nq - g * RASS_MAX_QBATCH);
+            rc = ivf_search_locked(v, d_queries + (int64_t)g * RASS_MAX_QBATCH * v->dim, b, k, nprobe,
+                                   d_q_filter ? d_q_filter + g * RASS_MAX_QBATCH : nullptr,
+                                   d_out_scores + (int64_t)g * RASS_MAX_QBATCH * k, d_out_ids + (int64_t)g * RASS_MAX_QBATCH * k);
+            if (rc != RASS_OK) return rc;
+            if (d_scanned_per_group)
+                HIP_TRY(hipMemcpyAsync(d_scanned_per_group + g, v->d_scanned, 8, hipMemcpyDeviceToDevice, v->eng->stream));
+        }
+        return RASS_OK;
+    }
+    return ivf_search_batch_locked(v, d_queries, nq, k, nprobe, d_q_filter, d_out_scores, d_out_ids, d_scanned_per_group);
+}
+
+int rass_ivf_search_device(rass_ivf_t* v, const float* d_queries, int nq, int k, int nprobe,
+                           const int32_t* d_q_filter, float* d_out_scores, int64_t* d_out_ids) {
+    if (!v) return fail(RASS_ERR_INVALID, "NULL argument");
+    std::lock_guard<std::mutex> lk(v->eng->mu);
+    return ivf_search_locked(v, d_queries, nq, k, nprobe, d_q_filter, d_out_scores, d_out_ids);
+}
+
+int rass_ivf_search(rass_ivf_t* v, const float* queries, int nq, int k, int nprobe, const int32_t* q_filter,
+                    float* out_scores, int64_t* out_ids, int64_t* scanned_rows) {
+    if (!v || !out_scores || !out_ids) return fail(RASS_ERR_INVALID, "NULL argument");
+    if (nq < 0 || (nq > 0 && !queries)) return fail(RASS_ERR_INVALID, "bad queries / nq");
+    if (int rc = check_k(k)) return rc;
+    return ivf_search_host(v, nullptr, {queries, nq, k, q_filter, nullptr, out_scores, out_ids}, nprobe, scanned_rows);
+}
+
+}  // extern "C"

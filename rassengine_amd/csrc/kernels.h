@@ -1,4 +1,4 @@
-// kernels.h — internal launcher interface between the C-ABI layer (api.hip) and the
+// kernels.h — internal launcher interface between the C-ABI layer (api_*.hip) and the
 // gfx950 kernels.  Not part of the public ABI (include/rass_engine.h is).
 #pragma once
 

@@ -402,7 +402,7 @@ __global__ __launch_bounds__(kThreads, 2) void scan_topk_f32_kernel(ScanArgs p) 
 }
 
 // ------------------------------------------------------------------------------------------
-// 64 queries per corpus pass: TWO consecutive full launch groups of a batch call in one launch (api.hip,
+// 64 queries per corpus pass: TWO consecutive full launch groups of a batch call in one launch (api_search.hip,
 // scan_launch_batch).  At 32 queries per pass the kernel above sits in the corner of the HBM rate and the fp32 MFMA
 // rate; a step of 1 024 queries streams the corpus 32 times.  This sibling streams it 16 times: the same 512 threads,
 // the same K split over the 8 waves and the same v_mfma_f32_16x16x4_f32 chain per (row, query) in k order from zero,
@@ -601,7 +601,7 @@ __global__ __launch_bounds__(kThreads, 2) void scan_topk_f32_pair_kernel(ScanArg
 // fmaf chain of the slice runs on in k order: a score is the same fixed sequence the oracle's emulation restates for
 // this stride), and each consumed register is refilled with the panel TWO steps ahead in the (tile, panel) sequence.
 // The query fragments of all panels stay in registers (row_stride / 32 VGPRs): that is what limits this kernel to 16
-// queries per launch (NT = 1; a 32-query group runs as two launches, api.hip).  Flat scans only (no IVF plan, no
+// queries per launch (NT = 1; a 32-query group runs as two launches, api_scan.hip).  Flat scans only (no IVF plan, no
 // cross-index work list, no sample floor: with <= 16 queries the scan is HBM-bound and the ranking hides under it).
 // Everything else — descriptors, XCD-aware item order, LDS images, one barrier per tile pair, ranking of the previous
 // pair between the MFMA chunks, register-only insertion, EXT filters / continuation bound — is the kernel above.

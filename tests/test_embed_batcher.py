@@ -255,7 +255,7 @@ class _FakeIndex:
 
 
 class _FakeEngine:
-    """rass_index_search_multi's admission rules (api.hip): fp32, plain ids, <= 65 536 tiles over the distinct indices."""
+    """rass_index_search_multi's admission rules (api_search.hip): fp32, plain ids, <= 65 536 tiles over the distinct indices."""
 
     def __init__(self):
         self.calls = []

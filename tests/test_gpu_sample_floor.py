@@ -1,4 +1,4 @@
-"""The scan's sample floor (api.hip scan_launch, ScanArgs::floors): a pre-pass over the first tile pair of every
+"""The scan's sample floor (api_scan.hip scan_launch, ScanArgs::floors): a pre-pass over the first tile pair of every
 workgroup gives each query a score that k rows are known to reach, and the big scan skips rows below it.  It must
 never change a result: same ids and bit-identical scores with it on, off and forced, against the CPU oracle, with
 filters whose matches are rare in the sample, tombstones, duplicated rows (ties with the floor) and k > 32 passes.

@@ -15,7 +15,7 @@ TOL_F64_WIDE = 3e-6  # the same for 1 024 < D <= 2 048 (twice as many fmaf steps
 
 
 def _stride(dim):
-    """api.hip pad_stride: whole 128-column units up to 1 024 columns, whole 256-column units above."""
+    """api_internal.h pad_stride: whole 128-column units up to 1 024 columns, whole 256-column units above."""
     return (dim + 127) // 128 * 128 if dim <= 1024 else (dim + 255) // 256 * 256
 
 
