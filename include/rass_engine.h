@@ -155,6 +155,22 @@ int rass_index_add_ex(rass_index_t* idx, const float* vecs, const int32_t* tags,
                       int device_source, int64_t* first_row);
 /* Tombstone a row (the overwrite semantics of `_id=doc_id`, app/main.py:1260). */
 int rass_index_delete(rass_index_t* idx, int64_t row);
+/* Remove every tombstoned row: live rows keep their relative order and their stored bits and take the
+ * ordinals 0 .. live-1; rass_index_rows() == rass_index_count() afterwards.  new_row_of (host, may be NULL)
+ * receives, for each of the *rows_before old ordinals, the new ordinal or -1; map_capacity < rows ->
+ * RASS_ERR_INVALID and nothing changes.  Caller-assigned ids (rass_index_add_ex) travel with their rows.
+ * Out of place: needs HBM for the compacted index next to the old one; RASS_ERR_OOM leaves the index as it was.
+ * No tombstone -> RASS_OK, identity map, nothing moved, layout epoch unchanged.
+ * fp32 indices in every prefilter mode (the candidate copies are rebuilt from the moved rows; mode 3's
+ * certificate maxima and counters are kept) and bf16 indices.  The HBM the index holds afterwards is that of
+ * its live rows (at least 1 024).  An IVF built from the index names its old ordinals: rebuild it. */
+int rass_index_compact(rass_index_t* idx, int64_t* new_row_of, int64_t map_capacity,
+                       int64_t* rows_before, int64_t* rows_after);
+/* Number of compactions that moved rows: a row ordinal is only meaningful together with this value.
+ * The host search entry points (rass_index_search, _ex, _multi) answer from ONE layout: read the epoch
+ * before and after such a call, and where the two agree the ids are ordinals of that layout.  The device
+ * entry points are asynchronous: pair their ids with the epoch read before the call.  0 after open / load. */
+int64_t rass_index_layout_epoch(const rass_index_t* idx);
 /* Copy one stored (normalised) row back to the host as fp32 (dim floats): the
  * reference returns the embedding inside `_source` (app/main.py:1555-1557). */
 int rass_index_get_row(rass_index_t* idx, int64_t row, float* out);
@@ -308,6 +324,21 @@ int rass_unpack_rows_f32(const float* d_packed, int64_t row_stride,
 int rass_gather_rows_f32(const float* d_packed, int64_t row_stride, int64_t n_rows,
                          const int64_t* d_row_ids, int64_t n, int dim, float* d_out,
                          int64_t out_stride, void* stream);
+/* The two steps of rass_index_compact on caller-owned arrays (all device, stream-ordered, stateless).
+ * rass_compact_plan: d_tags[n_rows] -> d_new_row[n_rows] (the number of live rows below r, -1 where
+ *   d_tags[r] == RASS_ROW_TAG_DELETED), d_src_row[j] = the old row that becomes row j (j < n_live; give it
+ *   n_rows entries) and *d_n_live.  Three launches; no workgroup waits on another.  d_workspace: at least
+ *   rass_compact_plan_workspace_bytes(n_rows) bytes.
+ * rass_compact_rows_f32: tile16 slab d_dst (whole blocks, >= round_up(n_dst, 16) rows) <- rows
+ *   d_src_row[0 .. n_dst) of the tile16 slab d_src (n_src_rows rows; an entry outside it gives a zero row);
+ *   the rows of the last block past n_dst are zeroed.  Rows are moved, bit for bit.  d_dst != d_src. */
+int rass_compact_plan(const int32_t* d_tags, int64_t n_rows, int64_t* d_new_row,
+                      int64_t* d_src_row, int64_t* d_n_live, void* d_workspace,
+                      size_t workspace_bytes, void* stream);
+size_t rass_compact_plan_workspace_bytes(int64_t n_rows);
+int rass_compact_rows_f32(const float* d_src, float* d_dst, int64_t row_stride,
+                          const int64_t* d_src_row, int64_t n_dst, int64_t n_src_rows,
+                          void* stream);
 
 /* K1+K2: fused flat cosine scan + per-workgroup top-k + merge over a tile16
  * fp32 corpus slab in HBM.  Rows must already be normalised (rass_pack_rows_f32

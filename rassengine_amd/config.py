@@ -52,6 +52,15 @@ try:
     RASS_IVF_REBUILD_FRACTION = float(os.getenv("RASS_IVF_REBUILD_FRACTION", "0.25"))
 except ValueError:
     RASS_IVF_REBUILD_FRACTION = 0.25
+# Compaction of tombstoned rows (docstore.IndexState.compact, rass_index_compact): an `_id` overwrite appends the new row and
+# tombstones the old one, whose 4 KiB every later scan still streams.  RASS_COMPACT_FRACTION: 0 = never (the default);
+# > 0: add_documents compacts the index once its tombstones exceed that fraction of its rows and it holds at least
+# RASS_COMPACT_MIN_ROWS rows.  Out of place: needs HBM for the compacted index next to the old one.
+try:
+    RASS_COMPACT_FRACTION = float(os.getenv("RASS_COMPACT_FRACTION", "0"))
+except ValueError:
+    RASS_COMPACT_FRACTION = 0.0
+RASS_COMPACT_MIN_ROWS = _int("RASS_COMPACT_MIN_ROWS", 65536)
 
 
 def get_index_name(user_id: str) -> str:

@@ -7,6 +7,7 @@
 //   api_scan.hip     the tuning switches, the shared launch helpers declared below, and the four flat launch paths
 //   api_search.hip   flat search entry points: one group, the fused batches, the host API with its pinned slots, search_multi
 //   api_ivf.hip      IVF build, persistence, probe, delta and batch
+//   api_compact.hip  compaction of a flat index, its layout epoch, the stateless wrappers of compact.hip
 //
 // Ownership model: the engine singleton of a process owns the corpus slabs
 // for process lifetime; callers own every host buffer they pass in or get filled.
@@ -257,6 +258,9 @@ struct rass_index {
     unsigned* d_cert_stats = nullptr;
     unsigned long long* d_cert_counts = nullptr;
     std::vector<uint8_t> host_deleted;  // tombstone bitmap mirror (host)
+    // compactions that moved rows (rass_index_compact): a row ordinal is only meaningful together with this value.
+    // Written under mu + eng->mu; the host search entry points read it around their launch groups
+    std::atomic<int64_t> layout_epoch{0};
     std::mutex mu;
 };
 
@@ -291,6 +295,7 @@ struct rass_ivf {
     // IVF + flat delta (rass_ivf_search_delta*): the IVF covers source rows [0, src_rows); rows the source index took
     // afterwards are scanned exactly from its own slab and merged with the probe's list
     int64_t src_rows = 0;
+    int64_t src_epoch = -1;           // layout epoch of the source index the ids name; -1 (a loaded IVF): adopted from the first source searched
     std::vector<int32_t> pos_of;      // host: slab position of source row r (< src_rows), -1 = not in the slab (tombstoned)
     float* d_pair_scores = nullptr;   // [2][32][32] the probe's list and the delta scan's list of one launch group
     int64_t* d_pair_ids = nullptr;
@@ -304,6 +309,7 @@ namespace host {
 int set_device(const rass_engine* eng);
 int index_reserve(rass_index* idx, int64_t need_rows);   // api.hip; the caller holds idx->mu and eng->mu
 void index_free_slabs(rass_index* idx);                  // every device array of the index, freed and nulled
+int index_refresh_copies(rass_index* idx, int64_t first, int64_t n, hipStream_t st);   // the prefilter mode's candidate copies of rows [first, first + n)
 
 // ---- the tuning switches (api_scan.hip: the only place of the host layer that reads the environment)
 int scan_xcd_skew(int nq, int grid, int n_cus);   // ScanArgs::xcd_skew of a launch; RASS_SCAN_XCD_SKEW, read once

@@ -102,6 +102,7 @@ int rass_ivf_build_prefix(rass_index_t* src, const float* centroids, int nlist, 
     v->rows = 0;
     for (int l = 0; l < nlist; ++l) v->rows += len[(size_t)l];
     v->src_rows = n;
+    v->src_epoch = src->layout_epoch.load();
     v->pos_of.assign((size_t)n, -1);
     for (int64_t d = 0; d < slab_rows; ++d)
         if (src_of[(size_t)d] >= 0) v->pos_of[(size_t)src_of[(size_t)d]] = (int32_t)d;
@@ -502,6 +503,11 @@ static int ivf_delta_group_locked(rass_ivf_t* v, rass_index* flat, const float* 
         return fail(RASS_ERR_UNSUPPORTED, "the delta index must be the fp32 index the IVF was built from");
     if (int rc = check_k(k)) return rc;
     if (d_q_filter_mask && !d_q_filter) return fail(RASS_ERR_INVALID, "q_filter_mask without q_filter");
+    // the IVF's ids are ordinals of the source as it was laid out at build time (a loaded IVF trusts its first source)
+    const int64_t epoch = flat->layout_epoch.load(std::memory_order_acquire);
+    if (v->src_epoch < 0) v->src_epoch = epoch;
+    if (v->src_epoch != epoch)
+        return fail(RASS_ERR_INVALID, "the source index was compacted after this IVF was built (its ids are stale ordinals): rebuild the IVF");
     const int64_t rows = flat->rows.load(std::memory_order_acquire);
     const int64_t covered = v->src_rows;
     if (covered > rows) return fail(RASS_ERR_INVALID, "the IVF covers more rows than the delta index holds");

@@ -287,6 +287,21 @@ int search_device_locked(rass_index_t* idx, const FlatRequest& r) {
 
 using namespace rass::host;
 
+// One layout per answer.  The host entry points below release eng->mu between launch groups and between the passes of a
+// k > 32 search, and a pass's continuation bound names a row ORDINAL: a compaction (rass_index_compact) landing in between
+// would mix two layouts in one answer.  They read the layout epoch(s) first and run again when it moved meanwhile — bounded:
+// a compaction is rare and takes far longer than a search.
+constexpr int kLayoutAttempts = 8;
+template <class Epoch, class Once>
+static int one_layout(Epoch&& epoch, Once&& once) {
+    for (int attempt = 0; attempt < kLayoutAttempts; ++attempt) {
+        const int64_t before = epoch();
+        const int rc = once();
+        if (rc != RASS_OK || epoch() == before) return rc;
+    }
+    return fail(RASS_ERR_UNSUPPORTED, "the index was compacted during every attempt of this search: try again");
+}
+
 extern "C" {
 
 int rass_index_search_device_ex(rass_index_t* idx, const float* d_queries, int nq, int k, const int32_t* d_q_filter,
@@ -405,12 +420,8 @@ int rass_index_candidates_exact_device(rass_index_t* idx, const float* d_queries
     return cert_launch(idx, r);
 }
 
-int rass_index_search_ex(rass_index_t* idx, const float* queries, int nq, int k, const int32_t* q_filter,
-                         const int32_t* q_filter_mask, float* out_scores, int64_t* out_ids) {
-    if (!idx || !out_scores || !out_ids) return fail(RASS_ERR_INVALID, "NULL argument");
-    if (nq < 0 || (nq > 0 && !queries)) return fail(RASS_ERR_INVALID, "bad queries / nq");
-    if (k < 1 || k > RASS_MAX_K_MULTIPASS) return fail(RASS_ERR_INVALID, "k must be in [1, RASS_MAX_K_MULTIPASS]");
-    if (q_filter_mask && !q_filter) return fail(RASS_ERR_INVALID, "q_filter_mask without q_filter");
+static int search_ex_once(rass_index_t* idx, const float* queries, int nq, int k, const int32_t* q_filter,
+                          const int32_t* q_filter_mask, float* out_scores, int64_t* out_ids) {
     rass_engine* eng = idx->eng;
     int rc = set_device(eng);
     if (rc != RASS_OK) return rc;
@@ -465,22 +476,18 @@ int rass_index_search_ex(rass_index_t* idx, const float* queries, int nq, int k,
     return RASS_OK;
 }
 
-int rass_index_search_multi(rass_index_t* const* idxs, const float* queries, int nq, int k, const int32_t* q_filter,
-                            const int32_t* q_filter_mask, float* out_scores, int64_t* out_ids) {
-    if (!idxs || !out_scores || !out_ids) return fail(RASS_ERR_INVALID, "NULL argument");
+int rass_index_search_ex(rass_index_t* idx, const float* queries, int nq, int k, const int32_t* q_filter,
+                         const int32_t* q_filter_mask, float* out_scores, int64_t* out_ids) {
+    if (!idx || !out_scores || !out_ids) return fail(RASS_ERR_INVALID, "NULL argument");
     if (nq < 0 || (nq > 0 && !queries)) return fail(RASS_ERR_INVALID, "bad queries / nq");
-    if (int rc = check_k(k)) return rc;
+    if (k < 1 || k > RASS_MAX_K_MULTIPASS) return fail(RASS_ERR_INVALID, "k must be in [1, RASS_MAX_K_MULTIPASS]");
     if (q_filter_mask && !q_filter) return fail(RASS_ERR_INVALID, "q_filter_mask without q_filter");
-    if (nq == 0) return RASS_OK;
-    rass_engine* eng = idxs[0] ? idxs[0]->eng : nullptr;
-    for (int q = 0; q < nq; ++q) {
-        if (!idxs[q]) return fail(RASS_ERR_INVALID, "NULL index");
-        if (idxs[q]->eng != eng) return fail(RASS_ERR_INVALID, "the indices of one batch must share an engine (one GPU)");
-        if (idxs[q]->dtype != RASS_F32) return fail(RASS_ERR_UNSUPPORTED, "cross-index batches are fp32-only");
-        if (idxs[q]->has_gid.load()) return fail(RASS_ERR_UNSUPPORTED, "cross-index batches need plain row ids");
-    }
-    if (eng && eng->dim > kNarrowStride)
-        return fail(RASS_ERR_UNSUPPORTED, "cross-index batches need dim <= 1024: search wide-row indices one by one");
+    return one_layout([&] { return idx->layout_epoch.load(std::memory_order_acquire); },
+                      [&] { return search_ex_once(idx, queries, nq, k, q_filter, q_filter_mask, out_scores, out_ids); });
+}
+
+static int search_multi_once(rass_engine* eng, rass_index_t* const* idxs, const float* queries, int nq, int k,
+                             const int32_t* q_filter, const int32_t* q_filter_mask, float* out_scores, int64_t* out_ids) {
     int rc = set_device(eng);
     if (rc != RASS_OK) return rc;
     const int dim = eng->dim;
@@ -577,6 +584,31 @@ int rass_index_search_multi(rass_index_t* const* idxs, const float* queries, int
         done += b;
     }
     return RASS_OK;
+}
+
+int rass_index_search_multi(rass_index_t* const* idxs, const float* queries, int nq, int k, const int32_t* q_filter,
+                            const int32_t* q_filter_mask, float* out_scores, int64_t* out_ids) {
+    if (!idxs || !out_scores || !out_ids) return fail(RASS_ERR_INVALID, "NULL argument");
+    if (nq < 0 || (nq > 0 && !queries)) return fail(RASS_ERR_INVALID, "bad queries / nq");
+    if (int rc = check_k(k)) return rc;
+    if (q_filter_mask && !q_filter) return fail(RASS_ERR_INVALID, "q_filter_mask without q_filter");
+    if (nq == 0) return RASS_OK;
+    rass_engine* eng = idxs[0] ? idxs[0]->eng : nullptr;
+    for (int q = 0; q < nq; ++q) {
+        if (!idxs[q]) return fail(RASS_ERR_INVALID, "NULL index");
+        if (idxs[q]->eng != eng) return fail(RASS_ERR_INVALID, "the indices of one batch must share an engine (one GPU)");
+        if (idxs[q]->dtype != RASS_F32) return fail(RASS_ERR_UNSUPPORTED, "cross-index batches are fp32-only");
+        if (idxs[q]->has_gid.load()) return fail(RASS_ERR_UNSUPPORTED, "cross-index batches need plain row ids");
+    }
+    if (eng && eng->dim > kNarrowStride)
+        return fail(RASS_ERR_UNSUPPORTED, "cross-index batches need dim <= 1024: search wide-row indices one by one");
+    // epochs only grow: their sum over the batch's indices stands still exactly when every one of them does
+    auto epochs = [&] {
+        int64_t sum = 0;
+        for (int q = 0; q < nq; ++q) sum += idxs[q]->layout_epoch.load(std::memory_order_acquire);
+        return sum;
+    };
+    return one_layout(epochs, [&] { return search_multi_once(eng, idxs, queries, nq, k, q_filter, q_filter_mask, out_scores, out_ids); });
 }
 
 int rass_index_search(rass_index_t* idx, const float* queries, int nq, int k, const int32_t* q_filter,

@@ -318,6 +318,22 @@ hipError_t launch_gather_rows_tile16(const float* packed, int64_t stride, const 
 hipError_t launch_fill_synthetic_f32(float* packed, int64_t stride, int64_t first_row, int64_t n, int dim,
                                      uint64_t seed, int64_t row_id_base, hipStream_t stream);
 
+// ---- compaction (compact.hip): tombstoned rows squeezed out of a slab, rows only moved
+// tags[n_rows] -> new_row[n_rows] (exclusive prefix count of the live rows, -1 for a tombstone), src_row[>= n_live] (its
+// inverse) and *n_live, all on the device; three launches, no workgroup waits on another.  workspace: compact_plan_workspace_bytes.
+size_t compact_plan_workspace_bytes(int64_t n_rows);
+hipError_t launch_compact_plan(const int32_t* tags, int64_t n_rows, int64_t* new_row, int64_t* src_row, int64_t* n_live,
+                               void* workspace, hipStream_t stream);
+// dst rows [0, n_dst) <- rows src_row[0 .. n_dst) of src, 16 bytes per lane, whole 1 KiB chunks per store; the rows of dst's
+// last block past n_dst are zeroed.  tile16 (fp32) and tile16b (bf16): one kernel body, two instantiations.
+hipError_t launch_compact_rows_tile16(const float* src, float* dst, int64_t row_stride, const int64_t* src_row, int64_t n_dst,
+                                      int64_t n_src_rows, hipStream_t stream);
+hipError_t launch_compact_rows_tile16b(const void* src, void* dst, int64_t row_stride, const int64_t* src_row, int64_t n_dst,
+                                       int64_t n_src_rows, hipStream_t stream);
+// dst[i] = src[src_row[i]], i < n (row tags, reported ids)
+hipError_t launch_gather_i32(const int32_t* src, int32_t* dst, const int64_t* src_row, int64_t n, int64_t n_src, hipStream_t stream);
+hipError_t launch_gather_i64(const int64_t* src, int64_t* dst, const int64_t* src_row, int64_t n, int64_t n_src, hipStream_t stream);
+
 hipError_t launch_fill_i32(int32_t* dst, int64_t n, int32_t value, hipStream_t stream);
 // dst[i] = base + i
 hipError_t launch_iota_i64(int64_t* dst, int64_t n, int64_t base, hipStream_t stream);

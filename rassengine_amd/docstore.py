@@ -84,6 +84,7 @@ class IndexState:
         self._dead_since: List[int] = []         # rows < _ckpt_rows tombstoned since
         self._structured_dirty: set = set()      # structured doc_ids (re)written since
         self._delta_seq = 0                      # delta segments written on top of the current snapshot
+        self._delta_broken = False               # a compaction renumbered the rows: the log is unusable until the next save()
 
     def live_count(self) -> int:
         return len(self.doc_row) + len(self.structured)
@@ -95,6 +96,27 @@ class IndexState:
 
     def note_structured(self, doc_id: str) -> None:
         self._structured_dirty.add(doc_id)
+
+    # ---- compaction: tombstoned rows leave the index (FlatIndex.compact) and every ordinal kept here follows
+    def compact(self) -> Tuple[int, int]:
+        """Remove the tombstoned rows from the index and renumber ``row_doc`` / ``doc_row`` through the old -> new map it
+        returns, all under the state's lock: a reader that maps ids under the lock sees the old layout or the new one
+        (``indexer.HipIndexer._hits`` compares the index's ``layout_epoch``).  The delta log speaks old ordinals:
+        ``save_delta`` answers False ("take a snapshot") until the next ``save``.  Returns (rows before, rows after)."""
+        with self.lock:
+            new_row = np.asarray(self.index.compact(), dtype=np.int64)
+            before, after = int(new_row.shape[0]), int(self.index.rows)
+            if after == before:             # no tombstone: nothing moved
+                return before, after
+            row_doc: List[Optional[dict]] = [None] * after
+            for old, new in enumerate(new_row.tolist()):
+                if new >= 0 and old < len(self.row_doc):
+                    row_doc[new] = self.row_doc[old]
+            self.row_doc = row_doc
+            self.doc_row = {doc_id: int(new_row[old]) for doc_id, old in self.doc_row.items() if new_row[old] >= 0}
+            self._delta_broken = True
+            self._dead_since = []
+            return before, after
 
     def tag_of(self, doc: dict) -> int:
         return compose_tag(self.patients.encode(doc.get("patientId")), self.doc_types.encode(doc.get("doc_type")))
@@ -150,6 +172,7 @@ class IndexState:
             self.generation = gen
             # the snapshot covers everything: the delta log of the previous generation goes with it
             self._ckpt_rows, self._dead_since, self._structured_dirty, self._delta_seq = int(self.index.rows), [], set(), 0
+            self._delta_broken = False
             self._remove_deltas(prefix, keep_generation=None)
             if prev and prev != vec_path and os.path.exists(prev):
                 # a sharded index's vector "file" is a manifest naming one shard file per rank
@@ -170,6 +193,8 @@ class IndexState:
         with self.lock:
             get_rows = getattr(self.index, "get_rows", None)
             if get_rows is None or self.generation == 0 or self._manifest_generation_only(prefix) != self.generation:
+                return False
+            if self._delta_broken:          # a compaction since the snapshot: _ckpt_rows / the log's "dead" are old ordinals
                 return False
             rows_now = int(self.index.rows)
             n_new = rows_now - self._ckpt_rows

@@ -222,6 +222,31 @@ class FlatIndex:
     def delete(self, row: int) -> None:
         N.check("rass_index_delete", self._L.rass_index_delete(self._h, int(row)))
 
+    def compact(self) -> np.ndarray:
+        """Remove every tombstoned row on the GPU (``rass_index_compact``): the live rows keep their order and their stored
+        bits and take the ordinals 0 .. count-1, and the HBM of the dead ones is returned.  Returns the old -> new ordinal
+        map (int64, -1 for a removed row).  Out of place: needs room for the compacted index next to the old one.  Ordinals
+        handed out earlier are only valid for the ``layout_epoch`` they were read under."""
+        while True:
+            new_row = np.empty(self.rows, dtype=np.int64)
+            before, after = ctypes.c_int64(-1), ctypes.c_int64(-1)
+            rc = self._L.rass_index_compact(self._h, _np_ptr(new_row), new_row.shape[0], ctypes.byref(before), ctypes.byref(after))
+            if rc < 0 and before.value > new_row.shape[0]:
+                continue            # rows were appended since the map was sized
+            N.check("rass_index_compact", rc)
+            return new_row[:before.value]
+
+    @property
+    def layout_epoch(self) -> int:
+        """Compactions that moved rows so far: a row ordinal is only meaningful together with this value."""
+        return int(self._L.rass_index_layout_epoch(self._h))
+
+    @property
+    def epoch(self) -> Tuple[int, int, int]:
+        """(rows, tombstones, layout_epoch): changes whenever a stored answer could (``prefetch.index_epoch``)."""
+        rows = self.rows
+        return (rows, rows - self.count, self.layout_epoch)
+
     def get_row(self, row: int) -> np.ndarray:
         out = np.empty(self.dim, dtype=np.float32)
         N.check("rass_index_get_row", self._L.rass_index_get_row(self._h, int(row), _np_ptr(out)))

@@ -75,6 +75,14 @@ def _term_from_filter(filter_clause: Any, field: str) -> Optional[Any]:
     return None
 
 
+LAYOUT_ATTEMPTS = 8   # searches tried before giving up on an index that is compacted during every one of them
+
+
+def _layout_epoch(index: Any) -> int:
+    """Compactions the index has been through (``FlatIndex.layout_epoch``; 0 for an index that cannot compact)."""
+    return int(getattr(index, "layout_epoch", 0))
+
+
 def _empty(query_emb) -> bool:
     return query_emb is None or np.size(query_emb) == 0
 
@@ -195,18 +203,23 @@ class HipIndexer:
                 return []
             q, k_eff, (fval, fmask) = prep
             eng = getattr(st.index, "engine", None)
-            if eng is not None and hasattr(eng, "search_multi") and k_eff <= 32:
-                # one batcher per ENGINE: concurrent users' per-user indices share scan launches
-                if getattr(eng, "_cross_batcher", None) is None:
-                    from .batcher import CrossIndexBatcher
-                    eng._cross_batcher = CrossIndexBatcher(eng)
-                scores, ids = await eng._cross_batcher.search(st.index, q[0], k_eff, fval, fmask)
-                return self._hits(st, scores, ids, 1.0, None)
-            if st.batcher is None:
-                from .batcher import QueryBatcher
-                st.batcher = QueryBatcher(st.index)
-            scores, ids = await st.batcher.search(q[0], k_eff, fval, fmask)
-            return self._hits(st, scores, ids, 1.0, None)
+            for _ in range(LAYOUT_ATTEMPTS):    # the batchers hand back row ids: paired with the layout epoch as in _knn
+                layout = _layout_epoch(st.index)
+                if eng is not None and hasattr(eng, "search_multi") and k_eff <= 32:
+                    # one batcher per ENGINE: concurrent users' per-user indices share scan launches
+                    if getattr(eng, "_cross_batcher", None) is None:
+                        from .batcher import CrossIndexBatcher
+                        eng._cross_batcher = CrossIndexBatcher(eng)
+                    scores, ids = await eng._cross_batcher.search(st.index, q[0], k_eff, fval, fmask)
+                else:
+                    if st.batcher is None:
+                        from .batcher import QueryBatcher
+                        st.batcher = QueryBatcher(st.index)
+                    scores, ids = await st.batcher.search(q[0], k_eff, fval, fmask)
+                hits = self._hits(st, scores, ids, 1.0, None, layout)
+                if hits is not None:
+                    return hits
+            raise RuntimeError(f"{self.index_name}: the index was compacted during every one of {LAYOUT_ATTEMPTS} searches")
         except Exception as e:
             logger.error(f"Semantic search error: {e}")
             return []
@@ -240,20 +253,35 @@ class HipIndexer:
         if prep is None:
             return []
         q, k_eff, (fval, fmask) = prep
-        parked = prefetch.take(st, q, k_eff, fval, fmask)
-        if parked is not None:      # this request's scan was shared with the other requests in flight
-            return self._hits(st, parked[0], parked[1], boost, score_mode)
-        if fmask:
-            scores, ids = st.index.search(q, k_eff, q_filter=np.array([fval], dtype=np.int32),
-                                          q_filter_mask=np.array([fmask], dtype=np.int32))
-        else:
-            scores, ids = st.index.search(q, k_eff)
-        return self._hits(st, scores[0], ids[0], boost, score_mode)
+        # Row ids are ordinals of ONE layout of the index (a compaction renumbers them, docstore.IndexState.compact): the
+        # layout epoch is read before the search and compared under st.lock before the ids are mapped through row_doc;
+        # when a compaction landed in between, the search runs again (a compaction is rare and far slower than a search).
+        for _ in range(LAYOUT_ATTEMPTS):
+            layout = _layout_epoch(st.index)
+            parked = prefetch.take(st, q, k_eff, fval, fmask)
+            if parked is not None:      # this request's scan was shared with the other requests in flight
+                scores, ids = parked
+            elif fmask:
+                scores, ids = st.index.search(q, k_eff, q_filter=np.array([fval], dtype=np.int32),
+                                              q_filter_mask=np.array([fmask], dtype=np.int32))
+                scores, ids = scores[0], ids[0]
+            else:
+                scores, ids = st.index.search(q, k_eff)
+                scores, ids = scores[0], ids[0]
+            hits = self._hits(st, scores, ids, boost, score_mode, layout)
+            if hits is not None:
+                return hits
+        raise RuntimeError(f"{self.index_name}: the index was compacted during every one of {LAYOUT_ATTEMPTS} searches")
 
     @staticmethod
-    def _hits(st: IndexState, scores, ids, boost, score_mode) -> List[Tuple[Dict, float]]:
+    def _hits(st: IndexState, scores, ids, boost, score_mode, layout: Optional[int] = None
+              ) -> Optional[List[Tuple[Dict, float]]]:
+        """ids -> docs under the state's lock.  ``layout``: the index's layout epoch read BEFORE the search; None is
+        returned (search again) when the index has been compacted since — the ids would name other rows now."""
         out: List[Tuple[Dict, float]] = []
         with st.lock:
+            if layout is not None and _layout_epoch(st.index) != layout:
+                return None
             for cos, row in zip(scores, ids):
                 if row < 0:
                     break
@@ -374,7 +402,26 @@ def add_documents(index_name: str, docs: List[Dict], embeddings: Optional[np.nda
                 st.doc_row[d.get("doc_id")] = r
             else:
                 st.index.delete(r)  # superseded inside the same batch
+        _maybe_compact(st)
         return rows
+
+
+def _maybe_compact(st: IndexState) -> None:
+    """The compaction policy (``RASS_COMPACT_FRACTION`` / ``RASS_COMPACT_MIN_ROWS``, off by default): once the tombstones
+    of an index exceed the fraction of its rows, they are squeezed out on the GPU.  An index that cannot compact (a
+    sharded front) is skipped.  The caller holds ``st.lock``.  (The row ids ``add_documents`` returns are those of the
+    append, as before: after a compaction they have been renumbered like every other row.)"""
+    fraction = config.RASS_COMPACT_FRACTION
+    if fraction <= 0 or not callable(getattr(st.index, "compact", None)):
+        return
+    rows = int(st.index.rows)
+    dead = rows - int(st.index.count)
+    if rows < config.RASS_COMPACT_MIN_ROWS or dead <= fraction * rows:
+        return
+    try:
+        st.compact()
+    except NotImplementedError:     # an index whose compaction is out of scope (serving.ShardedIndex)
+        pass
 
 
 async def _call_embed(embed_fn, texts: List[str]) -> np.ndarray:

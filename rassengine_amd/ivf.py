@@ -542,9 +542,9 @@ class IvfBackedIndex(FlatIndex):
         return ivf.covered_rows if ivf is not None else 0
 
     @property
-    def epoch(self) -> Tuple[int, int, int]:
+    def epoch(self) -> Tuple[int, int, int, int]:
         rows = self.rows
-        return rows, rows - self.count, self.builds
+        return rows, rows - self.count, self.builds, self.layout_epoch
 
     @property
     def multi_tiles(self) -> int:
@@ -603,6 +603,15 @@ class IvfBackedIndex(FlatIndex):
             super().delete(row)
             if self.ivf is not None:
                 self.ivf.delete(row)
+
+    def compact(self) -> np.ndarray:
+        """``FlatIndex.compact`` for an index with an IVF: the IVF's ids are ordinals of the old layout, so it is dropped
+        first and rebuilt over the compacted rows when the policy says so (until then searches are the exact flat scan)."""
+        with self._ivf_lock:
+            self.drop_ivf()
+            new_row = super().compact()
+            self.maybe_rebuild()
+        return new_row
 
     # ---- persistence: `<path>` = the flat index (authoritative), `<path minus .tmp>.ivf` = the IVF's device state
     @staticmethod

@@ -99,13 +99,15 @@ def remember(emb: np.ndarray) -> None:
         _slots[t] = _Slot(np.array(emb, dtype=np.float32, copy=True).reshape(-1))
 
 
-def index_epoch(index: Any) -> Tuple[int, int]:
-    """(rows ever appended, rows tombstoned) — both only grow, so equal epochs mean no write in between."""
+def index_epoch(index: Any) -> Tuple[int, ...]:
+    """(rows, rows tombstoned, layout epoch).  Between two compactions the first two only grow; a compaction brings them
+    back (append 10, overwrite 10, compact: the same two numbers with other rows behind the ordinals) and bumps the third.
+    Equal epochs mean no write and no compaction in between."""
     ep = getattr(index, "epoch", None)
     if ep is not None:
         return ep
     rows = int(index.rows)
-    return rows, rows - int(index.count)
+    return rows, rows - int(index.count), int(getattr(index, "layout_epoch", 0))
 
 
 def _batcher_for(st) -> Any:

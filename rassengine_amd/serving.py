@@ -864,6 +864,12 @@ class ShardedIndex:
                 f.flush()
                 os.fsync(f.fileno())
 
+    def compact(self):
+        """Not offered: the extent table maps global ids to (rank, ordinal), so a compaction would have to renumber it on
+        every rank together.  (``rass_index_compact`` itself carries caller-assigned ids with their rows.)"""
+        raise NotImplementedError("compaction of a sharded index is out of scope: its extent tables map global ids to "
+                                  "(rank, ordinal) and would need a collective remap")
+
     def saved_files(self, manifest_path: str) -> List[str]:
         """The shard files a manifest of this index names (``IndexState.save`` removes the previous generation's)."""
         try:
