@@ -510,6 +510,50 @@ int rass_ivf_search_delta_device(rass_ivf_t* ivf, rass_index_t* src,
                                  const int32_t* d_q_filter, const int32_t* d_q_filter_mask,
                                  float* d_out_scores, int64_t* d_out_ids);
 
+/* ---- IVF builds whose list plan runs on the GPU, and an IVF extended without retraining.
+ * The list plan is the step between "every row has a list" and "the slab is filled": list lengths, tile-aligned
+ * list offsets, the source row at every slab position and its inverse.  rass_ivf_build_prefix computes it in host
+ * loops over all rows; here it is a stable counting sort on the device (csrc/ivf_build.hip), DEFINED to give what
+ * those loops give.  No O(rows) host work, no id upload: per build the host reads 24 bytes (to size the slab) and
+ * the row -> slab position map once (rass_ivf_delete reads it on the host).
+ *
+ * rass_ivf_plan_lists: the plan on caller-owned device arrays; stateless, ordered on `stream`.
+ *   in : d_assign[n_rows] (the list of source row r), d_tags[n_rows] (RASS_ROW_TAG_DELETED = in no list), nlist in
+ *        [1, 32768], tile_rows 32 or 64.
+ *   out: d_list_len[nlist] live rows per list; d_list_tile0[nlist] the exclusive prefix of ceil(len / tile_rows);
+ *        *d_total_tiles their sum (0 when no row is live); d_slab_ids[slab_rows], slab_rows = max(total_tiles, 1) *
+ *        tile_rows: the source row at each slab position, ascending inside a list, -1 on padding; d_pos_of[n_rows]
+ *        the slab position of each source row, -1 for a row in no list; *d_status: 0, or a sum of 1 (a live row's
+ *        list id is outside [0, nlist): such rows are left out), 2 (total_tiles * tile_rows exceeds 0x7fffffc0:
+ *        nothing is placed) and 4 (slab_rows exceeds slab_ids_capacity: nothing is written at or past it).
+ *   d_workspace: rass_ivf_plan_workspace_bytes(n_rows, nlist) bytes (0 for arguments out of range).
+ *   The output is a function of the input: atomics produce counts only, and no workgroup waits on another.
+ * rass_ivf_build_device: rass_ivf_build_prefix with the assignment in device memory (what rass_kmeans_assign
+ *   wrote); `centroids` stays a host array.  The same IVF, array by array (rass_ivf_save: the same bytes).
+ * rass_ivf_absorb: a NEW IVF with the centroids, nlist and slab dtype of `ivf`, covering source rows [0, n_rows)
+ *   (-1 = all): rows `ivf` covers keep their list, the rows after them go to their nearest centroid (as a build:
+ *   ties to the lowest list), rows tombstoned since the build drop out.  The result is the IVF rass_ivf_build_prefix
+ *   gives from those centroids and that assignment.  `ivf` is untouched and stays searchable; the caller destroys
+ *   it.  Out of place, like rass_index_compact: the new IVF needs HBM next to the old one (RASS_ERR_OOM).
+ *   RASS_ERR_INVALID: n_rows below rass_ivf_covered_rows(ivf), above the source's rows, or neither a multiple of
+ *   32 nor all rows; a source compacted since the build.  RASS_ERR_UNSUPPORTED: a non-fp32 or wide-row source.
+ *   Every refusal leaves *out = NULL and both inputs as they were.
+ * rass_ivf_lists_device: the lists of an IVF (built, absorbed or loaded) as arrays: d_assign[covered] (may be
+ *   NULL) the list of every covered source row in the slab, -1 for the others; d_list_len[nlist] (may be NULL).
+ *   Returns with the copies complete. */
+size_t rass_ivf_plan_workspace_bytes(int64_t n_rows, int nlist);
+int rass_ivf_plan_lists(const int32_t* d_assign, const int32_t* d_tags, int64_t n_rows, int nlist,
+                        int tile_rows, int32_t* d_list_len, int32_t* d_list_tile0,
+                        int64_t* d_total_tiles, int64_t* d_slab_ids, int64_t slab_ids_capacity,
+                        int32_t* d_pos_of, int32_t* d_status, void* d_workspace,
+                        size_t workspace_bytes, void* stream);
+int rass_ivf_build_device(rass_index_t* src, const float* centroids, int nlist,
+                          const int32_t* d_assign, rass_dtype slab_dtype, int64_t n_rows,
+                          rass_ivf_t** out);
+int rass_ivf_absorb(rass_ivf_t* ivf, rass_index_t* src, int64_t n_rows, rass_ivf_t** out);
+int rass_ivf_lists_device(rass_ivf_t* ivf, int32_t* d_assign, int64_t assign_capacity,
+                          int32_t* d_list_len);
+
 /* ---------------------------------------------------------------- encoder
  * Replaces ollama_embed_text / embed_texts_in_batches / embed_query's HTTP hop
  * to Ollama (app/main.py:225-274): a BERT-class post-LN sentence encoder

@@ -52,6 +52,14 @@ try:
     RASS_IVF_REBUILD_FRACTION = float(os.getenv("RASS_IVF_REBUILD_FRACTION", "0.25"))
 except ValueError:
     RASS_IVF_REBUILD_FRACTION = 0.25
+# RASS_IVF_ABSORB_FRACTION: 0 = never (the default: the delta only leaves through a rebuild).  > 0: once the delta exceeds
+# that fraction of the covered rows the IVF is extended over it on the GPU with the centroids it has (ivf.IvfBackedIndex.
+# absorb_delta: no training, no host pass over the rows), and RASS_IVF_REBUILD_FRACTION then counts growth since the
+# centroids were last TRAINED.  Out of place: needs HBM for the new IVF next to the old one.
+try:
+    RASS_IVF_ABSORB_FRACTION = float(os.getenv("RASS_IVF_ABSORB_FRACTION", "0"))
+except ValueError:
+    RASS_IVF_ABSORB_FRACTION = 0.0
 # Compaction of tombstoned rows (docstore.IndexState.compact, rass_index_compact): an `_id` overwrite appends the new row and
 # tombstones the old one, whose 4 KiB every later scan still streams.  RASS_COMPACT_FRACTION: 0 = never (the default);
 # > 0: add_documents compacts the index once its tombstones exceed that fraction of its rows and it holds at least

@@ -814,4 +814,248 @@ int rass_ivf_search(rass_ivf_t* v, const float* queries, int nq, int k, int npro
     return ivf_search_host(v, nullptr, {queries, nq, k, q_filter, nullptr, out_scores, out_ids}, nprobe, scanned_rows);
 }
 
+// ---- builds whose list plan runs on the GPU (ivf_build.hip): from a device-resident assignment, and an existing IVF
+// extended over the rows its source took since, without retraining.  Both produce the IVF rass_ivf_build_prefix would produce
+// from the same centroids and the same assignment, array by array (tests/test_gpu_ivf_absorb.py compares the saved files).
+// Host traffic: total_tiles / live rows / status (24 bytes, sizes the slab), pos_of once (rass_ivf_delete reads it on the
+// host), and the centroids of rass_ivf_build_device.
+
+// The temporaries of a device-planned build; what is still set when it goes out of scope is released.
+struct IvfPlanBlocks {
+    int32_t *len = nullptr, *tile0 = nullptr, *pos = nullptr, *assign = nullptr;
+    int64_t* head = nullptr;   // [0] total_tiles, [1] live rows, [2] status (its low int32)
+    void* ws = nullptr;
+    ~IvfPlanBlocks() {
+        for (void* p : {(void*)len, (void*)tile0, (void*)pos, (void*)assign, (void*)head, ws})
+            if (p) (void)hipFree(p);
+    }
+};
+
+static int ivf_hip_fail(const char* what, hipError_t e) {
+    return fail(e == hipErrorOutOfMemory ? RASS_ERR_OOM : RASS_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
+}
+
+// The caller holds src->mu, has set the device and checked src / nlist / slab_dtype.  d_assign[n] on the device; exactly one
+// of `centroids` (host, row-major: normalised and packed as the host build does) and `d_centroids_tile16` (a centroid slab
+// of the same nlist and stride: copied) is given.
+static int ivf_build_planned(rass_index* src, int nlist, const int32_t* d_assign, rass_dtype slab_dtype, int64_t n,
+                             const float* centroids, const float* d_centroids_tile16, IvfPlanBlocks& t, rass_ivf_t** out) {
+    rass_engine* eng = src->eng;
+    hipStream_t st = eng->stream;
+    const int tile_rows = slab_dtype == RASS_F32 ? 32 : 64;
+    const size_t ws_bytes = rass::ivf_plan_workspace_bytes(n, nlist);
+    hipError_t e = hipMalloc((void**)&t.len, (size_t)nlist * 4);
+    if (e == hipSuccess) e = hipMalloc((void**)&t.tile0, (size_t)nlist * 4);
+    if (e == hipSuccess) e = hipMalloc((void**)&t.pos, (size_t)std::max<int64_t>(n, 1) * 4);
+    if (e == hipSuccess) e = hipMalloc((void**)&t.head, 24);
+    if (e == hipSuccess) e = hipMalloc(&t.ws, ws_bytes);
+    if (e != hipSuccess) return ivf_hip_fail("ivf build: allocating the list plan failed", e);
+    int32_t* d_status = reinterpret_cast<int32_t*>(t.head + 2);
+    HIP_TRY(rass::launch_ivf_plan_count(d_assign, src->d_tags, n, nlist, tile_rows, t.len, t.tile0, t.head, t.head + 1, d_status,
+                                        t.ws, st));
+    int64_t head[3] = {0, 0, 0};
+    HIP_TRY(hipMemcpyAsync(head, t.head, 24, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    const int64_t tiles = head[0];
+    const int32_t status = (int32_t)(head[2] & 0xffffffffLL);
+    if (status & 1) return fail(RASS_ERR_INVALID, "assign[] holds a list id outside [0, nlist)");
+    if ((status & 2) || tiles * tile_rows > 0x7fffffc0LL) return fail(RASS_ERR_UNSUPPORTED, "slab too large for one IVF shard");
+    const int64_t slab_rows = std::max<int64_t>(tiles, 1) * tile_rows;
+    rass_ivf* v = new (std::nothrow) rass_ivf();
+    if (!v) return fail(RASS_ERR_OOM, "host allocation failed");
+    v->eng = eng;
+    v->dtype = slab_dtype;
+    v->tile_rows = tile_rows;
+    v->dim = src->dim;
+    v->stride = src->stride;
+    v->nlist = nlist;
+    v->rows = head[1];
+    v->src_rows = n;
+    v->src_epoch = src->layout_epoch.load();
+    v->slab_rows = slab_rows;
+    v->total_tiles = std::max<int64_t>(tiles, 1);
+    v->any_tags = src->has_tags;
+    if (slab_dtype == RASS_I8) v->stride_i8 = (v->stride + 511) / 512 * 512;
+    const int64_t cent_rows = ((int64_t)nlist + 15) / 16 * 16;
+#define IVF_TRY(expr)                                                                        \
+    do {                                                                                     \
+        hipError_t _e = (expr);                                                              \
+        if (_e != hipSuccess) {                                                              \
+            ivf_free(v);                                                                     \
+            return ivf_hip_fail("ivf build: " #expr, _e);                                    \
+        }                                                                                    \
+    } while (0)
+    try {
+        v->pos_of.resize((size_t)n);
+    } catch (const std::bad_alloc&) {
+        ivf_free(v);
+        return fail(RASS_ERR_OOM, "host allocation failed");
+    }
+    const char* what = "";
+    const hipError_t ae = ivf_alloc(v, &what);
+    if (ae != hipSuccess) {
+        ivf_free(v);
+        return ivf_hip_fail((std::string("ivf build: hipMalloc of ") + what).c_str(), ae);
+    }
+    if (slab_dtype == RASS_I8) IVF_TRY(hipMemsetAsync(v->d_slab_i8, 0, (size_t)slab_rows * v->stride_i8, st));
+    IVF_TRY(hipMemcpyAsync(v->d_list_tile0, t.tile0, (size_t)nlist * 4, hipMemcpyDeviceToDevice, st));
+    IVF_TRY(hipMemcpyAsync(v->d_list_len, t.len, (size_t)nlist * 4, hipMemcpyDeviceToDevice, st));
+    IVF_TRY(rass::launch_ivf_plan_place(d_assign, src->d_tags, n, nlist, tile_rows, t.tile0, t.head, v->d_ids, slab_rows, t.pos,
+                                        d_status, t.ws, st));
+    if (slab_dtype == RASS_BF16)
+        IVF_TRY(rass::launch_permute_rows_tile16_bf16(src->d_rows, v->d_slab_b16, v->stride, v->d_ids, slab_rows, st));
+    else
+        IVF_TRY(rass::launch_permute_rows_tile16(src->d_rows, v->d_slab, v->stride, v->d_ids, slab_rows, st));
+    if (slab_dtype == RASS_I8)
+        IVF_TRY(rass::launch_quantize_tile16_i8(v->d_slab, v->d_slab_i8, v->d_slab_scale, v->stride, v->stride_i8, 0, slab_rows / 16, st));
+    // tags: gathered through the slab's ids, padding rows keep 0
+    IVF_TRY(hipMemsetAsync(v->d_tags, 0, (size_t)slab_rows * 4, st));
+    IVF_TRY(rass::launch_gather_i32(src->d_tags, v->d_tags, v->d_ids, slab_rows, n, st));
+    if (n > 0) IVF_TRY(hipMemcpyAsync(v->pos_of.data(), t.pos, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+    if (d_centroids_tile16) {
+        IVF_TRY(hipMemcpyAsync(v->d_centroids, d_centroids_tile16, (size_t)cent_rows * v->stride * 4, hipMemcpyDeviceToDevice, st));
+    } else {   // normalise + pack through the engine's staging buffer
+        IVF_TRY(hipMemsetAsync(v->d_centroids, 0, (size_t)cent_rows * v->stride * 4, st));
+        std::lock_guard<std::mutex> elk(eng->mu);
+        for (int64_t done = 0; done < nlist; done += kStageRows) {
+            const int64_t m = std::min<int64_t>(kStageRows, nlist - done);
+            IVF_TRY(hipMemcpyAsync(eng->d_stage, centroids + done * v->dim, (size_t)m * v->dim * 4, hipMemcpyHostToDevice, st));
+            IVF_TRY(rass::launch_pack_rows_tile16(eng->d_stage, v->dim, v->d_centroids, v->stride, done, m, v->dim, 1, st));
+            IVF_TRY(hipStreamSynchronize(st));
+        }
+    }
+    IVF_TRY(hipStreamSynchronize(st));
+    // the count phase sized the slab: a place phase that disagrees with it must not be served
+    int32_t status_after = 0;
+    IVF_TRY(hipMemcpy(&status_after, d_status, 4, hipMemcpyDeviceToHost));
+#undef IVF_TRY
+    if (status_after != 0) {
+        ivf_free(v);
+        return fail(RASS_ERR_HIP, "ivf build: the list plan's two phases disagree (the assignment or the tags changed under it)");
+    }
+    *out = v;
+    return RASS_OK;
+}
+
+static int ivf_source_check(const rass_index* src, int nlist, rass_dtype slab_dtype) {
+    if (nlist < 1 || nlist > 32768) return fail(RASS_ERR_INVALID, "nlist must be in [1, 32768]");
+    if (src->dtype != RASS_F32) return fail(RASS_ERR_UNSUPPORTED, "the IVF build needs an fp32 source index");
+    if (src->stride > kNarrowStride) return fail(RASS_ERR_UNSUPPORTED, "IVF needs dim <= 1024 (wide rows: flat scan only)");
+    if (slab_dtype != RASS_F32 && slab_dtype != RASS_BF16 && slab_dtype != RASS_I8) return fail(RASS_ERR_INVALID, "unknown slab dtype");
+    if (slab_dtype == RASS_BF16 && src->stride % 256 != 0)
+        return fail(RASS_ERR_UNSUPPORTED, "a bf16 slab needs dim padded to a multiple of 256 (the bf16 scan's K split)");
+    return RASS_OK;
+}
+
+int rass_ivf_build_device(rass_index_t* src, const float* centroids, int nlist, const int32_t* d_assign, rass_dtype slab_dtype,
+                          int64_t n_rows, rass_ivf_t** out) {
+    if (!src || !centroids || !d_assign || !out) return fail(RASS_ERR_INVALID, "NULL argument");
+    *out = nullptr;
+    int rc = ivf_source_check(src, nlist, slab_dtype);
+    if (rc != RASS_OK) return rc;
+    std::lock_guard<std::mutex> lk(src->mu);
+    rc = set_device(src->eng);
+    if (rc != RASS_OK) return rc;
+    if (n_rows > src->rows) return fail(RASS_ERR_INVALID, "n_rows exceeds the rows of the source index");
+    const int64_t n = n_rows < 0 ? src->rows.load() : n_rows;
+    IvfPlanBlocks t;
+    return ivf_build_planned(src, nlist, d_assign, slab_dtype, n, centroids, nullptr, t, out);
+}
+
+int rass_ivf_absorb(rass_ivf_t* ivf, rass_index_t* src, int64_t n_rows, rass_ivf_t** out) {
+    if (!ivf || !src || !out) return fail(RASS_ERR_INVALID, "NULL argument");
+    *out = nullptr;
+    rass_engine* eng = src->eng;
+    const rass_dtype slab_dtype = (rass_dtype)ivf->dtype;
+    int rc = ivf_source_check(src, ivf->nlist, slab_dtype);
+    if (rc != RASS_OK) return rc;
+    if (ivf->eng != eng) return fail(RASS_ERR_INVALID, "the source index must live on the IVF's engine");
+    if (src->stride != ivf->stride || src->dim != ivf->dim)
+        return fail(RASS_ERR_INVALID, "the source index is not the one the IVF was built from (dim)");
+    std::lock_guard<std::mutex> lk(src->mu);
+    rc = set_device(eng);
+    if (rc != RASS_OK) return rc;
+    // the IVF's ids are ordinals of the source as it was laid out at build time (a loaded IVF trusts its source, as the search does)
+    if (ivf->src_epoch >= 0 && ivf->src_epoch != src->layout_epoch.load(std::memory_order_acquire))
+        return fail(RASS_ERR_INVALID, "the source index was compacted after this IVF was built (its ids are stale ordinals): rebuild the IVF");
+    const int64_t rows = src->rows.load(), covered = ivf->src_rows;
+    if (n_rows > rows) return fail(RASS_ERR_INVALID, "n_rows exceeds the rows of the source index");
+    const int64_t n = n_rows < 0 ? rows : n_rows;
+    if (n < covered) return fail(RASS_ERR_INVALID, "n_rows is below the rows the IVF already covers (rass_ivf_covered_rows)");
+    if (n % 32 != 0 && n != rows)
+        return fail(RASS_ERR_INVALID, "n_rows must be a multiple of 32 or every row of the source (the delta must start on a scan tile)");
+    hipStream_t st = eng->stream;
+    IvfPlanBlocks t;
+    const int64_t n_padded = std::max<int64_t>((n + 31) / 32 * 32, 32);
+    hipError_t e = hipMalloc((void**)&t.assign, (size_t)n_padded * 4);
+    if (e != hipSuccess) return ivf_hip_fail("ivf absorb: allocating the assignment failed", e);
+    // rows the old slab does not hold are tombstones of the source: their entries are never read as a list
+    HIP_TRY(hipMemsetAsync(t.assign, 0, (size_t)n_padded * 4, st));
+    // new rows: their nearest centroid, whole 32-row blocks from the one the covered rows end in (ties -> lowest list, as a build) ...
+    const int64_t first_block = covered / 32, n_blocks = (n + 31) / 32 - first_block;
+    if (n > covered) {
+        rass::AssignArgs a;
+        a.rows = src->d_rows;
+        a.centroids = ivf->d_centroids;
+        a.assign = t.assign + first_block * 32;
+        a.best = nullptr;
+        a.row_stride = src->stride;
+        a.slab_rows = src->capacity;
+        a.first_block = first_block;
+        a.block_step = 1;
+        a.n_blocks = (int)n_blocks;
+        a.nlist = ivf->nlist;
+        HIP_TRY(rass::launch_kmeans_assign_f32(a, eng->n_cus, st));
+    }
+    // ... covered rows keep their list (written second: the covered rows of a shared block win)
+    HIP_TRY(rass::launch_ivf_lists_to_assign(ivf->d_list_tile0, ivf->d_list_len, ivf->nlist, ivf->tile_rows, ivf->d_ids,
+                                             ivf->slab_rows, t.assign, covered, st));
+    return ivf_build_planned(src, ivf->nlist, t.assign, slab_dtype, n, nullptr, ivf->d_centroids, t, out);
+}
+
+int rass_ivf_lists_device(rass_ivf_t* ivf, int32_t* d_assign, int64_t assign_capacity, int32_t* d_list_len) {
+    if (!ivf) return fail(RASS_ERR_INVALID, "NULL argument");
+    if (d_assign && assign_capacity < ivf->src_rows)
+        return fail(RASS_ERR_INVALID, "assign_capacity is smaller than the rows the IVF covers (rass_ivf_covered_rows)");
+    rass_engine* eng = ivf->eng;
+    int rc = set_device(eng);
+    if (rc != RASS_OK) return rc;
+    std::lock_guard<std::mutex> lk(eng->mu);
+    hipStream_t st = eng->stream;
+    if (d_assign && ivf->src_rows > 0) {
+        HIP_TRY(hipMemsetAsync(d_assign, 0xff, (size_t)ivf->src_rows * 4, st));
+        HIP_TRY(rass::launch_ivf_lists_to_assign(ivf->d_list_tile0, ivf->d_list_len, ivf->nlist, ivf->tile_rows, ivf->d_ids,
+                                                 ivf->slab_rows, d_assign, ivf->src_rows, st));
+    }
+    if (d_list_len) HIP_TRY(hipMemcpyAsync(d_list_len, ivf->d_list_len, (size_t)ivf->nlist * 4, hipMemcpyDeviceToDevice, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return RASS_OK;
+}
+
+size_t rass_ivf_plan_workspace_bytes(int64_t n_rows, int nlist) {
+    return (n_rows < 0 || nlist < 1 || nlist > 32768) ? 0 : rass::ivf_plan_workspace_bytes(n_rows, nlist);
+}
+
+int rass_ivf_plan_lists(const int32_t* d_assign, const int32_t* d_tags, int64_t n_rows, int nlist, int tile_rows,
+                        int32_t* d_list_len, int32_t* d_list_tile0, int64_t* d_total_tiles, int64_t* d_slab_ids,
+                        int64_t slab_ids_capacity, int32_t* d_pos_of, int32_t* d_status, void* d_workspace, size_t workspace_bytes,
+                        void* stream) {
+    if (n_rows < 0 || n_rows > 0x7fffffc0LL) return fail(RASS_ERR_INVALID, "n_rows must be in [0, 0x7fffffc0]");
+    if (nlist < 1 || nlist > 32768) return fail(RASS_ERR_INVALID, "nlist must be in [1, 32768]");
+    if (tile_rows != 32 && tile_rows != 64) return fail(RASS_ERR_INVALID, "tile_rows must be 32 or 64");
+    if (slab_ids_capacity < tile_rows || slab_ids_capacity > 0x7fffffc0LL)
+        return fail(RASS_ERR_INVALID, "slab_ids_capacity must hold at least one tile and at most 0x7fffffc0 rows");
+    if (!d_list_len || !d_list_tile0 || !d_total_tiles || !d_slab_ids || !d_status || !d_workspace)
+        return fail(RASS_ERR_INVALID, "NULL argument");
+    if (n_rows > 0 && (!d_assign || !d_tags || !d_pos_of)) return fail(RASS_ERR_INVALID, "NULL argument");
+    if (workspace_bytes < rass::ivf_plan_workspace_bytes(n_rows, nlist))
+        return fail(RASS_ERR_INVALID, "workspace too small (rass_ivf_plan_workspace_bytes)");
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    HIP_TRY(rass::launch_ivf_plan_count(d_assign, d_tags, n_rows, nlist, tile_rows, d_list_len, d_list_tile0, d_total_tiles, nullptr,
+                                        d_status, d_workspace, st));
+    HIP_TRY(rass::launch_ivf_plan_place(d_assign, d_tags, n_rows, nlist, tile_rows, d_list_tile0, d_total_tiles, d_slab_ids,
+                                        slab_ids_capacity, d_pos_of, d_status, d_workspace, st));
+    return RASS_OK;
+}
+
 }  // extern "C"

@@ -334,6 +334,28 @@ hipError_t launch_compact_rows_tile16b(const void* src, void* dst, int64_t row_s
 hipError_t launch_gather_i32(const int32_t* src, int32_t* dst, const int64_t* src_row, int64_t n, int64_t n_src, hipStream_t stream);
 hipError_t launch_gather_i64(const int64_t* src, int64_t* dst, const int64_t* src_row, int64_t n, int64_t n_src, hipStream_t stream);
 
+// ---- the list plan of an IVF build (ivf_build.hip): a stable counting sort of the source rows by list id, rows tagged
+// RASS_ROW_TAG_DELETED left out; the outputs are those of rass_ivf_build_prefix's host loops.  Two phases so that a builder
+// can size its slab in between; no workgroup waits on another.  workspace: ivf_plan_workspace_bytes(n_rows, nlist), the same
+// block for both phases.
+// count: list_len[nlist], list_tile0[nlist], *total_tiles (0 for no live row), *n_live (nullptr = not wanted: the sum of
+// list_len); *status |= 1 for a live row whose list id is outside [0, nlist), |= 2 when total_tiles * tile_rows exceeds the
+// slab limit 0x7fffffc0.
+size_t ivf_plan_workspace_bytes(int64_t n_rows, int nlist);
+hipError_t launch_ivf_plan_count(const int32_t* assign, const int32_t* tags, int64_t n_rows, int nlist, int tile_rows,
+                                 int32_t* list_len, int32_t* list_tile0, int64_t* total_tiles, int64_t* n_live, int32_t* status,
+                                 void* workspace, hipStream_t stream);
+// place: slab_ids[0 .. max(*total_tiles, 1) * tile_rows) (ascending source row inside a list, -1 on padding) and
+// pos_of[n_rows] (-1 for a row in no list).  Nothing is written at or past slab_ids_capacity: *status |= 4 instead.
+hipError_t launch_ivf_plan_place(const int32_t* assign, const int32_t* tags, int64_t n_rows, int nlist, int tile_rows,
+                                 const int32_t* list_tile0, const int64_t* total_tiles, int64_t* slab_ids,
+                                 int64_t slab_ids_capacity, int32_t* pos_of, int32_t* status, void* workspace,
+                                 hipStream_t stream);
+// assign[slab_ids[p]] = l for every occupied position p of list l (ids outside [0, n_assign) are skipped)
+hipError_t launch_ivf_lists_to_assign(const int32_t* list_tile0, const int32_t* list_len, int nlist, int tile_rows,
+                                      const int64_t* slab_ids, int64_t slab_rows, int32_t* assign, int64_t n_assign,
+                                      hipStream_t stream);
+
 hipError_t launch_fill_i32(int32_t* dst, int64_t n, int32_t value, hipStream_t stream);
 // dst[i] = base + i
 hipError_t launch_iota_i64(int64_t* dst, int64_t n, int64_t base, hipStream_t stream);

@@ -318,6 +318,77 @@ class IvfIndex:
         self.engine = engine
         self.dim = dim
         self._L = N.lib()
+        self._assign = None          # host int32 [covered], or a callable that fetches it (device builds: on first use)
+
+    @property
+    def assign(self) -> Optional[np.ndarray]:
+        """List id of every covered source row (host int32).  After ``build``: the assignment the IVF was built from.
+        After ``build_device`` the same, fetched from the device on first use; after ``absorb``: read back from the lists
+        (``rass_ivf_lists_device``), -1 for a covered row that is not in the slab (tombstoned before the build)."""
+        if callable(self._assign):
+            self._assign = self._assign()
+        return self._assign
+
+    @assign.setter
+    def assign(self, value) -> None:
+        self._assign = value
+
+    def lists_device(self, want_assign: bool = True) -> Tuple[Optional[torch.Tensor], torch.Tensor]:
+        """(assign int32 [covered] or None, list lengths int32 [nlist]) as device tensors, read from the IVF's own arrays."""
+        dev = torch.device("cuda", self.engine.device)
+        covered = self.covered_rows
+        a = torch.empty((max(covered, 1),), dtype=torch.int32, device=dev) if want_assign else None
+        n = torch.empty((self.nlist,), dtype=torch.int32, device=dev)
+        torch.cuda.current_stream(dev).synchronize()    # the engine's stream writes them: the allocator's stream must be idle
+        N.check("rass_ivf_lists_device",
+                self._L.rass_ivf_lists_device(self._h, ctypes.c_void_p(a.data_ptr()) if a is not None else None,
+                                              int(a.numel()) if a is not None else 0, ctypes.c_void_p(n.data_ptr())))
+        return (a[:covered] if a is not None else None), n
+
+    @classmethod
+    def build_device(cls, index: FlatIndex, centroids: torch.Tensor, d_assign: Optional[torch.Tensor] = None,
+                     dtype: str = "f32", n_rows: int = -1) -> "IvfIndex":
+        """``build`` with the list plan on the GPU (``rass_ivf_build_device``): the assignment never leaves HBM.  ``d_assign``:
+        device int32, one list id per row (default: ``kmeans_assign`` against ``centroids``).  The same IVF as ``build`` from
+        the same centroids and assignment, array by array."""
+        if dtype not in SLAB_DTYPES:
+            raise ValueError(f"dtype must be one of {sorted(SLAB_DTYPES)}, got {dtype!r}")
+        dev = torch.device("cuda", index.engine.device)
+        need = index.rows if n_rows < 0 else int(n_rows)
+        if d_assign is None:
+            with _engine_on_torch_stream(index):
+                d_assign, _slab = kmeans_assign(index, centroids)
+        else:
+            if d_assign.dtype != torch.int32 or d_assign.dim() != 1 or not d_assign.is_cuda or d_assign.shape[0] < need:
+                raise ValueError(f"d_assign must be a device int32 vector of at least {need} list ids")
+            d_assign = d_assign.contiguous()
+            torch.cuda.current_stream(dev).synchronize()      # the engine's stream reads it
+        nlist = int(centroids.shape[0])
+        c_host = np.ascontiguousarray(centroids.cpu().numpy(), dtype=np.float32)
+        h = ctypes.c_void_p()
+        N.check("rass_ivf_build_device",
+                N.lib().rass_ivf_build_device(index._h, c_host.ctypes.data_as(ctypes.c_void_p), nlist,
+                                              ctypes.c_void_p(d_assign.data_ptr()), SLAB_DTYPES[dtype], int(n_rows),
+                                              ctypes.byref(h)))
+        ivf = cls(h, index.engine, index.dim)
+        covered = ivf.covered_rows
+        ivf.centroids = centroids
+        ivf.list_sizes = torch.bincount(d_assign[:covered].long(), minlength=nlist).cpu().numpy()
+        ivf.assign = lambda: d_assign[:covered].cpu().numpy()
+        return ivf
+
+    def absorb(self, flat: FlatIndex, n_rows: int = -1) -> "IvfIndex":
+        """A NEW IVF with this one's centroids, nlist and slab dtype over ``flat``'s first ``n_rows`` rows (-1 = all;
+        otherwise a multiple of 32): covered rows keep their list, the rows appended since go to their nearest centroid,
+        rows tombstoned since drop out (``rass_ivf_absorb``).  No training, no host pass over the rows.  This IVF is
+        untouched and stays searchable; the caller closes it."""
+        h = ctypes.c_void_p()
+        N.check("rass_ivf_absorb", self._L.rass_ivf_absorb(self._h, flat._h, int(n_rows), ctypes.byref(h)))
+        new = type(self)(h, self.engine, self.dim)
+        new.centroids = getattr(self, "centroids", None)
+        new.list_sizes = new.lists_device(want_assign=False)[1].cpu().numpy().astype(np.int64)
+        new.assign = lambda: new.lists_device()[0].cpu().numpy()
+        return new
 
     @classmethod
     def build(cls, index: FlatIndex, nlist: int = 4096, train_rows: int = 0, iters: int = 20, seed: int = 0,
@@ -494,19 +565,28 @@ class IvfPolicy:
     above it an IVF-``nlist`` is built over the rows it holds; rows appended afterwards form a flat DELTA that every
     search scans exactly next to the probe (``rass_ivf_search_delta``), and once the delta exceeds ``rebuild_fraction``
     of the covered rows the IVF is rebuilt over everything (2.4-3.7 s per 12.5 M rows, inside the ``add`` that crossed
-    the threshold — an ingest-path cost; searches keep being served from the old IVF + delta until the swap)."""
+    the threshold — an ingest-path cost; searches keep being served from the old IVF + delta until the swap).
+
+    ``absorb_fraction`` > 0 (``RASS_IVF_ABSORB_FRACTION``; 0 = never, the default: everything above holds unchanged)
+    separates the two things a rebuild does.  Centroids age with the rows TRAINED on: a retrain is due once the index has
+    grown by more than ``rebuild_fraction`` of ``trained_rows`` (the rows covered when the centroids were last trained; an
+    IVF loaded from disk takes its covered rows).  The delta ages much faster — it is scanned exactly by every search —
+    and is ABSORBED once it exceeds ``absorb_fraction`` of the covered rows: the appended rows get a list of the existing
+    centroids and join the slab (``IvfIndex.absorb``: no training, no host pass over the rows)."""
 
     def __init__(self, nlist: int = 0, nprobe: int = 8, min_rows: int = 262144, rebuild_fraction: float = 0.25,
-                 dtype: str = "f32", train_rows: int = 0, iters: int = 10, seed: int = 0):
+                 dtype: str = "f32", train_rows: int = 0, iters: int = 10, seed: int = 0, absorb_fraction: float = 0.0):
         self.nlist, self.nprobe, self.min_rows = int(nlist), max(1, int(nprobe)), int(min_rows)
         self.rebuild_fraction, self.dtype = float(rebuild_fraction), dtype
         self.train_rows, self.iters, self.seed = int(train_rows), int(iters), int(seed)
+        self.absorb_fraction = max(0.0, float(absorb_fraction))
 
     @classmethod
     def from_config(cls) -> "IvfPolicy":
         from . import config
         return cls(config.RASS_IVF_NLIST, config.RASS_IVF_NPROBE, config.RASS_IVF_MIN_ROWS,
-                   config.RASS_IVF_REBUILD_FRACTION, config.RASS_IVF_DTYPE)
+                   config.RASS_IVF_REBUILD_FRACTION, config.RASS_IVF_DTYPE,
+                   absorb_fraction=config.RASS_IVF_ABSORB_FRACTION)
 
     @classmethod
     def manual(cls, nprobe: int = 8) -> "IvfPolicy":
@@ -519,6 +599,22 @@ class IvfPolicy:
         if covered <= 0:
             return True
         return rows - covered > self.rebuild_fraction * covered
+
+    def action(self, rows: int, covered: int, trained_rows: int) -> Optional[str]:
+        """What an index of ``rows`` rows owes its IVF: ``"train"`` (train + build over everything), ``"absorb"`` (extend
+        the IVF over the delta with the centroids it has) or None.  With ``absorb_fraction`` = 0: ``due`` and nothing else."""
+        if self.absorb_fraction <= 0:
+            return "train" if self.due(rows, covered) else None
+        if self.nlist <= 0 or rows < max(self.min_rows, self.nlist):
+            return None
+        if covered <= 0:
+            return "train"
+        trained = trained_rows if trained_rows > 0 else covered
+        if rows - trained > self.rebuild_fraction * trained:
+            return "train"                      # the centroids are stale
+        if rows - covered > self.absorb_fraction * covered:
+            return "absorb"
+        return None
 
 
 class IvfBackedIndex(FlatIndex):
@@ -533,6 +629,7 @@ class IvfBackedIndex(FlatIndex):
         self.policy = policy or IvfPolicy.from_config()
         self.ivf: Optional[IvfIndex] = None
         self.builds = 0                      # bumped by every swap (part of ``epoch``)
+        self.trained_rows = 0                # rows covered when the IVF's centroids were last trained (IvfPolicy.action)
         self._ivf_lock = threading.RLock()   # deletes and the build's final phase exclude each other
 
     # ---- bookkeeping
@@ -565,27 +662,46 @@ class IvfBackedIndex(FlatIndex):
             centroids = train_centroids(self, nlist, p.train_rows, p.iters, p.seed, group)
         rows = self.rows
         assign = assign_rows(self, centroids)
+        new = self._swap_ivf(lambda: IvfIndex.build(self, nlist=nlist, centroids=centroids, dtype=dtype or p.dtype,
+                                                    assign=assign, n_rows=min(rows, len(assign)) // 32 * 32))
+        self.trained_rows = new.covered_rows
+        return new
+
+    def _swap_ivf(self, make) -> Optional[IvfIndex]:
+        """The one place an IVF is swapped: ``make()`` builds the new one (or returns None: no IVF) under the lock that
+        deletes take, so that no tombstone falls between the build's view of the tags and the swap; ``builds`` is bumped
+        and the old IVF freed.  (A reader that fetched the old IVF just before the swap: see ADVICE.md.)"""
         with self._ivf_lock:
-            new = IvfIndex.build(self, nlist=nlist, centroids=centroids, dtype=dtype or p.dtype, assign=assign,
-                                 n_rows=min(rows, len(assign)) // 32 * 32)
+            new = make()
             old, self.ivf = self.ivf, new
             self.builds += 1
         if old is not None:
             old.close()
         return new
 
+    def absorb_delta(self) -> Optional[IvfIndex]:
+        """Extend the IVF over the rows appended since its build, up to ``rows // 32 * 32`` (the delta must start on a scan
+        tile), with the centroids it has: ``IvfIndex.absorb``.  Returns the new IVF, or None when there is nothing to absorb
+        (no IVF, or fewer than 32 new rows)."""
+        with self._ivf_lock:
+            ivf = self.ivf
+            upto = self.rows // 32 * 32
+            if ivf is None or upto <= ivf.covered_rows:
+                return None
+            return self._swap_ivf(lambda: ivf.absorb(self, upto))
+
     def maybe_rebuild(self) -> bool:
-        if self.policy.due(self.rows, self.covered):
+        what = self.policy.action(self.rows, self.covered, self.trained_rows)
+        if what == "train":
             self.build_ivf()
             return True
+        if what == "absorb":
+            return self.absorb_delta() is not None
         return False
 
     def drop_ivf(self) -> None:
-        with self._ivf_lock:
-            old, self.ivf = self.ivf, None
-            self.builds += 1
-        if old is not None:
-            old.close()
+        self._swap_ivf(lambda: None)
+        self.trained_rows = 0
 
     # ---- write path
     def add(self, vecs, tags=None, normalize: bool = True, first_global_id: int = -1) -> int:
@@ -638,6 +754,7 @@ class IvfBackedIndex(FlatIndex):
                 ivf = IvfIndex.load(engine, f)
                 if ivf.covered_rows <= idx.rows and (ivf.covered_rows % 32 == 0 or ivf.covered_rows == idx.rows):
                     idx.ivf = ivf
+                    idx.trained_rows = ivf.covered_rows     # the file does not say what its centroids were trained on
                 else:
                     ivf.close()
             except Exception:       # a missing / torn IVF file costs a rebuild, never the index
