@@ -673,6 +673,13 @@ int rass_fold_gamma_bf16(const void* d_w, const float* d_gamma, const float* d_b
 int rass_gemm_bf16_fold(const void* d_x, const void* d_w, const float* d_bias, const void* d_residual_raw, void* d_y, int m,
                         int m_pad, int n, int k, int epilogue, const float* d_mr, const float* d_gamma, const float* d_beta,
                         float* d_stats, const float* d_colsum, void* stream);
+/* Which kernel a GEMM entry point would take for this shape, as a short label written into `label` (NUL-terminated, cut to
+ * label_bytes): entry 0 = rass_gemm_bf16_ws (epilogue 0 / 1 / 2), 1 = rass_gemm_bf16_residual_layernorm, 2 =
+ * rass_gemm_bf16_ln_input (epilogue 0 / 2), 3 = rass_gemm_bf16_fold (epilogue 3 / 4 / 5); ws_bytes = 0: no scratch lent.
+ * Labels: fewrows4, fewrows16, splitk<S>, mid64, mid128, tile128, p4, p5; residual_layernorm: fewrows4+ln, splitk<S>+ln,
+ * fewrows+pair, pair; ln_input: lnin16, lnin4; and "unsupported".  Stateless: it touches no device and needs none; it reads
+ * the RASS_GEMM_* switches of the environment as a launch would. */
+int rass_gemm_bf16_route(int entry, int m, int m_pad, int n, int k, int epilogue, size_t ws_bytes, char* label, size_t label_bytes);
 /* stats [rows][n / 128][2] of epilogue 3 -> mr [rows][2] = (mean, rsqrt(var + eps)), summed in chunk order. */
 int rass_ln_stats_finalize(const float* d_stats, int rows, int n, float eps, float* d_mr, void* stream);
 /* Pooling: out[s] = the mean over sequence s's tokens (mode_mean) or its first token, fp32 [nseq][hidden]; normalize:

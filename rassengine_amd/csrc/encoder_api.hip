@@ -22,6 +22,7 @@
 
 #include "../../include/rass_engine.h"
 #include "encoder_kernels.h"
+#include "gemm_route.h"
 
 extern "C" void rassint_set_last_error(const char* msg);  // api.hip (internal, not part of the ABI)
 
@@ -66,7 +67,7 @@ struct Layer {
     void* w_down = nullptr;  // bf16 [H][I]
     float* b_down = nullptr;
     float *ln2_g = nullptr, *ln2_b = nullptr;
-    // LayerNorm folded into its consumer GEMMs (big batches; encoder_gemm.hip, LnFold): W' = W diag(gamma) in bf16, the
+    // LayerNorm folded into its consumer GEMMs (big batches; gemm_common.h, LnFold): W' = W diag(gamma) in bf16, the
     // fp32 column sums of W' and bias' = b + beta W^T.  QKV folds the PREVIOUS layer's output LayerNorm (layer 0: identity,
     // its input arrives normalised from the embedding LayerNorm), FFN-up this layer's attention-output LayerNorm.
     void *w_qkv_f = nullptr, *w_up_f = nullptr;
@@ -227,7 +228,7 @@ int prepare_fold(rass_encoder* e) {
     return RASS_OK;
 }
 
-// The big-batch forward with both LayerNorms of every layer folded into the GEMMs around them (encoder_gemm.hip, LnFold):
+// The big-batch forward with both LayerNorms of every layer folded into the GEMMs around them (gemm_common.h, LnFold):
 // e->x holds the RAW layer output r2 (layer 0: the normalised embeddings, statistics = identity), e->y the raw r1.
 int forward_fold(rass_encoder* e, const int32_t* d_cu, int nseq, int total, int Tp, int max_seqlen, float* d_out, hipStream_t st) {
     const rass_encoder_config& c = e->cfg;
@@ -657,6 +658,14 @@ int rass_gemm_bf16_fold(const void* d_x, const void* d_w, const float* d_bias, c
     return launch_rc(rass::launch_gemm_bf16_fold(d_x, d_w, d_bias, d_residual_raw, d_y, m, m_pad, n, k, epilogue, d_mr, d_gamma, d_beta,
                                                  d_stats, d_colsum, reinterpret_cast<hipStream_t>(stream)),
                      "folded-LayerNorm GEMM launch");
+}
+
+int rass_gemm_bf16_route(int entry, int m, int m_pad, int n, int k, int epilogue, size_t ws_bytes, char* label, size_t label_bytes) {
+    rass::rass_env_new_scope();
+    if (!label || label_bytes == 0) return efail(RASS_ERR_INVALID, "NULL label");
+    if (entry < 0 || entry > 3) return efail(RASS_ERR_INVALID, "entry 0 (gemm_ws), 1 (residual_layernorm), 2 (ln_input) or 3 (fold)");
+    rass::gemm_route_label(entry, rass::GemmShape{m, m_pad, n, k}, epilogue, ws_bytes, rass::gemm_switches(), label, label_bytes);
+    return RASS_OK;
 }
 
 int rass_ln_stats_finalize(const float* d_stats, int rows, int n, float eps, float* d_mr, void* stream) {

@@ -27,6 +27,7 @@
 #include <string.h>
 
 #include "encoder_kernels.h"
+#include "gemm_route.h"
 
 namespace rass {
 
@@ -191,7 +192,7 @@ __global__ __launch_bounds__(kAttnThreads) void attention_kernel(const u16* __re
 // A query's few rows (all sequences of the batch together <= 32 tokens: embed_query / ollama_embed_text,
 // app/main.py:225-237, 266-274): the attention RECOMPUTED inside the attention-output GEMM (round 4).  Every kernel of a
 // one-query forward costs ~4-5 us whatever it does, and this attention is 16 heads x a 16 x 16 score tile:
-// each of the N / 16 workgroups of the few-rows GEMM (16 output features, encoder_gemm.hip gemm_bf16_fewrows_kernel) runs
+// each of the N / 16 workgroups of the few-rows GEMM (16 output features, gemm_fewrows.hip gemm_bf16_fewrows_kernel) runs
 // it again instead of reading `ctx` from a launch of its own.  A workgroup has 16 waves, wave = head = a 64-deep slice of
 // the GEMM's K: the wave
 //   1. has its two weight fragments W[n0 + i][64 head + 32 u + 8 g ..] in flight first,
@@ -374,8 +375,7 @@ bool attn_out_fused_ok(int M, int nseq, int hidden, int heads, int N) {
     // RASS_ATTN_FUSE=0 / RASS_GEMM_FEWROWS=0 (read per launch: the A/B) keep the attention launch + the few-rows GEMM
     const char* v = rass_env("RASS_ATTN_FUSE");
     if (v && v[0] == '0') return false;
-    const char* f = rass_env("RASS_GEMM_FEWROWS");
-    if (f && f[0] == '0') return false;
+    if (!gemm_switches().fewrows) return false;
     return M >= 1 && M <= 32 && nseq >= 1 && nseq <= M && hidden == 16 * kHeadDim && heads == 16 && N % 16 == 0 && N >= 16;
 }
 

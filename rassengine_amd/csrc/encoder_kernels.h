@@ -13,13 +13,16 @@ namespace rass {
 // environment: the host could not enqueue faster than the GPU ran (round 4: 4.5 us per launch on the host).  rass_env(name)
 // = getenv(name), remembered per thread until rass_env_new_scope() — called at every C-ABI entry of the encoder, so a switch is
 // still read once per call.  `name` must be a string literal (the table is keyed by its address).
+// (The GEMM's switches are parsed once per scope into GemmSwitches, gemm_route.h: the only reader of RASS_GEMM_* names.)
 const char* rass_env(const char* name);
 void rass_env_new_scope();
+unsigned long rass_env_scope();   // the current scope's number (what gemm_switches() keys its copy by)
 
 // K5: Y = epilogue(X[M,K] * W[N,K]^T + bias); epilogue 0 bias, 1 bias+residual, 2 bias+GELU(erf).
 // M_pad (multiple of 128) rows of X / Y / residual must be allocated; N % 128 == 0, K % 64 == 0.
-// With a scratch (`splitk_ws`, fp32) a GEMM over few rows (M_pad <= 256) is split over K so that enough workgroups
-// stream the weights (query-time embedding); the result is deterministic (slices summed in fixed order).
+// With a scratch (`splitk_ws`, fp32) a GEMM over few rows is split over K so that enough workgroups stream the weights, or
+// runs as one few-rows launch (query-time embedding); the result is deterministic (slices summed in fixed order).
+// Which kernel a shape gets: route_gemm (gemm_route.h; DESIGN.md §4 has the table).
 hipError_t launch_gemm_bf16(const void* X, const void* W, const float* bias, const void* residual, void* Y, int M,
                             int M_pad, int N, int K, int epilogue, hipStream_t stream, float* splitk_ws = nullptr,
                             size_t splitk_ws_bytes = 0);
@@ -42,7 +45,7 @@ hipError_t launch_splitk_residual_layernorm(const float* partial, int S, int row
                                             const float* bias, const void* residual, const float* gamma,
                                             const float* beta, float eps, void* out, hipStream_t stream);
 
-// ---- LayerNorm folded into the GEMMs around it (big batches on the persistent kernel; encoder_gemm.hip, LnFold) ----
+// ---- LayerNorm folded into the GEMMs around it (big batches on the persistent kernel; gemm_common.h, LnFold) ----
 // gemm_bf16_fold_ok: all four GEMMs of a layer run on the persistent 256^2 kernel at this batch (and RASS_ENCODER_LN_FOLD != 0).
 // launch_gemm_bf16_fold, epilogue 3: Y = X W^T + bias + LN(residual_raw) with LN rebuilt from (mr, gamma, beta) per element;
 //   Y is the RAW sum (bf16); `stats` [M][N/128][2] receives the partial (sum, sum of squares) of the stored values.

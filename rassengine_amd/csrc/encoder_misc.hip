@@ -423,6 +423,7 @@ thread_local unsigned long t_env_scope = 1;
 }  // namespace
 
 void rass_env_new_scope() { ++t_env_scope; }
+unsigned long rass_env_scope() { return t_env_scope; }
 
 const char* rass_env(const char* name) {
     for (int i = 0; i < t_env_n; ++i) {

@@ -1,4 +1,4 @@
-"""Derives and checks the constants of gelu_erf (rassengine_amd/csrc/encoder_gemm.hip):
+"""Derives and checks the constants of gelu_erf (rassengine_amd/csrc/gemm_common.h):
    GELU(x) = max(x, 0) - h * erfc(h sqrt2),  h = |x| / 2,  erfc(h sqrt2) ~= exp2(Q(min(h, 5 / sqrt2))),
 Q = the degree-7 least-squares (Chebyshev-node) fit of log2(erfc(z)) on z in [0, 5], re-expressed in h.  Prints the
 coefficients and the maximum |error| of the fp32 evaluation against math.erf over [-12, 12]."""

@@ -2,7 +2,7 @@
 // source (round 1's kernels, retired from the product in round 3: gemm_retired_kernels.hip; RASS_GEMM_CLOCKS adds four
 // wall-clock stamps per block: start, after the pipeline prologue, after the K loop, after the epilogue stores have
 // drained) and prints the mean phase lengths.  RASS_GEMM_VARIANT=ring | pring (default pring) picks the kernel.
-// Build: hipcc -O3 -std=c++17 --offload-arch=gfx950 -o gemm_phases.bin gemm_phases.hip ../../rassengine_amd/csrc/encoder_misc.hip
+// Build: hipcc -O3 -std=c++17 --offload-arch=gfx950 -o gemm_phases.bin gemm_phases.hip
 #define RASS_GEMM_CLOCKS 1
 #define RASS_RETIRED_NO_MAIN 1
 #include "gemm_retired_kernels.hip"

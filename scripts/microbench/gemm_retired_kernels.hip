@@ -6,13 +6,14 @@
 //   gemm_bf16_pring_kernel  its persistent form, next tile's first steps under the epilogue       (round 1 default)
 //   gemm_bf16_p64_kernel    64-deep K steps on two 64-KiB slots (whole cache lines per row)       (round 2)
 //   gemm_bf16_w4l_kernel    four waves of 128 x 128, accumulators pinned in AGPRs                 (round 2)
-// It still builds and runs (it includes the product source for the shared helpers and times every variant against p5):
-//   hipcc -O3 -std=c++17 --offload-arch=gfx950 -o gemm_retired.bin gemm_retired_kernels.hip ../../rassengine_amd/csrc/encoder_misc.hip && ./gemm_retired.bin
+// It still builds and runs (it includes the product's p5 unit, gemm_p5.hip, for p5 itself, the diagnostics' globals and —
+// through gemm_common.h — the shared helpers, and times every variant against p5):
+//   hipcc -O3 -std=c++17 --offload-arch=gfx950 -o gemm_retired.bin gemm_retired_kernels.hip && ./gemm_retired.bin
 // Not part of the product; nothing under rassengine_amd/ refers to it.
 #ifndef RASS_RETIRED_NO_MAIN
 #define RASS_RETIRED_WITH_MAIN 1
 #endif
-#include "../../rassengine_amd/csrc/encoder_gemm.hip"
+#include "../../rassengine_amd/csrc/gemm_p5.hip"
 
 namespace rass {
 
@@ -1215,7 +1216,16 @@ static hipError_t launch_retired_epi(const char* variant, const u16* X, const u1
     if (strcmp(variant, "pring") == 0) return launch_pring<EPI>(X, W, bias, residual, Y, M, M_pad, N, K, stream);
     if (strcmp(variant, "p64") == 0) return launch_p64<EPI>(X, W, bias, residual, Y, M, M_pad, N, K, stream);
     if (strcmp(variant, "w4l") == 0) return launch_w4l<EPI>(X, W, bias, residual, Y, M, M_pad, N, K, stream);
-    return launch_p5<EPI>(X, W, bias, residual, Y, M, M_pad, N, K, stream);
+    static int n_cus = 0;
+    if (n_cus == 0) {
+        int dev = 0;
+        if (hipGetDevice(&dev) != hipSuccess ||
+            hipDeviceGetAttribute(&n_cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n_cus <= 0)
+            n_cus = 256;
+    }
+    const int tiles_total = (N / RBN) * (M_pad / RBM);
+    return launch_p5(EPI, 1, GemmOperands{X, W, bias, residual, Y, M, N, K}, tiles_total, tiles_total < n_cus ? tiles_total : n_cus,
+                     stream, LnFold{});
 }
 
 hipError_t launch_retired(const char* variant, const void* X, const void* W, const float* bias, const void* residual, void* Y,

@@ -44,6 +44,8 @@ import ctypes
 import numpy as np
 import pytest
 
+from tests.helpers import _residual_branch, _splitk_slices  # noqa: F401  (the routing mirror)
+
 pytestmark = pytest.mark.gpu
 
 U = 2.0 ** -24
@@ -243,51 +245,6 @@ def test_layernorm_kernel(gpu, hidden, rows, monkeypatch):
 
 
 # --------------------------------------------------------------------------------------------- c. residual + LayerNorm
-def _splitk_slices(m_pad, n, k, ws_bytes):
-    tiles, steps = (n // 128) * (m_pad // 128), k // 64
-    if steps < 2:
-        return 0
-    s = 1
-    if k < 2048:
-        while s < 4 and tiles * s < 128 and steps % (2 * s) == 0:
-            s *= 2
-    else:
-        cap = 16 if tiles <= 8 else (8 if tiles < 48 else 4)
-        while s < cap and tiles * s * 2 <= 512 and steps % (2 * s) == 0:
-            s *= 2
-    while s > 1 and s * m_pad * n * 4 > ws_bytes:
-        s //= 2
-    return s if s > 1 else 0
-
-
-def _residual_branch(m, m_pad, n, k, ws_bytes, forced_s=None):
-    """the branch launch_gemm_bf16_residual_layernorm takes (default switches): mirrors its conditions"""
-    if not ws_bytes:
-        return "pair"
-
-    def fewrows_waves(M, N, K):
-        if M < 1 or N % 16 or N < 1024:
-            return 0
-        if K % 1024 == 0 and K <= 3072:
-            return 4 if M <= 96 else 0
-        if M > 64:
-            return 0
-        return 16 if (K % 4096 == 0 and K <= 8192) else 0
-
-    if m_pad >= 64 and m <= 64 and fewrows_waves(m, n, k // 4 if k % 4096 == 0 else k):
-        rows_pad = 64 if m <= 64 else 128
-        if k % 4096 == 0 and k // 4 <= 3072 and n % 8 == 0 and n <= 2048 and 4 * rows_pad * n * 4 <= ws_bytes:
-            return "fewrows4+ln" + ("_exact" if n == 1024 else "")
-        return "fewrows+pair"
-    mid = 96 < m <= 1024
-    if m_pad % 128 == 0 and n % 128 == 0 and k % 64 == 0 and n <= 2048 and not (mid and 256 <= k <= 1024):
-        mp = (m + 127) // 128 * 128
-        s = forced_s if forced_s else _splitk_slices(mp, n, k, ws_bytes)
-        if s:
-            return "splitk%d+ln" % s + ("_exact" if n == 1024 and s in (2, 4, 8) else "")
-    return "pair"
-
-
 _RES_CASES = [  # (m, n, k, ws?, forced RASS_GEMM_SPLITK_S)
     (1, 1024, 4096, True, None), (16, 1024, 4096, True, None), (17, 1024, 4096, True, None), (64, 1024, 4096, True, None),
     (1, 1024, 1024, True, None), (16, 1024, 1024, True, None),
