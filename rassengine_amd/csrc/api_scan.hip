@@ -50,11 +50,14 @@ int64_t scan_sample_floor_min_share() {  // the slab must hold at least this man
 }
 
 // The sample floor of the int8 and bf16 scans (scan_i8.hip, scan_bf16.hip): worth a short extra launch when the slab is many samples long.
-// RASS_I8_SAMPLE_FLOOR=0 turns it off (the A/B; results do not depend on it).  Read per call: the tests switch it.
+// RASS_I8_SAMPLE_FLOOR=0 turns it off and =force lowers the size rule from eight samples to two, as RASS_SCAN_SAMPLE_FLOOR=force
+// does for the fp32 scan (the A/B and the tests; results do not depend on it).  Read per call, so that one process can compare
+// the settings: tests/test_gpu_lowprec_floor.py checks 0 / force / default against the CPU oracle and against each other.
 bool i8_sample_floor(int64_t rows, int grid) {
     const char* e = getenv("RASS_I8_SAMPLE_FLOOR");
-    if (e && atoi(e) == 0) return false;
-    return grid <= rass::kMaxSampleGroups && rows >= (int64_t)8 * 64 * grid;
+    const bool force = e && e[0] == 'f';
+    if (e && !force && atoi(e) == 0) return false;
+    return grid <= rass::kMaxSampleGroups && rows >= (int64_t)(force ? 2 : 8) * 64 * grid;
 }
 
 // RASS_SCAN_BATCH_SAMPLE=groups: the fused fp32 batch samples group by group instead of in one launch (the A/B).  Read per call.

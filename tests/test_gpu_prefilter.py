@@ -1,21 +1,26 @@
 """Prefilter mode: bf16 candidate scan + exact fp32 re-rank.  Returned scores
 must be BIT-IDENTICAL to the flat fp32 path for every returned row; on these (random,
-well-separated) corpora the id lists must be identical too (recall 1.0)."""
+well-separated) corpora the id lists must be identical too (recall 1.0).  The two comparisons with the flat path run
+at every stride the bf16 scan is built for (256 / 512 / 768 / 1024 columns)."""
 import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
 
 
+DIMS = [256, 512, 768, 1024]
+
+
 @pytest.fixture()
-def engine(gpu):
+def engine(request, gpu):
     from rassengine_amd.engine import Engine
-    eng = Engine(device=0, dim=1024)
+    eng = Engine(device=0, dim=getattr(request, "param", 1024))
     yield eng
     eng.close()
 
 
-def test_prefilter_matches_flat_path(engine, oracle):
+@pytest.mark.parametrize("engine,dim", [(d, d) for d in DIMS], indirect=["engine"], ids=[str(d) for d in DIMS])
+def test_prefilter_matches_flat_path(engine, oracle, dim):
     rng = np.random.default_rng(8)
     idx = engine.open_index("pf")
     idx.set_prefilter(True)                      # enabled before any row exists
@@ -23,7 +28,7 @@ def test_prefilter_matches_flat_path(engine, oracle):
     n = 0
     tags_all = []
     for c in (1, 40, 3000, 17, 9000):            # odd batch sizes: bf16 slab kept in sync on add + growth
-        x = rng.standard_normal((c, 1024), dtype=np.float32)
+        x = rng.standard_normal((c, dim), dtype=np.float32)
         t = rng.integers(1, 4, size=c).astype(np.int32)
         idx.add(x, tags=t)
         tags_all.append(t)
@@ -31,7 +36,7 @@ def test_prefilter_matches_flat_path(engine, oracle):
     tags = np.concatenate(tags_all)
     idx.delete(7)
     idx.delete(4000)
-    q = rng.standard_normal((45, 1024), dtype=np.float32)
+    q = rng.standard_normal((45, dim), dtype=np.float32)
     qf = rng.integers(-1, 4, size=45).astype(np.int32)
     for k in (1, 5, 10, 16, 32):                 # k > 16 silently takes the exact flat scan
         s_p, i_p = idx.search(q, k, q_filter=qf)
@@ -61,14 +66,15 @@ def test_prefilter_small_and_padding(engine):
     assert i[0, 0] == 0 and i[1, 0] == 1
 
 
-def test_prefilter_near_duplicates_are_reranked_exactly(engine, oracle):
+@pytest.mark.parametrize("engine,dim", [(d, d) for d in DIMS], indirect=["engine"], ids=[str(d) for d in DIMS])
+def test_prefilter_near_duplicates_are_reranked_exactly(engine, oracle, dim):
     """Rows closer together than bf16 resolution: the candidate scan cannot order them, the
     fp32 re-rank must (and equal scores must come back id-ascending)."""
     rng = np.random.default_rng(10)
-    base = rng.standard_normal((1, 1024)).astype(np.float32)
-    x = np.repeat(base, 20, axis=0) + 1e-4 * rng.standard_normal((20, 1024)).astype(np.float32)
+    base = rng.standard_normal((1, dim)).astype(np.float32)
+    x = np.repeat(base, 20, axis=0) + 1e-4 * rng.standard_normal((20, dim)).astype(np.float32)
     x[11] = x[3]                                  # exact duplicate
-    filler = rng.standard_normal((2000, 1024)).astype(np.float32)
+    filler = rng.standard_normal((2000, dim)).astype(np.float32)
     idx = engine.open_index("pf-dup")
     idx.add(np.concatenate([filler, x]))
     q = base * 3.0
