@@ -250,6 +250,43 @@ int rass_index_search_device_batch(rass_index_t* idx, const float* d_queries, in
                                    float* d_out_scores, int64_t* d_out_ids,
                                    int64_t out_scores_group_stride, int64_t out_ids_group_stride);
 
+/* Score-threshold (RADIAL) search: every row whose score is at least min_score[q] — the radial form of the k-NN clause
+ * (`min_score` instead of `k`) — and how many there are, in ONE corpus pass per launch group: the flat scan computes every
+ * (row, query) score anyway, and a threshold question needs no ranking inside it, only emission.
+ * A row MATCHES query q when it is live, passes the filter exactly as in rass_index_search_ex (q_filter NULL, exact, or
+ * (tag & q_filter_mask[q]) == q_filter[q]) and its score s satisfies s >= min_score[q].  s is the fp32 value of the flat
+ * scan (the same MFMA chain, the same p0 + ... + p7 sum of the partials): bit-identical to the score rass_index_search_ex
+ * reports for that row.  out_total[q] is the EXACT number of matching rows, whatever max_hits is.
+ * out_scores / out_ids are [nq][max_hits], 1 <= max_hits <= RASS_MAX_K_MULTIPASS: the matching rows, score descending, ties
+ * by id ascending, (-inf, -1) past the end.  Ids as rass_index_search_ex reports them: ordinals, or the caller-assigned ids
+ * of rass_index_add_ex.
+ * More matches than max_hits (out_total[q] > max_hits): the list holds the BEST max_hits matching rows, which the call
+ * gets from the exact k = max_hits path of rass_index_search_ex for those queries only (ceil(max_hits / 32) more passes;
+ * on an index with caller-assigned ids that path serves max_hits <= RASS_MAX_K, beyond: RASS_ERR_UNSUPPORTED).
+ * min_score: -inf is allowed (with a patient filter out_total is then that patient's live row count); NaN ->
+ * RASS_ERR_INVALID.  Any nq (scanned in groups of RASS_MAX_QBATCH).
+ * fp32 indices of every dim the engine takes, wide rows included; a bf16 index answers RASS_ERR_UNSUPPORTED.  The
+ * prefilter mode of the index is ignored: a range search always runs the exact scan, because a candidate scan cannot
+ * bound a count.  IVF, cross-index batches and the sharded multi-GPU front have no range form.
+ * Thread-safety and layout epochs as rass_index_search_ex: the engine lock is held while enqueuing only, and the answer
+ * comes from ONE layout of the index. */
+int rass_index_search_range(rass_index_t* idx, const float* queries, int nq,
+                            const float* min_score, int max_hits,
+                            const int32_t* q_filter, const int32_t* q_filter_mask,
+                            float* out_scores, int64_t* out_ids, int64_t* out_total);
+/* Device-resident variant: every pointer is device memory, nothing is synchronised and nothing is read back;
+ * nq <= RASS_MAX_QBATCH.  Ids are id_base + row (ignored on an index with caller-assigned ids, which are reported), to be
+ * paired with the layout epoch read before the call.  d_total[q] is the exact count as above.  A query with more matches
+ * than max_hits gets the EMPTY list (every slot (-inf, -1)) and d_total[q] says why: which max_hits of the matching rows
+ * the scan kept depends on the order its workgroups ran in, so they are not reported; ask again with a larger max_hits,
+ * a higher threshold, or rass_index_search_device_ex with k = max_hits.  A NaN threshold matches nothing (total 0): it
+ * cannot be refused without reading it back. */
+int rass_index_search_range_device(rass_index_t* idx, const float* d_queries, int nq,
+                                   const float* d_min_score, int max_hits,
+                                   const int32_t* d_q_filter, const int32_t* d_q_filter_mask,
+                                   int64_t id_base, float* d_out_scores, int64_t* d_out_ids,
+                                   int64_t* d_total);
+
 /* Prefilter mode (SURVEY §8f-4 "bf16 (or int8)"; the reference's own index is approximate, app/main.py:563-572), OFF by
  * default.  `enable` = RASS_PREFILTER_BF16 (1): keep a bf16 copy of the slab, scan IT (half the HBM bytes per pass, bf16
  * MFMA) for the 32 best candidates per query; RASS_PREFILTER_INT8 (2): keep an int8 copy (a quarter of the bytes; per row

@@ -5,7 +5,8 @@
 //   api.hip          errors; the engine and the flat index: create / grow / add / delete / persist / destroy; timers, the
 //                    stateless wrappers, k-means, peer buffers
 //   api_scan.hip     the tuning switches, the shared launch helpers declared below, and the four flat launch paths
-//   api_search.hip   flat search entry points: one group, the fused batches, the host API with its pinned slots, search_multi
+//   api_search.hip   flat search entry points: one group, the fused batches, the host API with its pinned slots, search_multi,
+//                    the score-threshold (range) search
 //   api_ivf.hip      IVF build, persistence, probe, delta and batch
 //   api_compact.hip  compaction of a flat index, its layout epoch, the stateless wrappers of compact.hip
 //
@@ -165,6 +166,26 @@ struct CertView {
 };
 CertView cert_layout(unsigned char* base, int grid, int64_t stride, int64_t stride_i8, int dim);
 
+// A range search's share of the engine scratch (one launch group): the queries where every scan keeps them, one counter line
+// per query and the unsorted hits [32][kRangeMaxHits] — about 1.3 MiB of the scratch's 12.
+struct RangeView {
+    float* q_padded;
+    unsigned* count;               // [32][kRangeCountStride]
+    uint2* hits;                   // [32][kRangeMaxHits] (score bits, row); a call uses [nq][max_hits]
+    size_t total;
+};
+RangeView range_layout(unsigned char* base);
+
+// The host range search's device staging (eng->d_range): thresholds in, totals and lists out, of one launch group.
+struct RangeIoView {
+    float* thr;                    // [32]
+    int64_t* total;                // [32]
+    float* out_scores;             // [32][kRangeMaxHits]; a call uses [nq][max_hits]
+    int64_t* out_ids;
+    size_t bytes;
+};
+RangeIoView range_io_layout(unsigned char* base);
+
 // A grow-on-demand device block (eng->d_batch, eng->d_cert, rass_ivf::d_batch): at least `need` bytes afterwards.  Growth
 // waits for the stream first: an earlier call on it may still read the old block.
 int grow_block(unsigned char** block, size_t* bytes, size_t need, hipStream_t st);
@@ -182,6 +203,7 @@ struct HostSlot {
     int64_t* h_scanned = nullptr;  // [1]
     void* base = nullptr;          // the one hipHostMalloc behind all of the above
     void* h_items = nullptr;       // pinned work list of a cross-index batch (lazily allocated, kMultiMaxItems)
+    void* h_range = nullptr;       // pinned image of a RangeIoView: the host range search's group (lazily allocated)
     hipEvent_t done = nullptr;
     bool busy = false;
 };
@@ -206,6 +228,9 @@ struct rass_engine {
     // workspace of the certified int8 search (prefilter mode 3): one pass of kCertQ queries, grown on demand
     unsigned char* d_cert = nullptr;
     size_t cert_bytes = 0;
+    // device staging of the host range search (RangeIoView), allocated by its first call
+    unsigned char* d_range = nullptr;
+    size_t range_bytes = 0;
     // host-API staging
     float* d_qraw = nullptr;        // [32][dim]
     int32_t* d_qfilter = nullptr;   // [32]

@@ -148,6 +148,27 @@ CertView cert_layout(unsigned char* base, int grid, int64_t stride, int64_t stri
     return L;
 }
 
+RangeView range_layout(unsigned char* base) {
+    Carver c{base};
+    RangeView L;
+    L.q_padded = c.take<float>((size_t)RASS_MAX_QBATCH * kMaxStride * sizeof(float));   // = ScratchView::q_padded
+    L.count = c.take<unsigned>((size_t)RASS_MAX_QBATCH * rass::kRangeCountStride * sizeof(unsigned));
+    L.hits = c.take<uint2>((size_t)RASS_MAX_QBATCH * rass::kRangeMaxHits * sizeof(uint2));
+    L.total = c.off;
+    return L;
+}
+
+RangeIoView range_io_layout(unsigned char* base) {
+    Carver c{base};
+    RangeIoView L;
+    L.thr = c.take<float>(RASS_MAX_QBATCH * sizeof(float));
+    L.total = c.take<int64_t>(RASS_MAX_QBATCH * sizeof(int64_t));
+    L.out_scores = c.take<float>((size_t)RASS_MAX_QBATCH * rass::kRangeMaxHits * sizeof(float));
+    L.out_ids = c.take<int64_t>((size_t)RASS_MAX_QBATCH * rass::kRangeMaxHits * sizeof(int64_t));
+    L.bytes = c.off;
+    return L;
+}
+
 int grow_block(unsigned char** block, size_t* bytes, size_t need, hipStream_t st) {
     if (*bytes >= need) return RASS_OK;
     HIP_TRY(hipStreamSynchronize(st));   // growth only: the block may still be read by an earlier call

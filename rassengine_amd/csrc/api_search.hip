@@ -1,7 +1,7 @@
 // api_search.hip — the C ABI of include/rass_engine.h: searching a flat index.  The dispatch of one launch group
 // to its launch path (api_scan.hip), the two fused batches (fp32 and prefilter), the device entry points and the
-// candidates hooks, the host search API with its pinned slots (k > 32 in passes), and the cross-index batch
-// rass_index_search_multi.  Host-side C++ only.  The objects and the threading rules: api_internal.h.
+// candidates hooks, the host search API with its pinned slots (k > 32 in passes), the cross-index batch
+// rass_index_search_multi, and the score-threshold search rass_index_search_range(_device).  Host-side C++ only.  The objects and the threading rules: api_internal.h.
 
 #include "api_internal.h"
 
@@ -55,14 +55,15 @@ namespace {
 
 // One launch group (<= 32 queries) of a device search; the caller holds eng->mu and has set the device.  r.id_base is the
 // caller's; row_tag / id_map come from the index.  one_pass = false: a pass of a k > RASS_MAX_K host search, which stays
-// on the exact scan whatever the prefilter mode.
-int search_device_group(rass_index* idx, FlatRequest r, bool one_pass = true) {
+// on the exact scan whatever the prefilter mode.  exact = true: the exact scan whatever the mode and k (the overflow
+// fallback of a range search, whose answer may not depend on a candidate scan).
+int search_device_group(rass_index* idx, FlatRequest r, bool one_pass = true, bool exact = false) {
     rass_engine* eng = idx->eng;
     const IndexView iv = index_view(idx, r.q_filter != nullptr, r.id_base, r.after_score != nullptr);
     r.use(iv);
     if (idx->dtype == RASS_BF16) return bf16_scan_launch(idx, r);
-    if (idx->prefilter == 3 && iv.rows > 0 && !r.after_score && one_pass) return cert_launch(idx, r);
-    if (idx->prefilter && idx->prefilter != 3 && iv.rows > 0 && r.k <= kPrefilterMaxK && !r.after_score)
+    if (!exact && idx->prefilter == 3 && iv.rows > 0 && !r.after_score && one_pass) return cert_launch(idx, r);
+    if (!exact && idx->prefilter && idx->prefilter != 3 && iv.rows > 0 && r.k <= kPrefilterMaxK && !r.after_score)
         return prefilter_launch(idx, r);
     // the continuation bound names ROWS of this index (the kernel compares id_base + row): the scan runs with
     // id_base 0 and the ids are translated afterwards, as for caller-assigned ids
@@ -270,6 +271,70 @@ int prefilter_launch_batch(rass_index* idx, const FlatRequest& r, int64_t gs, in
     return RASS_OK;
 }
 
+// One launch group (<= 32 queries) of a range search: normalise -> zero the counters -> the range scan (two launches for
+// 17..32 queries on wide rows) -> range_finish.  Always the exact fp32 scan: the prefilter mode of the index is not looked
+// at.  Everything is a device pointer; the caller holds eng->mu, has set the device and has checked the arguments.
+struct RangeRequest {
+    const float* queries = nullptr;     // [nq][dim]
+    int nq = 0;
+    const float* min_score = nullptr;   // [nq]
+    int max_hits = 0;
+    const int32_t* q_filter = nullptr;
+    const int32_t* q_filter_mask = nullptr;
+    int64_t id_base = 0;
+    float* out_scores = nullptr;        // [nq][max_hits]
+    int64_t* out_ids = nullptr;
+    int64_t* total = nullptr;           // [nq]
+};
+int range_device_group(rass_index* idx, const RangeRequest& r) {
+    rass_engine* eng = idx->eng;
+    hipStream_t st = eng->stream;
+    const int nq = r.nq;
+    const IndexView iv = index_view(idx, r.q_filter != nullptr, r.id_base);
+    const int64_t stride = idx->stride;
+    if (iv.rows < 0 || iv.rows > 0x7fffffc0LL) return fail(RASS_ERR_INVALID, "n_rows out of range for one scan");
+    if (!rass::scan_supported_stride(stride) || stride > kMaxStride) return fail(RASS_ERR_UNSUPPORTED, kStrideMsg);
+    if (range_layout(nullptr).total > eng->scratch_bytes) return fail(RASS_ERR_INVALID, "scan workspace too small");
+    const RangeView L = range_layout(eng->d_scratch);
+    HIP_TRY(rass::launch_normalize_rows_f32(r.queries, idx->dim, L.q_padded, stride, nq, idx->dim, st, pad_nq(nq)));
+    HIP_TRY(hipMemsetAsync(L.count, 0, (size_t)RASS_MAX_QBATCH * rass::kRangeCountStride * sizeof(unsigned), st));
+    const int grid = scan_grid((iv.rows + 31) / 32, 1, eng->n_cus);
+    // wide rows: 16 queries per launch, as for the top-k scan (scan_launch)
+    const int per_launch = stride > kNarrowStride ? 16 : RASS_MAX_QBATCH;
+    for (int q0 = 0; q0 < nq; q0 += per_launch) {
+        rass::ScanArgs a;
+        a.corpus = iv.corpus;
+        a.row_tag = iv.row_tag;
+        a.q_padded = L.q_padded + (int64_t)q0 * stride;
+        a.q_filter = r.q_filter ? r.q_filter + q0 : nullptr;
+        a.q_filter_mask = r.q_filter_mask ? r.q_filter_mask + q0 : nullptr;
+        a.part_scores = nullptr;
+        a.part_ids = nullptr;
+        a.row_stride = stride;
+        a.id_base = 0;   // the hits name rows of the slab: range_finish translates them
+        a.n_rows = (int)iv.rows;
+        a.nq = std::min(per_launch, nq - q0);
+        a.k = 1;
+        a.xcd_skew = scan_xcd_skew(a.nq, grid, eng->n_cus);
+        a.range_thr = r.min_score + q0;
+        a.range_count = L.count + q0 * rass::kRangeCountStride;
+        a.range_hits = L.hits + (int64_t)q0 * r.max_hits;
+        a.range_cap = r.max_hits;
+        const int rc = timed_launch(eng, st, [&] { return HIP_RC(rass::launch_scan_topk_f32(a, grid, st)); });
+        if (rc != RASS_OK) return rc;
+    }
+    HIP_TRY(rass::launch_range_finish(L.count, L.hits, nq, r.max_hits, iv.id_base, iv.id_map, r.out_scores, r.out_ids, r.total, st));
+    return RASS_OK;
+}
+
+// The argument checks the two range entry points share.
+int check_range(const rass_index* idx, int max_hits, const int32_t* q_filter, const int32_t* q_filter_mask) {
+    if (max_hits < 1 || max_hits > RASS_MAX_K_MULTIPASS) return fail(RASS_ERR_INVALID, "max_hits must be in [1, RASS_MAX_K_MULTIPASS]");
+    if (q_filter_mask && !q_filter) return fail(RASS_ERR_INVALID, "q_filter_mask without q_filter");
+    if (idx->dtype != RASS_F32) return fail(RASS_ERR_UNSUPPORTED, "range search needs an fp32 index");
+    return RASS_OK;
+}
+
 // What the device entry points of one launch group share: argument checks, the engine lock, the device.
 int search_device_locked(rass_index_t* idx, const FlatRequest& r) {
     if (!idx || !r.queries || !r.out_scores || !r.out_ids) return fail(RASS_ERR_INVALID, "NULL argument");
@@ -420,8 +485,9 @@ int rass_index_candidates_exact_device(rass_index_t* idx, const float* d_queries
     return cert_launch(idx, r);
 }
 
+// exact = true: every pass on the exact fp32 scan, whatever the index's prefilter mode (search_device_group).
 static int search_ex_once(rass_index_t* idx, const float* queries, int nq, int k, const int32_t* q_filter,
-                          const int32_t* q_filter_mask, float* out_scores, int64_t* out_ids) {
+                          const int32_t* q_filter_mask, float* out_scores, int64_t* out_ids, bool exact = false) {
     rass_engine* eng = idx->eng;
     int rc = set_device(eng);
     if (rc != RASS_OK) return rc;
@@ -454,7 +520,7 @@ static int search_ex_once(rass_index_t* idx, const float* queries, int nq, int k
                 }
                 if (cont && idx->has_gid.load(std::memory_order_acquire))  // the continuation bound compares row ordinals, the caller would hand back global ids
                     return fail(RASS_ERR_UNSUPPORTED, "k > RASS_MAX_K on an index with caller-assigned row ids");
-                rc = search_device_group(idx, r, /*one_pass=*/k <= RASS_MAX_K);
+                rc = search_device_group(idx, r, /*one_pass=*/k <= RASS_MAX_K, exact);
                 if (rc != RASS_OK) return rc;
                 rc = slot_download(eng, sl, b, kk);
                 if (rc != RASS_OK) return rc;
@@ -609,6 +675,109 @@ int rass_index_search_multi(rass_index_t* const* idxs, const float* queries, int
         return sum;
     };
     return one_layout(epochs, [&] { return search_multi_once(eng, idxs, queries, nq, k, q_filter, q_filter_mask, out_scores, out_ids); });
+}
+
+int rass_index_search_range_device(rass_index_t* idx, const float* d_queries, int nq, const float* d_min_score, int max_hits,
+                                   const int32_t* d_q_filter, const int32_t* d_q_filter_mask, int64_t id_base,
+                                   float* d_out_scores, int64_t* d_out_ids, int64_t* d_total) {
+    if (!idx || !d_queries || !d_min_score || !d_out_scores || !d_out_ids || !d_total) return fail(RASS_ERR_INVALID, "NULL argument");
+    if (int rc = check_nq(nq)) return rc;
+    if (int rc = check_range(idx, max_hits, d_q_filter, d_q_filter_mask)) return rc;
+    rass_engine* eng = idx->eng;
+    std::lock_guard<std::mutex> lk(eng->mu);
+    int rc = set_device(eng);
+    if (rc != RASS_OK) return rc;
+    RangeRequest r;
+    r.queries = d_queries, r.nq = nq, r.min_score = d_min_score, r.max_hits = max_hits;
+    r.q_filter = d_q_filter, r.q_filter_mask = d_q_filter_mask, r.id_base = id_base;
+    r.out_scores = d_out_scores, r.out_ids = d_out_ids, r.total = d_total;
+    return range_device_group(idx, r);
+}
+
+// One attempt of the host range search (one_layout runs it again when a compaction landed meanwhile).  Phase 1: group by
+// group through a pinned slot, as search_ex_once.  Phase 2, with the slot released: the queries whose total exceeds max_hits
+// get the best max_hits matching rows — more than max_hits rows reach the threshold, so those are the plain top max_hits
+// under the query's filter — from the multipass top-k path itself, pinned to the exact scan.
+static int search_range_once(rass_index_t* idx, const float* queries, int nq, const float* min_score, int max_hits,
+                             const int32_t* q_filter, const int32_t* q_filter_mask, float* out_scores, int64_t* out_ids,
+                             int64_t* out_total) {
+    rass_engine* eng = idx->eng;
+    int rc = set_device(eng);
+    if (rc != RASS_OK) return rc;
+    const int dim = idx->dim;
+    {
+        SlotGuard guard(eng);
+        HostSlot* sl = guard.sl;
+        if (!sl->h_range) HIP_TRY(hipHostMalloc(&sl->h_range, range_io_layout(nullptr).bytes, hipHostMallocDefault));
+        const RangeIoView H = range_io_layout(static_cast<unsigned char*>(sl->h_range));
+        for (int done = 0; done < nq;) {
+            const int b = std::min(RASS_MAX_QBATCH, nq - done);
+            const size_t cells = (size_t)b * max_hits;
+            slot_fill(sl, dim, queries + (int64_t)done * dim, q_filter ? q_filter + done : nullptr,
+                      q_filter_mask ? q_filter_mask + done : nullptr, b);
+            memcpy(H.thr, min_score + done, (size_t)b * sizeof(float));
+            {
+                std::lock_guard<std::mutex> lk(eng->mu);   // while enqueuing only, as rass_index_search_ex
+                hipStream_t st = eng->stream;
+                rc = grow_block(&eng->d_range, &eng->range_bytes, range_io_layout(nullptr).bytes, st);
+                if (rc != RASS_OK) return rc;
+                const RangeIoView D = range_io_layout(eng->d_range);
+                rc = slot_upload(eng, sl, dim, q_filter != nullptr, q_filter_mask != nullptr, b);
+                if (rc != RASS_OK) return rc;
+                HIP_TRY(hipMemcpyAsync(D.thr, H.thr, (size_t)b * sizeof(float), hipMemcpyHostToDevice, st));
+                RangeRequest r;
+                r.queries = eng->d_qraw, r.nq = b, r.min_score = D.thr, r.max_hits = max_hits;
+                r.q_filter = q_filter ? eng->d_qfilter : nullptr, r.q_filter_mask = q_filter_mask ? eng->d_qmask : nullptr;
+                r.out_scores = D.out_scores, r.out_ids = D.out_ids, r.total = D.total;
+                rc = range_device_group(idx, r);
+                if (rc != RASS_OK) return rc;
+                HIP_TRY(hipMemcpyAsync(H.total, D.total, (size_t)b * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+                HIP_TRY(hipMemcpyAsync(H.out_scores, D.out_scores, cells * sizeof(float), hipMemcpyDeviceToHost, st));
+                HIP_TRY(hipMemcpyAsync(H.out_ids, D.out_ids, cells * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+                HIP_TRY(hipEventRecord(sl->done, st));
+            }
+            HIP_TRY(hipEventSynchronize(sl->done));
+            memcpy(out_total + done, H.total, (size_t)b * sizeof(int64_t));
+            memcpy(out_scores + (int64_t)done * max_hits, H.out_scores, cells * sizeof(float));
+            memcpy(out_ids + (int64_t)done * max_hits, H.out_ids, cells * sizeof(int64_t));
+            done += b;
+        }
+    }
+    std::vector<int> over;
+    for (int q = 0; q < nq; ++q)
+        if (out_total[q] > max_hits) over.push_back(q);
+    if (over.empty()) return RASS_OK;
+    const int no = (int)over.size();
+    std::vector<float> oq((size_t)no * dim), os((size_t)no * max_hits);
+    std::vector<int32_t> of(q_filter ? no : 0), om(q_filter_mask ? no : 0);
+    std::vector<int64_t> oi((size_t)no * max_hits);
+    for (int j = 0; j < no; ++j) {
+        memcpy(oq.data() + (size_t)j * dim, queries + (int64_t)over[j] * dim, (size_t)dim * sizeof(float));
+        if (q_filter) of[j] = q_filter[over[j]];
+        if (q_filter_mask) om[j] = q_filter_mask[over[j]];
+    }
+    rc = search_ex_once(idx, oq.data(), no, max_hits, q_filter ? of.data() : nullptr, q_filter_mask ? om.data() : nullptr, os.data(),
+                        oi.data(), /*exact=*/true);
+    if (rc != RASS_OK) return rc;
+    for (int j = 0; j < no; ++j) {
+        memcpy(out_scores + (int64_t)over[j] * max_hits, os.data() + (size_t)j * max_hits, (size_t)max_hits * sizeof(float));
+        memcpy(out_ids + (int64_t)over[j] * max_hits, oi.data() + (size_t)j * max_hits, (size_t)max_hits * sizeof(int64_t));
+    }
+    return RASS_OK;
+}
+
+int rass_index_search_range(rass_index_t* idx, const float* queries, int nq, const float* min_score, int max_hits,
+                            const int32_t* q_filter, const int32_t* q_filter_mask, float* out_scores, int64_t* out_ids,
+                            int64_t* out_total) {
+    if (!idx || !out_scores || !out_ids || !out_total) return fail(RASS_ERR_INVALID, "NULL argument");
+    if (nq < 0 || (nq > 0 && (!queries || !min_score))) return fail(RASS_ERR_INVALID, "bad queries / min_score / nq");
+    if (int rc = check_range(idx, max_hits, q_filter, q_filter_mask)) return rc;
+    for (int q = 0; q < nq; ++q)
+        if (min_score[q] != min_score[q]) return fail(RASS_ERR_INVALID, "min_score is NaN");
+    if (nq == 0) return RASS_OK;
+    return one_layout([&] { return idx->layout_epoch.load(std::memory_order_acquire); }, [&] {
+        return search_range_once(idx, queries, nq, min_score, max_hits, q_filter, q_filter_mask, out_scores, out_ids, out_total);
+    });
 }
 
 int rass_index_search(rass_index_t* idx, const float* queries, int nq, int k, const int32_t* q_filter,

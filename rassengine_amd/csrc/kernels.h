@@ -68,7 +68,18 @@ struct ScanArgs {
     // [wgs_per_group][that many][k] at part_* + g * part_group_stride.
     int64_t work_group_stride = 0;
     int nq_total = 0;
+    // Range scan (kRange; range_count != nullptr selects it: flat scans only, no sample floor, no continuation bound, `k`
+    // and part_* unused).  A row that is live and passes query q's filter is a HIT when its score >= range_thr[q] (a NaN
+    // threshold matches nothing).  range_count[q * kRangeCountStride] (zeroed by the caller) ends as the exact number of
+    // hits; the first range_cap of them to arrive are stored, unsorted, at range_hits[q * range_cap + ..] as (score bits,
+    // row of this slab).  launch_range_finish turns that into the answer.
+    const float* range_thr = nullptr;
+    unsigned* range_count = nullptr;
+    uint2* range_hits = nullptr;
+    int range_cap = 0;
 };
+constexpr int kRangeCountStride = 32;   // one 128-byte line per query's counter: every workgroup adds to all of them
+constexpr int kRangeMaxHits = 4096;     // = RASS_MAX_K_MULTIPASS: 4 096 64-bit sort keys are range_finish's 32 KiB of LDS
 
 bool scan_supported_stride(int64_t row_stride);
 hipError_t launch_scan_topk_f32(const ScanArgs& a, int grid, hipStream_t stream);
@@ -96,6 +107,13 @@ hipError_t launch_merge_topk(const float* scores, const int64_t* ids, int n_list
                              const int64_t* id_map = nullptr, int64_t score_list_stride = 0,
                              int64_t id_list_stride = 0, const MergeGroups* groups = nullptr,
                              const int32_t* live_nq = nullptr);   // as ScanArgs::live_nq: 0 = every workgroup exits
+
+// The answer of a range scan, one workgroup per query (merge_topk.hip).  total[q] = count[q].  count <= cap: the emitted pairs
+// sorted (score desc, row asc) into out_scores / out_ids [nq][cap], ids = id_map[row] (ascending with the row) or id_base +
+// row, the slots past the end (-inf, -1).  count > cap: which pairs were stored depended on timing — the whole list is
+// (-inf, -1) and the total says why.
+hipError_t launch_range_finish(const unsigned* count, const uint2* hits, int nq, int cap, int64_t id_base, const int64_t* id_map,
+                               float* out_scores, int64_t* out_ids, int64_t* total, hipStream_t stream);
 
 // ---- bf16 candidate scan + exact re-rank (scan_bf16.hip)
 struct ScanBf16Args {

@@ -12,6 +12,8 @@
 // and folds them into its running best-32 with a 6-stage bitonic merge (running list in
 // lanes 0..31, the new group's best 32 reversed into lanes 32..63).  The 16 per-wave lists
 // meet once in LDS and wave 0 folds them the same way.  k <= 32.
+//
+// range_finish (below): the last step of a score-threshold search, the unsorted hits of a range scan -> the answer.
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -230,6 +232,77 @@ hipError_t launch_merge_topk(const float* scores, const int64_t* ids, int n_list
     }
     hipLaunchKernelGGL(merge_topk_kernel, dim3(nq), dim3(kMergeThreads), 0, stream, scores, ids, n_lists, nq, k,
                        out_scores, out_ids, id_map, score_list_stride, id_list_stride, grp, live_nq);
+    return hipGetLastError();
+}
+
+// ---- range_finish: one workgroup per query of a range scan (scan_topk.hip kRange; kernels.h launch_range_finish).
+// The emitted (score bits, row) pairs become 64-bit keys — the score's order-preserving key in the high word, 0x7fffffff - row
+// in the low one, so that descending key order IS (score desc, row asc) — and are sorted by a bitonic network in LDS, padded
+// with key 0 (below every real key) to the next power of two: 4 096 keys take 32 KiB.  -0.0f is keyed as +0.0f (the two compare
+// equal, so the row decides); the scan's fmaf chains start from +0 and cannot produce it anyway.
+constexpr int kRangeFinishThreads = 1024;
+
+__device__ __forceinline__ unsigned range_score_key(unsigned bits) {
+    if (bits == 0x80000000u) bits = 0u;
+    return (bits & 0x80000000u) ? ~bits : (bits | 0x80000000u);
+}
+
+__global__ __launch_bounds__(kRangeFinishThreads) void range_finish_kernel(const unsigned* __restrict__ count,
+                                                                             const uint2* __restrict__ hits, int cap, int64_t id_base,
+                                                                             const int64_t* __restrict__ id_map,
+                                                                             float* __restrict__ out_scores, int64_t* __restrict__ out_ids,
+                                                                             int64_t* __restrict__ total) {
+    __shared__ unsigned long long keys[kRangeMaxHits];
+    const int q = blockIdx.x, tid = threadIdx.x;
+    const unsigned cnt = count[q * kRangeCountStride];
+    if (tid == 0) total[q] = (int64_t)cnt;
+    float* os = out_scores + (int64_t)q * cap;
+    int64_t* oi = out_ids + (int64_t)q * cap;
+    const int n = cnt > (unsigned)cap ? 0 : (int)cnt;   // overflow: the empty list
+    int n2 = 1;
+    while (n2 < n) n2 <<= 1;
+    const uint2* h = hits + (int64_t)q * cap;
+    for (int i = tid; i < n2; i += kRangeFinishThreads) {
+        unsigned long long key = 0ull;
+        if (i < n) {
+            const uint2 e = h[i];
+            key = ((unsigned long long)range_score_key(e.x) << 32) | (unsigned long long)(0x7fffffffu - e.y);
+        }
+        keys[i] = key;
+    }
+    __syncthreads();
+    for (int size = 2; size <= n2; size <<= 1)
+        for (int stride = size >> 1; stride > 0; stride >>= 1) {
+            for (int i = tid; i < n2; i += kRangeFinishThreads) {
+                const int j = i ^ stride;
+                if (j > i) {
+                    const unsigned long long a = keys[i], b = keys[j];
+                    const bool descending = (i & size) == 0;
+                    if ((a < b) == descending) keys[i] = b, keys[j] = a;
+                }
+            }
+            __syncthreads();
+        }
+    for (int i = tid; i < cap; i += kRangeFinishThreads) {
+        float s = -INFINITY;
+        int64_t id = -1;
+        if (i < n) {
+            const unsigned long long key = keys[i];
+            const unsigned sk = (unsigned)(key >> 32);
+            const int64_t row = (int64_t)(0x7fffffffu - (unsigned)key);
+            s = __uint_as_float((sk & 0x80000000u) ? (sk ^ 0x80000000u) : ~sk);
+            id = id_map ? id_map[row] : id_base + row;
+        }
+        os[i] = s;
+        oi[i] = id;
+    }
+}
+
+hipError_t launch_range_finish(const unsigned* count, const uint2* hits, int nq, int cap, int64_t id_base, const int64_t* id_map,
+                               float* out_scores, int64_t* out_ids, int64_t* total, hipStream_t stream) {
+    if (nq < 1 || cap < 1 || cap > kRangeMaxHits || !count || !hits || !out_scores || !out_ids || !total) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(range_finish_kernel, dim3(nq), dim3(kRangeFinishThreads), 0, stream, count, hits, cap, id_base, id_map,
+                       out_scores, out_ids, total);
     return hipGetLastError();
 }
 

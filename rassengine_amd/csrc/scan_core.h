@@ -52,9 +52,11 @@ struct WorkItem {
 // kIvfGroups: ONE launch walks the probe plans of several launch groups (each its own work list, item count, queries and
 // lists): the fine stage of an IVF batch without a launch boundary — ramp-up, tail, gap — between the groups.
 // kFlatSampleGroups: the sample passes of several launch groups in one launch (a batch call's 32 passes of 20 us each).
-enum ScanMode { kFlat = 0, kIvf = 1, kMulti = 2, kFlatSample = 3, kFlatGroups = 4, kIvfGroups = 5, kFlatSampleGroups = 6 };
+// kRange: a flat scan that RANKS nothing: every row scoring >= the query's threshold is counted and emitted unsorted
+// (emit_range below; ScanArgs::range_*), for the score-threshold search.  No sample pass, no floor, no TopList.
+enum ScanMode { kFlat = 0, kIvf = 1, kMulti = 2, kFlatSample = 3, kFlatGroups = 4, kIvfGroups = 5, kFlatSampleGroups = 6, kRange = 7 };
 constexpr bool mode_is_flat(int mode) {
-    return mode == kFlat || mode == kFlatSample || mode == kFlatGroups || mode == kFlatSampleGroups;
+    return mode == kFlat || mode == kFlatSample || mode == kFlatGroups || mode == kFlatSampleGroups || mode == kRange;
 }
 constexpr bool mode_is_sample(int mode) { return mode == kFlatSample || mode == kFlatSampleGroups; }
 
@@ -218,6 +220,23 @@ __device__ __forceinline__ unsigned score_key(float s) {
 }
 __device__ __forceinline__ float key_score(unsigned k) {
     return __uint_as_float((k & 0x80000000u) ? (k ^ 0x80000000u) : ~k);
+}
+
+// The emission of a range scan (kRange), in the place of insert_candidates: a half-wave holds one query's 32 rows of a tile.
+// One ballot; where a half has hits, its first lane adds their number to the query's counter (one vector atomic per (tile,
+// query) at the most) and every hitting lane stores (score bits, local row) at counter + its rank among the half's hits while
+// that is below `cap`.  The counter runs on past cap: it is the exact total.  Which workgroup lands where depends on timing;
+// range_finish sorts the pairs under a total order, so the answer does not.
+__device__ __forceinline__ void emit_range(bool hit, float s, int row, unsigned* count, uint2* hits, int cap) {
+    const unsigned long long b = __ballot(hit);
+    if (b == 0) return;   // wave-uniform
+    const int lane = lane_id();
+    const unsigned mine = (lane & 32) ? (unsigned)(b >> 32) : (unsigned)b;
+    unsigned base = 0;
+    if ((lane & 31) == 0 && mine != 0) base = atomicAdd(count, (unsigned)__popc(mine));
+    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)base, 0), hi = (unsigned)__builtin_amdgcn_readlane((int)base, 32);
+    const unsigned pos = ((lane & 32) ? hi : lo) + (unsigned)__popc(mine & ((1u << (lane & 31)) - 1u));
+    if (hit && pos < (unsigned)cap) hits[pos] = make_uint2(__float_as_uint(s), (unsigned)row);
 }
 
 // Half-wave sorted list: lanes 0..31 hold query A's best-first top-32, lanes 32..63 query B's.

@@ -362,6 +362,65 @@ class FlatIndex:
                                                                     _np_ptr(m), _np_ptr(out_s), _np_ptr(out_i)))
         return out_s, out_i
 
+    MAX_HITS = N.RASS_MAX_K_MULTIPASS   # search_range: the longest list one call returns
+
+    def search_range(self, queries: np.ndarray, min_score, max_hits: int = 256, q_filter: Optional[np.ndarray] = None,
+                     q_filter_mask: Optional[np.ndarray] = None) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """Score-threshold (radial) search, ``rass_index_search_range``: every live row that passes query q's filter and
+        scores ``>= min_score[q]`` (raw cosine; one float32 per query, or one number for all of them; ``-inf`` allowed, NaN
+        refused).  Returns (scores f32 [nq, max_hits], ids i64 [nq, max_hits], totals i64 [nq]): the matching rows best
+        first, ties by id ascending, (-inf, -1) padding, and the EXACT number of matching rows — where that exceeds
+        ``max_hits`` (<= 4096) the list is the best ``max_hits`` of them.  One corpus pass per 32 queries whatever the
+        number of hits; always the exact fp32 scan (the prefilter mode is ignored); fp32 indices only.  Thread-safe."""
+        q = np.ascontiguousarray(queries, dtype=np.float32)
+        if q.ndim != 2 or q.shape[1] != self.dim:
+            raise ValueError(f"expected [nq, {self.dim}] queries, got {q.shape}")
+        nq = q.shape[0]
+        thr = np.asarray(min_score)
+        if thr.dtype.kind not in "fiu":
+            raise ValueError(f"min_score must be real numbers, not {thr.dtype}")
+        if thr.ndim == 0:
+            thr = np.full(nq, thr)
+        thr = np.ascontiguousarray(thr, dtype=np.float32)
+        if thr.shape != (nq,):
+            raise ValueError("min_score must be one number, or one per query")
+        if np.isnan(thr).any():
+            raise ValueError("min_score must not be NaN")
+        max_hits = int(max_hits)
+        if not 1 <= max_hits <= self.MAX_HITS:
+            raise ValueError(f"max_hits must be in [1, {self.MAX_HITS}], got {max_hits}")
+        f = m = None
+        if q_filter is not None:
+            f = np.ascontiguousarray(q_filter, dtype=np.int32)
+            if f.shape != (nq,):
+                raise ValueError("q_filter must be one int32 per query")
+        if q_filter_mask is not None:
+            if f is None:
+                raise ValueError("q_filter_mask needs q_filter")
+            m = np.ascontiguousarray(q_filter_mask, dtype=np.int32)
+            if m.shape != (nq,):
+                raise ValueError("q_filter_mask must be one int32 per query")
+        out_s = np.empty((nq, max_hits), dtype=np.float32)
+        out_i = np.empty((nq, max_hits), dtype=np.int64)
+        total = np.empty((nq,), dtype=np.int64)
+        N.check("rass_index_search_range",
+                self._L.rass_index_search_range(self._h, _np_ptr(q), nq, _np_ptr(thr), max_hits, _np_ptr(f), _np_ptr(m),
+                                                _np_ptr(out_s), _np_ptr(out_i), _np_ptr(total)))
+        return out_s, out_i, total
+
+    def search_range_device(self, d_queries_ptr: int, nq: int, d_min_score_ptr: int, max_hits: int, d_out_scores_ptr: int,
+                            d_out_ids_ptr: int, d_total_ptr: int, id_base: int = 0, d_q_filter_ptr: int = 0,
+                            d_q_filter_mask_ptr: int = 0) -> None:
+        """Async, device-resident ``search_range`` (``rass_index_search_range_device``); nq <= 32.  A query with more
+        matches than ``max_hits`` gets the EMPTY list and its exact total; a NaN threshold matches nothing."""
+        N.check("rass_index_search_range_device",
+                self._L.rass_index_search_range_device(self._h, ctypes.c_void_p(d_queries_ptr), int(nq),
+                                                       ctypes.c_void_p(d_min_score_ptr), int(max_hits),
+                                                       ctypes.c_void_p(d_q_filter_ptr or 0),
+                                                       ctypes.c_void_p(d_q_filter_mask_ptr or 0), int(id_base),
+                                                       ctypes.c_void_p(d_out_scores_ptr), ctypes.c_void_p(d_out_ids_ptr),
+                                                       ctypes.c_void_p(d_total_ptr)))
+
     def search_device(self, d_queries_ptr: int, nq: int, k: int, d_out_scores_ptr: int, d_out_ids_ptr: int,
                       id_base: int = 0, d_q_filter_ptr: int = 0, d_q_filter_mask_ptr: int = 0) -> None:
         """Async, device-resident variant (multi-GPU path, benchmark); nq <= 32."""

@@ -67,6 +67,18 @@ def _score_out(cos: float, mode: Optional[str] = None) -> float:
     return float(1.0 / (2.0 - float(cos)))  # OpenSearch k-NN cosinesimil: 1 / (1 + (1 - cos))
 
 
+def _cos_of_score(score: float, mode: Optional[str] = None) -> float:
+    """The inverse of ``_score_out``: the cosine a reported score stands for.  OpenSearch scores lie in [1/3, 1]: a bound at
+    or below 0 is below every row (-inf), one above 1 names a cosine no row reaches."""
+    mode = mode or config.RASS_SCORE_MODE
+    score = float(score)
+    if mode == "cosine" or score != score:
+        return score
+    if score <= 0.0:
+        return float("-inf")
+    return 2.0 - 1.0 / score
+
+
 def _term_from_filter(filter_clause: Any, field: str) -> Optional[Any]:
     if isinstance(filter_clause, dict):
         term = filter_clause.get("term")
@@ -142,6 +154,36 @@ class HipIndexer:
         except Exception as e:  # reference: log and return [] (1558-1560)
             logger.error(f"Semantic search error: {e}")
             return []
+
+    def semantic_search_above(self, query_emb: np.ndarray, min_score: float, limit: int = 256,
+                              filter_clause: Optional[Dict] = None, patient_id: Optional[str] = None
+                              ) -> Tuple[List[Tuple[Dict, float]], int]:
+        """The radial form of the k-NN clause (``min_score`` instead of ``k``): every chunk whose score is at least
+        ``min_score`` and how many there are, in one pass over the index (``FlatIndex.search_range``).  ``min_score`` is in
+        the units ``semantic_search`` returns (``RASS_SCORE_MODE``) and is converted to a cosine once.  Returns
+        ``(hits, total)``: ``[(doc_dict, float(score))]`` best first, at most ``limit`` (<= 4096) of them, and the exact
+        number of matching rows, which may exceed ``limit``.  Filters as ``semantic_search``.  An empty embedding or an
+        unindexed patient gives ``([], 0)``; errors raise (this method has no counterpart in the reference to mirror)."""
+        if _empty(query_emb):
+            return [], 0
+        st: Optional[IndexState] = REGISTRY.get(self.index_name, create=False)
+        if st is None:
+            return [], 0
+        prep = self._prepare(st, query_emb, limit, filter_clause, patient_id, None)
+        if prep is None:
+            return [], 0
+        q, limit_eff, (fval, fmask) = prep
+        thr = np.array([_cos_of_score(min_score)], dtype=np.float32)
+        if np.isnan(thr[0]):
+            raise ValueError("min_score must not be NaN")
+        flt = dict(q_filter=np.array([fval], dtype=np.int32), q_filter_mask=np.array([fmask], dtype=np.int32)) if fmask else {}
+        for _ in range(LAYOUT_ATTEMPTS):    # row ids belong to one layout of the index, as in _knn
+            layout = _layout_epoch(st.index)
+            scores, ids, totals = st.index.search_range(q, thr, max_hits=limit_eff, **flt)
+            hits = self._hits(st, scores[0], ids[0], 1.0, None, layout)
+            if hits is not None:
+                return hits, int(totals[0])
+        raise RuntimeError(f"{self.index_name}: the index was compacted during every one of {LAYOUT_ATTEMPTS} searches")
 
     def knn_scores(self, query_emb: np.ndarray, k: int = TOP_K, boost: float = 1.0,
                    filter_clause: Optional[Dict] = None, patient_id: Optional[str] = None,
