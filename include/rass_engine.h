@@ -287,6 +287,43 @@ int rass_index_search_range_device(rass_index_t* idx, const float* d_queries, in
                                    int64_t id_base, float* d_out_scores, int64_t* d_out_ids,
                                    int64_t* d_total);
 
+/* Grouped (COLLAPSED) search: the best row of every group, the k best groups — OpenSearch's `"collapse": {"field": ...}` next to
+ * a k-NN clause.  The group of a row is a bit field of its tag: (tag & group_mask) >> ctz(group_mask); RASS_TAG_PATIENT_MASK
+ * collapses by patient, RASS_TAG_DOCTYPE_MASK by doc type.  Group 0 ("none") is a group like any other, as OpenSearch
+ * collapses missing values together.  ONE corpus pass per launch group answers any k exactly: the flat scan keeps a running
+ * maximum per (query, group) instead of ranking rows, and a select over the n_groups slots of each query finishes it.
+ * A row MATCHES query q exactly as in rass_index_search_ex: it is live and passes q_filter (NULL, exact, or
+ * (tag & q_filter_mask[q]) == q_filter[q]).  Every group with a matching row is REPRESENTED by its best matching row under
+ * (score descending, row ordinal ascending); the answer lists the representatives of the k best groups in that same order:
+ * out_scores / out_ids / out_groups are [nq][k], (-inf, -1, -1) past the end.  Scores are the fp32 values of the flat scan (the
+ * same MFMA chain, the same p0 + ... + p7 sum): bit-identical to what rass_index_search_ex reports for that row.  Ids as
+ * rass_index_search_ex reports them: ordinals, or the caller-assigned ids of rass_index_add_ex.  out_group_total[q] is the
+ * EXACT number of distinct groups with a matching row, whatever k is.
+ * group_mask: non-zero, within 0x7fffffff.  n_groups: the exclusive bound of the group key, 1 .. 1 048 576 (the call keeps
+ * nq x n_groups 8-byte slots on the device, up to 256 MiB, in an engine-owned block grown on demand; RASS_ERR_OOM when it
+ * cannot be had, and nothing has changed).  1 <= k <= RASS_MAX_K_MULTIPASS.  Outside those: RASS_ERR_INVALID.
+ * A live matching row whose group key is >= n_groups is left out of the answer: RASS_ERR_INVALID, named in
+ * rass_last_error(), and the outputs are unspecified.  Any nq (scanned in groups of RASS_MAX_QBATCH).
+ * fp32 indices of every dim the engine takes, wide rows included; a bf16 index answers RASS_ERR_UNSUPPORTED.  The
+ * prefilter mode of the index is ignored: a candidate scan cannot see a group's maximum.  IVF, cross-index batches
+ * (rass_index_search_multi), the sharded multi-GPU front and the 64-query pair kernel of the batch call have no grouped form.
+ * Thread-safety and layout epochs as rass_index_search_range: the engine lock is held while enqueuing only, and the answer
+ * comes from ONE layout of the index. */
+int rass_index_search_grouped(rass_index_t* idx, const float* queries, int nq, int k,
+                              int32_t group_mask, int32_t n_groups,
+                              const int32_t* q_filter, const int32_t* q_filter_mask,
+                              float* out_scores, int64_t* out_ids, int32_t* out_groups,
+                              int64_t* out_group_total);
+/* Device-resident variant: every pointer is device memory, the call is stream-ordered, nothing is synchronised and nothing is
+ * read back; nq <= RASS_MAX_QBATCH.  Ids are id_base + row (ignored on an index with caller-assigned ids, which are
+ * reported), to be paired with the layout epoch read before the call.  *d_status = 1 when a live matching row's group key was
+ * >= n_groups (that row is left out; the other rows' answer is intact), else 0. */
+int rass_index_search_grouped_device(rass_index_t* idx, const float* d_queries, int nq, int k,
+                                     int32_t group_mask, int32_t n_groups,
+                                     const int32_t* d_q_filter, const int32_t* d_q_filter_mask,
+                                     int64_t id_base, float* d_out_scores, int64_t* d_out_ids,
+                                     int32_t* d_out_groups, int64_t* d_group_total, int32_t* d_status);
+
 /* Prefilter mode (SURVEY §8f-4 "bf16 (or int8)"; the reference's own index is approximate, app/main.py:563-572), OFF by
  * default.  `enable` = RASS_PREFILTER_BF16 (1): keep a bf16 copy of the slab, scan IT (half the HBM bytes per pass, bf16
  * MFMA) for the 32 best candidates per query; RASS_PREFILTER_INT8 (2): keep an int8 copy (a quarter of the bytes; per row

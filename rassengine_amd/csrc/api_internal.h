@@ -6,7 +6,7 @@
 //                    stateless wrappers, k-means, peer buffers
 //   api_scan.hip     the tuning switches, the shared launch helpers declared below, and the four flat launch paths
 //   api_search.hip   flat search entry points: one group, the fused batches, the host API with its pinned slots, search_multi,
-//                    the score-threshold (range) search
+//                    the score-threshold (range) search, the grouped (collapsed) search
 //   api_ivf.hip      IVF build, persistence, probe, delta and batch
 //   api_compact.hip  compaction of a flat index, its layout epoch, the stateless wrappers of compact.hip
 //
@@ -186,6 +186,26 @@ struct RangeIoView {
 };
 RangeIoView range_io_layout(unsigned char* base);
 
+// A grouped search's table block (eng->d_group, one launch group): the status word, then one 64-bit slot per (query, group).
+// Status and table are adjacent: one memset zeroes both.  Up to 256 MiB, so it is a block of its own, grown on demand.
+struct GroupView {
+    unsigned* status;              // [1] on a 256-byte line
+    unsigned long long* table;     // [nq][n_groups]
+    size_t total;
+};
+GroupView group_layout(unsigned char* base, int nq, int n_groups);
+
+// The host grouped search's device staging (eng->d_group_io): totals, status and lists out, of one launch group.
+struct GroupIoView {
+    int64_t* total;                // [32]
+    int32_t* status;               // [1]
+    float* out_scores;             // [32][kGroupMaxK]; a call uses [nq][k]
+    int64_t* out_ids;
+    int32_t* out_groups;
+    size_t bytes;
+};
+GroupIoView group_io_layout(unsigned char* base);
+
 // A grow-on-demand device block (eng->d_batch, eng->d_cert, rass_ivf::d_batch): at least `need` bytes afterwards.  Growth
 // waits for the stream first: an earlier call on it may still read the old block.
 int grow_block(unsigned char** block, size_t* bytes, size_t need, hipStream_t st);
@@ -204,6 +224,7 @@ struct HostSlot {
     void* base = nullptr;          // the one hipHostMalloc behind all of the above
     void* h_items = nullptr;       // pinned work list of a cross-index batch (lazily allocated, kMultiMaxItems)
     void* h_range = nullptr;       // pinned image of a RangeIoView: the host range search's group (lazily allocated)
+    void* h_group = nullptr;       // pinned image of a GroupIoView: the host grouped search's group (lazily allocated)
     hipEvent_t done = nullptr;
     bool busy = false;
 };
@@ -231,6 +252,12 @@ struct rass_engine {
     // device staging of the host range search (RangeIoView), allocated by its first call
     unsigned char* d_range = nullptr;
     size_t range_bytes = 0;
+    // the grouped search: its table block (GroupView, grown on demand, up to 256 MiB) and the host variant's device staging
+    // (GroupIoView); both used under mu and in stream order, like d_scratch
+    unsigned char* d_group = nullptr;
+    size_t group_bytes = 0;
+    unsigned char* d_group_io = nullptr;
+    size_t group_io_bytes = 0;
     // host-API staging
     float* d_qraw = nullptr;        // [32][dim]
     int32_t* d_qfilter = nullptr;   // [32]

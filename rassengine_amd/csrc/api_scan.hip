@@ -169,6 +169,27 @@ RangeIoView range_io_layout(unsigned char* base) {
     return L;
 }
 
+GroupView group_layout(unsigned char* base, int nq, int n_groups) {
+    Carver c{base};
+    GroupView L;
+    L.status = c.take<unsigned>(sizeof(unsigned));
+    L.table = c.take<unsigned long long>((size_t)nq * n_groups * sizeof(unsigned long long));
+    L.total = c.off;
+    return L;
+}
+
+GroupIoView group_io_layout(unsigned char* base) {
+    Carver c{base};
+    GroupIoView L;
+    L.total = c.take<int64_t>(RASS_MAX_QBATCH * sizeof(int64_t));
+    L.status = c.take<int32_t>(sizeof(int32_t));
+    L.out_scores = c.take<float>((size_t)RASS_MAX_QBATCH * rass::kGroupMaxK * sizeof(float));
+    L.out_ids = c.take<int64_t>((size_t)RASS_MAX_QBATCH * rass::kGroupMaxK * sizeof(int64_t));
+    L.out_groups = c.take<int32_t>((size_t)RASS_MAX_QBATCH * rass::kGroupMaxK * sizeof(int32_t));
+    L.bytes = c.off;
+    return L;
+}
+
 int grow_block(unsigned char** block, size_t* bytes, size_t need, hipStream_t st) {
     if (*bytes >= need) return RASS_OK;
     HIP_TRY(hipStreamSynchronize(st));   // growth only: the block may still be read by an earlier call

@@ -1,7 +1,8 @@
 // api_search.hip — the C ABI of include/rass_engine.h: searching a flat index.  The dispatch of one launch group
 // to its launch path (api_scan.hip), the two fused batches (fp32 and prefilter), the device entry points and the
 // candidates hooks, the host search API with its pinned slots (k > 32 in passes), the cross-index batch
-// rass_index_search_multi, and the score-threshold search rass_index_search_range(_device).  Host-side C++ only.  The objects and the threading rules: api_internal.h.
+// rass_index_search_multi, the score-threshold search rass_index_search_range(_device) and the grouped (collapsed) search
+// rass_index_search_grouped(_device).  Host-side C++ only.  The objects and the threading rules: api_internal.h.
 
 #include "api_internal.h"
 
@@ -332,6 +333,102 @@ int check_range(const rass_index* idx, int max_hits, const int32_t* q_filter, co
     if (max_hits < 1 || max_hits > RASS_MAX_K_MULTIPASS) return fail(RASS_ERR_INVALID, "max_hits must be in [1, RASS_MAX_K_MULTIPASS]");
     if (q_filter_mask && !q_filter) return fail(RASS_ERR_INVALID, "q_filter_mask without q_filter");
     if (idx->dtype != RASS_F32) return fail(RASS_ERR_UNSUPPORTED, "range search needs an fp32 index");
+    return RASS_OK;
+}
+
+// One launch group (<= 32 queries) of a grouped search: normalise -> zero the status word and the table -> the group-max
+// scan (two launches for 17..32 queries on wide rows) -> group_select.  Always the exact fp32 scan: the prefilter mode of
+// the index is not looked at.  Everything is a device pointer; the caller holds eng->mu, has set the device and has checked
+// the arguments.
+struct GroupRequest {
+    const float* queries = nullptr;     // [nq][dim]
+    int nq = 0;
+    int k = 0;
+    int32_t group_mask = 0;
+    int32_t n_groups = 0;
+    const int32_t* q_filter = nullptr;
+    const int32_t* q_filter_mask = nullptr;
+    int64_t id_base = 0;
+    float* out_scores = nullptr;        // [nq][k]
+    int64_t* out_ids = nullptr;
+    int32_t* out_groups = nullptr;
+    int64_t* total = nullptr;           // [nq]
+    int32_t* status = nullptr;          // [1]
+};
+
+// The table block at least `need` bytes.  The new block is allocated BEFORE the old one is let go: a failure leaves the engine
+// as it was.  Growth waits for the stream first: an earlier call on it may still use the old block.
+int grow_group_table(rass_engine* eng, size_t need, hipStream_t st) {
+    if (eng->group_bytes >= need) return RASS_OK;
+    unsigned char* block = nullptr;
+    if (hipMalloc(reinterpret_cast<void**>(&block), need) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(RASS_ERR_OOM, "grouped search: hipMalloc of the group table (" + std::to_string(need) + " bytes) failed");
+    }
+    const int rc = HIP_RC(hipStreamSynchronize(st));
+    if (rc != RASS_OK) {
+        (void)hipFree(block);
+        return rc;
+    }
+    if (eng->d_group) (void)hipFree(eng->d_group);
+    eng->d_group = block;
+    eng->group_bytes = need;
+    return RASS_OK;
+}
+
+int group_device_group(rass_index* idx, const GroupRequest& r) {
+    rass_engine* eng = idx->eng;
+    hipStream_t st = eng->stream;
+    const int nq = r.nq;
+    const IndexView iv = index_view(idx, /*filtered=*/true, r.id_base);   // the group key is in the tag: always read them
+    const int64_t stride = idx->stride;
+    if (iv.rows < 0 || iv.rows > 0x7fffffc0LL) return fail(RASS_ERR_INVALID, "n_rows out of range for one scan");
+    if (!rass::scan_supported_stride(stride) || stride > kMaxStride) return fail(RASS_ERR_UNSUPPORTED, kStrideMsg);
+    if (range_layout(nullptr).total > eng->scratch_bytes) return fail(RASS_ERR_INVALID, "scan workspace too small");
+    if (int rc = grow_group_table(eng, group_layout(nullptr, nq, r.n_groups).total, st)) return rc;
+    const GroupView G = group_layout(eng->d_group, nq, r.n_groups);
+    float* q_padded = range_layout(eng->d_scratch).q_padded;   // where every scan keeps its queries
+    HIP_TRY(rass::launch_normalize_rows_f32(r.queries, idx->dim, q_padded, stride, nq, idx->dim, st, pad_nq(nq)));
+    HIP_TRY(hipMemsetAsync(G.status, 0, G.total, st));
+    const int grid = scan_grid((iv.rows + 31) / 32, 1, eng->n_cus);
+    // wide rows: 16 queries per launch, as for the top-k scan (scan_launch)
+    const int per_launch = stride > kNarrowStride ? 16 : RASS_MAX_QBATCH;
+    for (int q0 = 0; q0 < nq && iv.rows > 0; q0 += per_launch) {
+        rass::ScanArgs a;
+        a.corpus = iv.corpus;
+        a.row_tag = iv.row_tag;
+        a.q_padded = q_padded + (int64_t)q0 * stride;
+        a.q_filter = r.q_filter ? r.q_filter + q0 : nullptr;
+        a.q_filter_mask = r.q_filter_mask ? r.q_filter_mask + q0 : nullptr;
+        a.part_scores = nullptr;
+        a.part_ids = nullptr;
+        a.row_stride = stride;
+        a.id_base = 0;   // the keys name rows of the slab: group_select translates them
+        a.n_rows = (int)iv.rows;
+        a.nq = std::min(per_launch, nq - q0);
+        a.k = 1;
+        a.xcd_skew = scan_xcd_skew(a.nq, grid, eng->n_cus);
+        a.group_table = G.table + (int64_t)q0 * r.n_groups;
+        a.group_status = G.status;
+        a.group_mask = r.group_mask;
+        a.group_shift = __builtin_ctz((unsigned)r.group_mask);
+        a.group_n = r.n_groups;
+        const int rc = timed_launch(eng, st, [&] { return HIP_RC(rass::launch_scan_topk_f32(a, grid, st)); });
+        if (rc != RASS_OK) return rc;
+    }
+    HIP_TRY(rass::launch_group_select(G.table, nq, r.n_groups, r.k, iv.id_base, iv.id_map, r.out_scores, r.out_ids, r.out_groups,
+                                      r.total, G.status, r.status, st));
+    return RASS_OK;
+}
+
+// The argument checks the two grouped entry points share.
+int check_grouped(const rass_index* idx, int k, int32_t group_mask, int32_t n_groups, const int32_t* q_filter,
+                  const int32_t* q_filter_mask) {
+    if (k < 1 || k > RASS_MAX_K_MULTIPASS) return fail(RASS_ERR_INVALID, "k must be in [1, RASS_MAX_K_MULTIPASS]");
+    if (group_mask <= 0) return fail(RASS_ERR_INVALID, "group_mask must be non-zero and within 0x7fffffff");
+    if (n_groups < 1 || n_groups > rass::kGroupMaxGroups) return fail(RASS_ERR_INVALID, "n_groups must be in [1, 1048576]");
+    if (q_filter_mask && !q_filter) return fail(RASS_ERR_INVALID, "q_filter_mask without q_filter");
+    if (idx->dtype != RASS_F32) return fail(RASS_ERR_UNSUPPORTED, "grouped search needs an fp32 index");
     return RASS_OK;
 }
 
@@ -777,6 +874,89 @@ int rass_index_search_range(rass_index_t* idx, const float* queries, int nq, con
     if (nq == 0) return RASS_OK;
     return one_layout([&] { return idx->layout_epoch.load(std::memory_order_acquire); }, [&] {
         return search_range_once(idx, queries, nq, min_score, max_hits, q_filter, q_filter_mask, out_scores, out_ids, out_total);
+    });
+}
+
+int rass_index_search_grouped_device(rass_index_t* idx, const float* d_queries, int nq, int k, int32_t group_mask, int32_t n_groups,
+                                     const int32_t* d_q_filter, const int32_t* d_q_filter_mask, int64_t id_base,
+                                     float* d_out_scores, int64_t* d_out_ids, int32_t* d_out_groups, int64_t* d_group_total,
+                                     int32_t* d_status) {
+    if (!idx || !d_queries || !d_out_scores || !d_out_ids || !d_out_groups || !d_group_total || !d_status)
+        return fail(RASS_ERR_INVALID, "NULL argument");
+    if (int rc = check_nq(nq)) return rc;
+    if (int rc = check_grouped(idx, k, group_mask, n_groups, d_q_filter, d_q_filter_mask)) return rc;
+    rass_engine* eng = idx->eng;
+    std::lock_guard<std::mutex> lk(eng->mu);
+    int rc = set_device(eng);
+    if (rc != RASS_OK) return rc;
+    GroupRequest r;
+    r.queries = d_queries, r.nq = nq, r.k = k, r.group_mask = group_mask, r.n_groups = n_groups;
+    r.q_filter = d_q_filter, r.q_filter_mask = d_q_filter_mask, r.id_base = id_base;
+    r.out_scores = d_out_scores, r.out_ids = d_out_ids, r.out_groups = d_out_groups, r.total = d_group_total, r.status = d_status;
+    return group_device_group(idx, r);
+}
+
+// One attempt of the host grouped search (one_layout runs it again when a compaction landed meanwhile): group by group
+// through a pinned slot, as search_range_once.  A group whose scan met a group key >= n_groups ends the call.
+static int search_grouped_once(rass_index_t* idx, const float* queries, int nq, int k, int32_t group_mask, int32_t n_groups,
+                               const int32_t* q_filter, const int32_t* q_filter_mask, float* out_scores, int64_t* out_ids,
+                               int32_t* out_groups, int64_t* out_total) {
+    rass_engine* eng = idx->eng;
+    int rc = set_device(eng);
+    if (rc != RASS_OK) return rc;
+    const int dim = idx->dim;
+    SlotGuard guard(eng);
+    HostSlot* sl = guard.sl;
+    if (!sl->h_group) HIP_TRY(hipHostMalloc(&sl->h_group, group_io_layout(nullptr).bytes, hipHostMallocDefault));
+    const GroupIoView H = group_io_layout(static_cast<unsigned char*>(sl->h_group));
+    for (int done = 0; done < nq;) {
+        const int b = std::min(RASS_MAX_QBATCH, nq - done);
+        const size_t cells = (size_t)b * k;
+        slot_fill(sl, dim, queries + (int64_t)done * dim, q_filter ? q_filter + done : nullptr,
+                  q_filter_mask ? q_filter_mask + done : nullptr, b);
+        {
+            std::lock_guard<std::mutex> lk(eng->mu);   // while enqueuing only, as rass_index_search_ex
+            hipStream_t st = eng->stream;
+            rc = grow_block(&eng->d_group_io, &eng->group_io_bytes, group_io_layout(nullptr).bytes, st);
+            if (rc != RASS_OK) return rc;
+            const GroupIoView D = group_io_layout(eng->d_group_io);
+            rc = slot_upload(eng, sl, dim, q_filter != nullptr, q_filter_mask != nullptr, b);
+            if (rc != RASS_OK) return rc;
+            GroupRequest r;
+            r.queries = eng->d_qraw, r.nq = b, r.k = k, r.group_mask = group_mask, r.n_groups = n_groups;
+            r.q_filter = q_filter ? eng->d_qfilter : nullptr, r.q_filter_mask = q_filter_mask ? eng->d_qmask : nullptr;
+            r.out_scores = D.out_scores, r.out_ids = D.out_ids, r.out_groups = D.out_groups, r.total = D.total, r.status = D.status;
+            rc = group_device_group(idx, r);
+            if (rc != RASS_OK) return rc;
+            HIP_TRY(hipMemcpyAsync(H.total, D.total, (size_t)b * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipMemcpyAsync(H.status, D.status, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipMemcpyAsync(H.out_scores, D.out_scores, cells * sizeof(float), hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipMemcpyAsync(H.out_ids, D.out_ids, cells * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipMemcpyAsync(H.out_groups, D.out_groups, cells * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipEventRecord(sl->done, st));
+        }
+        HIP_TRY(hipEventSynchronize(sl->done));
+        if (*H.status != 0)
+            return fail(RASS_ERR_INVALID, "grouped search: a matching row's group key is >= n_groups (" + std::to_string(n_groups) + ")");
+        memcpy(out_total + done, H.total, (size_t)b * sizeof(int64_t));
+        memcpy(out_scores + (int64_t)done * k, H.out_scores, cells * sizeof(float));
+        memcpy(out_ids + (int64_t)done * k, H.out_ids, cells * sizeof(int64_t));
+        memcpy(out_groups + (int64_t)done * k, H.out_groups, cells * sizeof(int32_t));
+        done += b;
+    }
+    return RASS_OK;
+}
+
+int rass_index_search_grouped(rass_index_t* idx, const float* queries, int nq, int k, int32_t group_mask, int32_t n_groups,
+                              const int32_t* q_filter, const int32_t* q_filter_mask, float* out_scores, int64_t* out_ids,
+                              int32_t* out_groups, int64_t* out_group_total) {
+    if (!idx || !out_scores || !out_ids || !out_groups || !out_group_total) return fail(RASS_ERR_INVALID, "NULL argument");
+    if (nq < 0 || (nq > 0 && !queries)) return fail(RASS_ERR_INVALID, "bad queries / nq");
+    if (int rc = check_grouped(idx, k, group_mask, n_groups, q_filter, q_filter_mask)) return rc;
+    if (nq == 0) return RASS_OK;
+    return one_layout([&] { return idx->layout_epoch.load(std::memory_order_acquire); }, [&] {
+        return search_grouped_once(idx, queries, nq, k, group_mask, n_groups, q_filter, q_filter_mask, out_scores, out_ids, out_groups,
+                                   out_group_total);
     });
 }
 

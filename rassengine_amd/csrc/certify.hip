@@ -18,11 +18,6 @@ namespace rass {
 
 constexpr int kSelThreads = 1024;
 
-// key of a candidate: larger = ranks first under (score desc, row asc); 0 = none
-__device__ __forceinline__ uint64_t cand_key(float s, int32_t row) {
-    return ((uint64_t)score_key(s) << 32) | (uint64_t)(0xffffffffu - (uint32_t)row);
-}
-
 __global__ __launch_bounds__(kSelThreads) void cert_select_kernel(const float* __restrict__ list_s, const int32_t* __restrict__ list_r,
                                                                   const int32_t* __restrict__ list_n, const float* __restrict__ list_floor,
                                                                   int grid, int nq, int64_t* __restrict__ cand_rows,

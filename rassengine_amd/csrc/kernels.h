@@ -77,6 +77,15 @@ struct ScanArgs {
     unsigned* range_count = nullptr;
     uint2* range_hits = nullptr;
     int range_cap = 0;
+    // Group-max scan (kGroupMax; group_table != nullptr selects it: flat scans only, no sample floor, no continuation bound,
+    // `k` and part_* unused).  The group key of a row is (tag & group_mask) >> group_shift.  A row that is live and passes
+    // query q's filter is folded into group_table[q * group_n + key] (zeroed by the caller; row_tag must not be null): the
+    // slot ends as the largest candidate key (scan_core.h cand_key: score desc, row asc) of the group's matching rows, 0 =
+    // none.  A matching row with key >= group_n is left out and sets *group_status (zeroed by the caller) to 1.
+    // launch_group_select turns the table into the answer.
+    unsigned long long* group_table = nullptr;
+    unsigned* group_status = nullptr;
+    int group_mask = 0, group_shift = 0, group_n = 0;
 };
 constexpr int kRangeCountStride = 32;   // one 128-byte line per query's counter: every workgroup adds to all of them
 constexpr int kRangeMaxHits = 4096;     // = RASS_MAX_K_MULTIPASS: 4 096 64-bit sort keys are range_finish's 32 KiB of LDS
@@ -114,6 +123,17 @@ hipError_t launch_merge_topk(const float* scores, const int64_t* ids, int n_list
 // (-inf, -1) and the total says why.
 hipError_t launch_range_finish(const unsigned* count, const uint2* hits, int nq, int cap, int64_t id_base, const int64_t* id_map,
                                float* out_scores, int64_t* out_ids, int64_t* total, hipStream_t stream);
+
+// The answer of a group-max scan, one workgroup per query (group_topk.hip).  table [nq][n_groups] holds each group's best
+// candidate key (0 = no matching row).  total[q] = the number of non-zero slots.  The k largest keys (all of them where
+// total <= k), best first: out_scores / out_ids / out_groups [nq][k] = the key's score, id_map[row] (ascending with the row)
+// or id_base + row, and the slot index; (-inf, -1, -1) past the end.  1 <= k <= kGroupMaxK.  *out_status = the scan's status
+// word (ScanArgs::group_status) as 0 / 1.
+constexpr int kGroupMaxK = 4096;          // = RASS_MAX_K_MULTIPASS: the selected keys and their slots are 48 KiB of LDS
+constexpr int kGroupMaxGroups = 1 << 20;  // the exclusive bound of a group key: a 32-query table is 256 MiB
+hipError_t launch_group_select(const unsigned long long* table, int nq, int n_groups, int k, int64_t id_base, const int64_t* id_map,
+                               float* out_scores, int64_t* out_ids, int32_t* out_groups, int64_t* total, const unsigned* status,
+                               int32_t* out_status, hipStream_t stream);
 
 // ---- bf16 candidate scan + exact re-rank (scan_bf16.hip)
 struct ScanBf16Args {

@@ -54,9 +54,13 @@ struct WorkItem {
 // kFlatSampleGroups: the sample passes of several launch groups in one launch (a batch call's 32 passes of 20 us each).
 // kRange: a flat scan that RANKS nothing: every row scoring >= the query's threshold is counted and emitted unsorted
 // (emit_range below; ScanArgs::range_*), for the score-threshold search.  No sample pass, no floor, no TopList.
-enum ScanMode { kFlat = 0, kIvf = 1, kMulti = 2, kFlatSample = 3, kFlatGroups = 4, kIvfGroups = 5, kFlatSampleGroups = 6, kRange = 7 };
+// kGroupMax: a flat scan that ranks nothing either: every matching row is folded into the running maximum of its (query,
+// group) slot (emit_group_max below; ScanArgs::group_*), for the grouped (collapsed) search.  No sample pass, no floor, no TopList.
+enum ScanMode { kFlat = 0, kIvf = 1, kMulti = 2, kFlatSample = 3, kFlatGroups = 4, kIvfGroups = 5, kFlatSampleGroups = 6, kRange = 7,
+                kGroupMax = 8 };
 constexpr bool mode_is_flat(int mode) {
-    return mode == kFlat || mode == kFlatSample || mode == kFlatGroups || mode == kFlatSampleGroups || mode == kRange;
+    return mode == kFlat || mode == kFlatSample || mode == kFlatGroups || mode == kFlatSampleGroups || mode == kRange ||
+           mode == kGroupMax;
 }
 constexpr bool mode_is_sample(int mode) { return mode == kFlatSample || mode == kFlatSampleGroups; }
 
@@ -237,6 +241,32 @@ __device__ __forceinline__ void emit_range(bool hit, float s, int row, unsigned*
     const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)base, 0), hi = (unsigned)__builtin_amdgcn_readlane((int)base, 32);
     const unsigned pos = ((lane & 32) ? hi : lo) + (unsigned)__popc(mine & ((1u << (lane & 31)) - 1u));
     if (hit && pos < (unsigned)cap) hits[pos] = make_uint2(__float_as_uint(s), (unsigned)row);
+}
+
+// Key of a candidate (score, row): larger = ranks first under (score desc, row asc); 0 = none (a finite score's key is
+// >= 0x00800000 and -inf's is 0x007fffff).  -0.0f would rank below +0.0f, but the scan's fmaf chains start from +0 and
+// cannot produce it.
+__device__ __forceinline__ uint64_t cand_key(float s, int32_t row) {
+    return ((uint64_t)score_key(s) << 32) | (uint64_t)(0xffffffffu - (uint32_t)row);
+}
+
+// The emission of a group-max scan (kGroupMax), in the place of insert_candidates: a lane holds one (row, query) score.
+// The row's group key comes from its tag; the lane's candidate key is folded into slot[g] of its query's table row
+// (`table_q`, zeroed by the caller) by a 64-bit atomicMax, which a relaxed device-scope pre-read of the slot skips where
+// the key cannot raise it.  A slot only grows, so a stale pre-read costs an extra atomic and never an answer: the table is
+// the per-(query, group) maximum of the keys whatever order the workgroups ran in.  A matching row whose group key is
+// >= n_groups is left out and sets *status.  Plain vector loads, stores and atomics.
+__device__ __forceinline__ void emit_group_max(bool ok, float s, int row, int tag, int group_mask, int group_shift, int n_groups,
+                                               unsigned long long* table_q, unsigned* status) {
+    const unsigned g = (unsigned)(tag & group_mask) >> group_shift;
+    if (!ok) return;
+    if (g >= (unsigned)n_groups) {
+        __hip_atomic_store(status, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        return;
+    }
+    const unsigned long long key = cand_key(s, row);
+    unsigned long long* slot = table_q + g;
+    if (key > __hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(slot, key);
 }
 
 // Half-wave sorted list: lanes 0..31 hold query A's best-first top-32, lanes 32..63 query B's.

@@ -294,6 +294,11 @@ __global__ __launch_bounds__(kThreads, 2) void scan_topk_f32_kernel(ScanArgs p) 
                        p.range_cap);
             return;
         }
+        if (MODE == kGroupMax) {   // no ranking either: the row's key goes into its (query, group) slot
+            emit_group_max(ok && q < p.nq, s, row, tag, p.group_mask, p.group_shift, p.group_n,
+                           p.group_table + (int64_t)q * p.group_n, p.group_status);
+            return;
+        }
         // the sample floor: k rows of the corpus already score >= floor_q, so a row below it cannot be in the
         // query's top-k (ties are kept: the id order decides them in the merge)
         const float floor_q = MODE == kFlat ? sh_floor[q] : -INFINITY;
@@ -381,7 +386,7 @@ __global__ __launch_bounds__(kThreads, 2) void scan_topk_f32_kernel(ScanArgs p) 
     if (threadIdx.x == 0) g_scan_clocks[2 * blockIdx.x + 1] = wall_clock64();
     if (threadIdx.x == 0 && blockIdx.x == 0) g_scan_core[1] = clock64();
 #endif
-    if (MODE == kRange) return;   // everything was emitted on the way
+    if (MODE == kRange || MODE == kGroupMax) return;   // everything was emitted on the way
     if (mode_is_sample(MODE)) {
         // The sample pass: this workgroup's best score per query -> part_scores[32][kMaxSampleGroups] (-inf: no row of the
         // sample passed the query's filters); the big scan's waves take the k-th largest over the workgroups.
@@ -627,8 +632,9 @@ __device__ __forceinline__ void wide_panels(TileRegs<CHP>& R0, TileRegs<CHP>& R1
     }
 }
 
-template <int CHP, int P, bool EXT, bool RANGE>
+template <int CHP, int P, bool EXT, bool RANGE, bool GROUP>
 __global__ __launch_bounds__(kThreads, 2) void scan_topk_f32_wide_kernel(ScanArgs p) {
+    static_assert(!(RANGE && GROUP), "one emission per kernel");
     static_assert(P == 2 || P == 4, "R0 holds the even panels, R1 the odd ones");
     constexpr int NQ = 16, CHT = P * CHP;
     extern __shared__ __attribute__((aligned(16))) float lds[];  // [4][kWaves][NQ][kPitch]
@@ -713,6 +719,11 @@ __global__ __launch_bounds__(kThreads, 2) void scan_topk_f32_wide_kernel(ScanArg
                        p.range_cap);
             return;
         }
+        if (GROUP) {   // the emission of scan_topk_f32_kernel's kGroupMax mode
+            emit_group_max(ok && q < p.nq, s, row, tag, p.group_mask, p.group_shift, p.group_n,
+                           p.group_table + (int64_t)q * p.group_n, p.group_status);
+            return;
+        }
         s = ok ? s : -INFINITY;
         insert_candidates(L, tau, s, row, p.k);
     };
@@ -744,7 +755,7 @@ __global__ __launch_bounds__(kThreads, 2) void scan_topk_f32_wide_kernel(ScanArg
     }
     rank_tile(Pa, pair ^ 2);
     rank_tile(Pb, (pair ^ 2) + 1);
-    if (RANGE) return;
+    if (RANGE || GROUP) return;
 
     const int lpos = lane & 31;
     const int q = (lane >> 5) * 8 + wid;
@@ -756,27 +767,27 @@ __global__ __launch_bounds__(kThreads, 2) void scan_topk_f32_wide_kernel(ScanArg
     }
 }
 
-template <int CHP, int P, bool EXT, bool RANGE>
+template <int CHP, int P, bool EXT, bool RANGE, bool GROUP>
 static hipError_t launch_wide_variant(const ScanArgs& a, int grid, hipStream_t stream) {
     constexpr size_t lds_bytes = (size_t)4 * kWaves * 16 * kPitch * sizeof(float);  // 72 KiB
     static bool attr_set = false;
     if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&scan_topk_f32_wide_kernel<CHP, P, EXT, RANGE>),
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&scan_topk_f32_wide_kernel<CHP, P, EXT, RANGE, GROUP>),
                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
         if (e != hipSuccess) return e;
         attr_set = true;
     }
-    hipLaunchKernelGGL((scan_topk_f32_wide_kernel<CHP, P, EXT, RANGE>), dim3(grid), dim3(kThreads), lds_bytes, stream, a);
+    hipLaunchKernelGGL((scan_topk_f32_wide_kernel<CHP, P, EXT, RANGE, GROUP>), dim3(grid), dim3(kThreads), lds_bytes, stream, a);
     return hipGetLastError();
 }
 
-template <bool EXT, bool RANGE = false>
+template <bool EXT, bool RANGE = false, bool GROUP = false>
 static hipError_t launch_wide(int ch_total, const ScanArgs& a, int grid, hipStream_t stream) {
     switch (ch_total) {
-        case 10: return launch_wide_variant<5, 2, EXT, RANGE>(a, grid, stream);
-        case 12: return launch_wide_variant<6, 2, EXT, RANGE>(a, grid, stream);
-        case 14: return launch_wide_variant<7, 2, EXT, RANGE>(a, grid, stream);
-        case 16: return launch_wide_variant<4, 4, EXT, RANGE>(a, grid, stream);   // 2 x 8 chunks spill (256 VGPRs at 2 waves per SIMD)
+        case 10: return launch_wide_variant<5, 2, EXT, RANGE, GROUP>(a, grid, stream);
+        case 12: return launch_wide_variant<6, 2, EXT, RANGE, GROUP>(a, grid, stream);
+        case 14: return launch_wide_variant<7, 2, EXT, RANGE, GROUP>(a, grid, stream);
+        case 16: return launch_wide_variant<4, 4, EXT, RANGE, GROUP>(a, grid, stream);   // 2 x 8 chunks spill (256 VGPRs at 2 waves per SIMD)
         default: return hipErrorInvalidValue;
     }
 }
@@ -870,6 +881,21 @@ hipError_t launch_scan_topk_f32(const ScanArgs& a, int grid, hipStream_t stream)
         }
         if (a.nq <= 16) return ext ? launch_ch<1, kRange, true>(ch, a, grid, stream) : launch_ch<1, kRange>(ch, a, grid, stream);
         return ext ? launch_ch<2, kRange, true>(ch, a, grid, stream) : launch_ch<2, kRange>(ch, a, grid, stream);
+    }
+    if (a.group_table != nullptr) {  // the group-max scan: flat, every stride, plain or masked filters, nothing else
+        if (!a.group_status || !a.row_tag || a.group_mask <= 0 || a.group_n < 1 || a.group_n > kGroupMaxGroups || a.nq < 1 || a.nq > 32)
+            return hipErrorInvalidValue;
+        if (a.group_shift != __builtin_ctz((unsigned)a.group_mask)) return hipErrorInvalidValue;
+        if (a.q_after_score || a.q_after_id || a.work_tile || a.work_base || a.sample_pass || a.sample_best || a.wgs_per_group ||
+            a.live_nq)
+            return hipErrorInvalidValue;
+        if (a.q_filter_mask != nullptr && a.q_filter == nullptr) return hipErrorInvalidValue;
+        if (ch > 8) {
+            if (a.nq > 16) return hipErrorInvalidValue;   // the caller splits larger groups, as for the top-k scan
+            return ext ? launch_wide<true, false, true>(ch, a, grid, stream) : launch_wide<false, false, true>(ch, a, grid, stream);
+        }
+        if (a.nq <= 16) return ext ? launch_ch<1, kGroupMax, true>(ch, a, grid, stream) : launch_ch<1, kGroupMax>(ch, a, grid, stream);
+        return ext ? launch_ch<2, kGroupMax, true>(ch, a, grid, stream) : launch_ch<2, kGroupMax>(ch, a, grid, stream);
     }
     if (a.wgs_per_group > 0 && (ext || ch > 8 || a.work_base)) return hipErrorInvalidValue;
     if (a.wgs_per_group > 0 && a.work_tile != nullptr) {  // the fine scans of several IVF launch groups in one launch

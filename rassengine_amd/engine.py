@@ -421,6 +421,69 @@ class FlatIndex:
                                                        ctypes.c_void_p(d_out_scores_ptr), ctypes.c_void_p(d_out_ids_ptr),
                                                        ctypes.c_void_p(d_total_ptr)))
 
+    MAX_GROUPS = 1 << 20                # search_grouped: the exclusive bound of a group key
+
+    @staticmethod
+    def _check_grouped(k, group_mask, n_groups) -> Tuple[int, int, int]:
+        k, group_mask, n_groups = int(k), int(group_mask), int(n_groups)
+        if not 1 <= k <= N.RASS_MAX_K_MULTIPASS:
+            raise ValueError(f"k must be in [1, {N.RASS_MAX_K_MULTIPASS}], got {k}")
+        if not 1 <= group_mask <= 0x7FFFFFFF:
+            raise ValueError(f"group_mask must be non-zero and within 0x7fffffff, got {group_mask:#x}")
+        if not 1 <= n_groups <= FlatIndex.MAX_GROUPS:
+            raise ValueError(f"n_groups must be in [1, {FlatIndex.MAX_GROUPS}], got {n_groups}")
+        return k, group_mask, n_groups
+
+    def search_grouped(self, queries: np.ndarray, k: int, group_mask: int, n_groups: int, q_filter: Optional[np.ndarray] = None,
+                       q_filter_mask: Optional[np.ndarray] = None
+                       ) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+        """Grouped (collapsed) search, ``rass_index_search_grouped``: the group of a row is
+        ``(tag & group_mask) >> ctz(group_mask)`` (``RASS_TAG_PATIENT_MASK``: by patient, ``RASS_TAG_DOCTYPE_MASK``: by doc
+        type; group 0 is a group like any other), ``n_groups`` the exclusive bound of that key (<= 1 048 576).  Every group
+        with a live row passing query q's filter is represented by its best such row (score desc, row asc).  Returns
+        (scores f32 [nq, k], ids i64 [nq, k], groups i32 [nq, k], totals i64 [nq]): the representatives of the k best
+        groups, best first, (-inf, -1, -1) padding, and the EXACT number of distinct groups with a matching row.  One corpus
+        pass per 32 queries whatever k (<= 4096) is; always the exact fp32 scan (the prefilter mode is ignored); fp32
+        indices only.  A matching row whose group key is >= ``n_groups`` makes the call fail.  Thread-safe."""
+        q = np.ascontiguousarray(queries, dtype=np.float32)
+        if q.ndim != 2 or q.shape[1] != self.dim:
+            raise ValueError(f"expected [nq, {self.dim}] queries, got {q.shape}")
+        nq = q.shape[0]
+        k, group_mask, n_groups = self._check_grouped(k, group_mask, n_groups)
+        f = m = None
+        if q_filter is not None:
+            f = np.ascontiguousarray(q_filter, dtype=np.int32)
+            if f.shape != (nq,):
+                raise ValueError("q_filter must be one int32 per query")
+        if q_filter_mask is not None:
+            if f is None:
+                raise ValueError("q_filter_mask needs q_filter")
+            m = np.ascontiguousarray(q_filter_mask, dtype=np.int32)
+            if m.shape != (nq,):
+                raise ValueError("q_filter_mask must be one int32 per query")
+        out_s = np.empty((nq, k), dtype=np.float32)
+        out_i = np.empty((nq, k), dtype=np.int64)
+        out_g = np.empty((nq, k), dtype=np.int32)
+        total = np.empty((nq,), dtype=np.int64)
+        N.check("rass_index_search_grouped",
+                self._L.rass_index_search_grouped(self._h, _np_ptr(q), nq, k, group_mask, n_groups, _np_ptr(f), _np_ptr(m),
+                                                  _np_ptr(out_s), _np_ptr(out_i), _np_ptr(out_g), _np_ptr(total)))
+        return out_s, out_i, out_g, total
+
+    def search_grouped_device(self, d_queries_ptr: int, nq: int, k: int, group_mask: int, n_groups: int, d_out_scores_ptr: int,
+                              d_out_ids_ptr: int, d_out_groups_ptr: int, d_group_total_ptr: int, d_status_ptr: int,
+                              id_base: int = 0, d_q_filter_ptr: int = 0, d_q_filter_mask_ptr: int = 0) -> None:
+        """Async, device-resident ``search_grouped`` (``rass_index_search_grouped_device``); nq <= 32.  ``*d_status`` (one
+        int32) ends as 1 when a matching row's group key was >= ``n_groups`` (that row is left out), else 0."""
+        k, group_mask, n_groups = self._check_grouped(k, group_mask, n_groups)
+        N.check("rass_index_search_grouped_device",
+                self._L.rass_index_search_grouped_device(self._h, ctypes.c_void_p(d_queries_ptr), int(nq), k, group_mask, n_groups,
+                                                         ctypes.c_void_p(d_q_filter_ptr or 0),
+                                                         ctypes.c_void_p(d_q_filter_mask_ptr or 0), int(id_base),
+                                                         ctypes.c_void_p(d_out_scores_ptr), ctypes.c_void_p(d_out_ids_ptr),
+                                                         ctypes.c_void_p(d_out_groups_ptr), ctypes.c_void_p(d_group_total_ptr),
+                                                         ctypes.c_void_p(d_status_ptr)))
+
     def search_device(self, d_queries_ptr: int, nq: int, k: int, d_out_scores_ptr: int, d_out_ids_ptr: int,
                       id_base: int = 0, d_q_filter_ptr: int = 0, d_q_filter_mask_ptr: int = 0) -> None:
         """Async, device-resident variant (multi-GPU path, benchmark); nq <= 32."""

@@ -46,7 +46,7 @@ from typing import Any, Callable, Dict, List, Optional, Tuple
 import numpy as np
 
 from . import config, prefetch
-from .docstore import REGISTRY, IndexState
+from .docstore import REGISTRY, TAG_DOCTYPE_MASK, TAG_PATIENT_MASK, IndexState
 
 logger = logging.getLogger("rassengine_amd")
 
@@ -180,6 +180,41 @@ class HipIndexer:
         for _ in range(LAYOUT_ATTEMPTS):    # row ids belong to one layout of the index, as in _knn
             layout = _layout_epoch(st.index)
             scores, ids, totals = st.index.search_range(q, thr, max_hits=limit_eff, **flt)
+            hits = self._hits(st, scores[0], ids[0], 1.0, None, layout)
+            if hits is not None:
+                return hits, int(totals[0])
+        raise RuntimeError(f"{self.index_name}: the index was compacted during every one of {LAYOUT_ATTEMPTS} searches")
+
+    def semantic_search_collapsed(self, query_emb: np.ndarray, k: int = TOP_K, collapse: str = "patientId",
+                                  filter_clause: Optional[Dict] = None, patient_id: Optional[str] = None
+                                  ) -> Tuple[List[Tuple[Dict, float]], int]:
+        """The k-NN clause under ``"collapse": {"field": collapse}``: the best chunk of every distinct ``patientId`` (or
+        ``doc_type``), the k best of those, in one pass over the index whatever k is (``FlatIndex.search_grouped``).
+        Returns ``(hits, total_groups)``: ``[(doc_dict, float(score))]`` best first in ``semantic_search``'s score units,
+        and the exact number of distinct values among the matching chunks (chunks without the field count as one value,
+        as OpenSearch collapses missing values together).  Filters as ``semantic_search``.  An empty embedding or an
+        unindexed patient gives ``([], 0)``; errors raise (this method has no counterpart in the reference to mirror)."""
+        if collapse not in ("patientId", "doc_type"):
+            raise ValueError(f"collapse must be 'patientId' or 'doc_type', not {collapse!r}")
+        if _empty(query_emb):
+            return [], 0
+        st: Optional[IndexState] = REGISTRY.get(self.index_name, create=False)
+        if st is None:
+            return [], 0
+        prep = self._prepare(st, query_emb, k, filter_clause, patient_id, None)
+        if prep is None:
+            return [], 0
+        q, k_eff, (fval, fmask) = prep
+        if not hasattr(st.index, "search_grouped"):
+            raise NotImplementedError(f"{self.index_name}: {type(st.index).__name__} has no grouped search "
+                                      "(IVF-backed and sharded indices cannot collapse; use a flat fp32 index)")
+        group_mask = TAG_PATIENT_MASK if collapse == "patientId" else TAG_DOCTYPE_MASK
+        flt = dict(q_filter=np.array([fval], dtype=np.int32), q_filter_mask=np.array([fmask], dtype=np.int32)) if fmask else {}
+        for _ in range(LAYOUT_ATTEMPTS):    # row ids belong to one layout of the index, as in _knn
+            layout = _layout_epoch(st.index)
+            # codes run 1 .. len, 0 = none; read per attempt: a concurrent ingest may have added a value
+            n_groups = len(st.patients if collapse == "patientId" else st.doc_types) + 1
+            scores, ids, _groups, totals = st.index.search_grouped(q, k_eff, group_mask, n_groups, **flt)
             hits = self._hits(st, scores[0], ids[0], 1.0, None, layout)
             if hits is not None:
                 return hits, int(totals[0])
