@@ -324,6 +324,55 @@ int rass_index_search_grouped_device(rass_index_t* idx, const float* d_queries, 
                                      int64_t id_base, float* d_out_scores, int64_t* d_out_ids,
                                      int32_t* d_out_groups, int64_t* d_group_total, int32_t* d_status);
 
+/* ALLOW-LIST search: the exact top-k among the rows a per-query BITMAP allows — the general restriction next to the tag
+ * compare: a set of patients or doc types (OpenSearch `terms`), the hit set of a text query (`ids`), a date range or an ACL
+ * resolved elsewhere.  A bitmap is uint32 words, bit (r & 31) of word r >> 5 allows row ordinal r; `allow` is
+ * uint32[n_bitmaps][words_per_bitmap], row-major, words_per_bitmap >= ceil(rows / 32) for the index's row count at the call.
+ * n_bitmaps = nq: bitmap q belongs to query q; n_bitmaps = 1: ONE bitmap shared by every query (it is read in place, never
+ * expanded).  Bits of tombstoned rows, bits at or past the row count and surplus words allow nothing.
+ * A row MATCHES query q when it is live, passes the filter exactly as in rass_index_search_ex (q_filter NULL, exact, or
+ * (tag & q_filter_mask[q]) == q_filter[q]) and its bit is set.  out_scores / out_ids are [nq][k]: the matching rows, score
+ * descending, ties by row ordinal ascending, (-inf, -1) past the end, as rass_index_search_ex pads.  Scores are the fp32
+ * values of the flat scan (the same MFMA chain, the same p0 + ... + p7 sum): bit-identical to what rass_index_search_ex
+ * reports for that row; with every bit set the answer IS rass_index_search_ex's.  Ids as rass_index_search_ex reports them:
+ * ordinals, or the caller-assigned ids of rass_index_add_ex.
+ * Cost follows the bitmap, not the index: per launch group of RASS_MAX_QBATCH queries a plan kernel lists the 32-row tiles
+ * in which some query has a bit set, and the scan streams those tiles only.  No sample floor is used.
+ * 1 <= k <= RASS_MAX_K_MULTIPASS (k > RASS_MAX_K in passes of RASS_MAX_K under the continuation bound, over the same work
+ * list); 0 <= nq <= RASS_MAX_DEVICE_BATCH.  Outside those, n_bitmaps neither 1 nor nq, or words_per_bitmap too small:
+ * RASS_ERR_INVALID.  fp32 indices with dim <= 1024; a bf16 index or a wide-row index answers RASS_ERR_UNSUPPORTED.  The
+ * prefilter mode of the index is ignored: an allowed search always runs the exact fp32 scan.  IVF, cross-index batches
+ * (rass_index_search_multi), the sharded multi-GPU front, the 64-query pair kernel, and the range and grouped searches have
+ * no allow-list form.
+ * A bitmap names row ordinals of ONE layout of the index: build it and search under one layout epoch
+ * (rass_index_layout_epoch).  Thread-safety and layout epochs as rass_index_search_ex. */
+int rass_index_search_allowed(rass_index_t* idx, const float* queries, int nq, int k,
+                              const uint32_t* allow, int n_bitmaps, int64_t words_per_bitmap,
+                              const int32_t* q_filter, const int32_t* q_filter_mask,
+                              float* out_scores, int64_t* out_ids);
+/* Device-resident variant: every pointer is device memory, the call is stream-ordered, nothing is synchronised and nothing
+ * is read back; the same bounds on nq and k (every pass of a k > RASS_MAX_K search is enqueued by the one call).  Ids are
+ * id_base + row (ignored on an index with caller-assigned ids, which are reported). */
+int rass_index_search_allowed_device(rass_index_t* idx, const float* d_queries, int nq, int k,
+                                     const uint32_t* d_allow, int n_bitmaps, int64_t words_per_bitmap,
+                                     const int32_t* d_q_filter, const int32_t* d_q_filter_mask,
+                                     int64_t id_base, float* d_out_scores, int64_t* d_out_ids);
+/* Bitmap builders: d_allow is DEVICE memory of `words` >= ceil(rows / 32) uint32, overwritten whole; rows / values are HOST
+ * arrays.  Stream-ordered on the engine's stream; the host arrays may be reused when the call returns.
+ * _from_rows: the bits of the n row ordinals in `rows`; ids outside [0, rows) are ignored, duplicates are fine.
+ * _from_tag_values: the bit of every live row whose (tag & mask) is one of the n_values `values` (any order, duplicates
+ * fine): OpenSearch's `terms` filter on patientId (mask RASS_TAG_PATIENT_MASK) or doc_type (RASS_TAG_DOCTYPE_MASK, values
+ * shifted by RASS_TAG_DOCTYPE_SHIFT). */
+int rass_index_allow_from_rows(rass_index_t* idx, const int64_t* rows, int64_t n, uint32_t* d_allow, int64_t words);
+int rass_index_allow_from_tag_values(rass_index_t* idx, const int32_t* values, int64_t n_values, int32_t mask,
+                                     uint32_t* d_allow, int64_t words);
+/* The work list an allowed search of ONE launch group (1 <= nq <= RASS_MAX_QBATCH) would walk, for tests and tools: d_allow
+ * as in rass_index_search_allowed_device.  *out_n = the number of items = the tiles in which some query has a bit set below
+ * the row count; the first min(*out_n, capacity) items, tiles ascending, go to the HOST arrays out_tile / out_rows (rows of
+ * the tile that exist) / out_mask (bit q set iff query q has a bit set in the tile).  Synchronises. */
+int rass_index_allow_plan(rass_index_t* idx, const uint32_t* d_allow, int n_bitmaps, int64_t words_per_bitmap, int nq,
+                          int32_t* out_tile, int32_t* out_rows, uint32_t* out_mask, int64_t capacity, int64_t* out_n);
+
 /* Prefilter mode (SURVEY §8f-4 "bf16 (or int8)"; the reference's own index is approximate, app/main.py:563-572), OFF by
  * default.  `enable` = RASS_PREFILTER_BF16 (1): keep a bf16 copy of the slab, scan IT (half the HBM bytes per pass, bf16
  * MFMA) for the 32 best candidates per query; RASS_PREFILTER_INT8 (2): keep an int8 copy (a quarter of the bytes; per row

@@ -8,6 +8,7 @@
 //   api_search.hip   flat search entry points: one group, the fused batches, the host API with its pinned slots, search_multi,
 //                    the score-threshold (range) search, the grouped (collapsed) search
 //   api_ivf.hip      IVF build, persistence, probe, delta and batch
+//   api_allow.hip    the allow-list search (top-k within a per-query row bitmap), its bitmap builders and its plan
 //   api_compact.hip  compaction of a flat index, its layout epoch, the stateless wrappers of compact.hip
 //
 // Ownership model: the engine singleton of a process owns the corpus slabs
@@ -258,6 +259,12 @@ struct rass_engine {
     size_t group_bytes = 0;
     unsigned char* d_group_io = nullptr;
     size_t group_io_bytes = 0;
+    // the allow-list search (api_allow.hip): the work list and plan workspace of one launch group (AllowView), and the host
+    // entry points' device staging (bitmaps, row / value lists in; lists out); both grown on demand, used under mu in stream order
+    unsigned char* d_allow = nullptr;
+    size_t allow_bytes = 0;
+    unsigned char* d_allow_io = nullptr;
+    size_t allow_io_bytes = 0;
     // host-API staging
     float* d_qraw = nullptr;        // [32][dim]
     int32_t* d_qfilter = nullptr;   // [32]
@@ -490,6 +497,21 @@ struct FlatRequest {
 int bf16_scan_launch(rass_index* idx, const FlatRequest& r);
 int prefilter_launch(rass_index* idx, const FlatRequest& r);
 int cert_launch(rass_index* idx, const FlatRequest& r);
+
+// One layout per answer.  The host search entry points release eng->mu between launch groups and between the passes of a
+// k > 32 search, and a pass's continuation bound names a row ORDINAL: a compaction (rass_index_compact) landing in between
+// would mix two layouts in one answer.  They read the layout epoch(s) first and run again when it moved meanwhile — bounded:
+// a compaction is rare and takes far longer than a search.
+constexpr int kLayoutAttempts = 8;
+template <class Epoch, class Once>
+int one_layout(Epoch&& epoch, Once&& once) {
+    for (int attempt = 0; attempt < kLayoutAttempts; ++attempt) {
+        const int64_t before = epoch();
+        const int rc = once();
+        if (rc != RASS_OK || epoch() == before) return rc;
+    }
+    return fail(RASS_ERR_UNSUPPORTED, "the index was compacted during every attempt of this search: try again");
+}
 
 // A pinned host slot for one search call in flight (blocks while all kHostSlots are taken); api_search.hip.
 HostSlot* slot_acquire(rass_engine* eng);

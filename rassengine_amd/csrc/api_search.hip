@@ -449,21 +449,6 @@ int search_device_locked(rass_index_t* idx, const FlatRequest& r) {
 
 using namespace rass::host;
 
-// One layout per answer.  The host entry points below release eng->mu between launch groups and between the passes of a
-// k > 32 search, and a pass's continuation bound names a row ORDINAL: a compaction (rass_index_compact) landing in between
-// would mix two layouts in one answer.  They read the layout epoch(s) first and run again when it moved meanwhile — bounded:
-// a compaction is rare and takes far longer than a search.
-constexpr int kLayoutAttempts = 8;
-template <class Epoch, class Once>
-static int one_layout(Epoch&& epoch, Once&& once) {
-    for (int attempt = 0; attempt < kLayoutAttempts; ++attempt) {
-        const int64_t before = epoch();
-        const int rc = once();
-        if (rc != RASS_OK || epoch() == before) return rc;
-    }
-    return fail(RASS_ERR_UNSUPPORTED, "the index was compacted during every attempt of this search: try again");
-}
-
 extern "C" {
 
 int rass_index_search_device_ex(rass_index_t* idx, const float* d_queries, int nq, int k, const int32_t* d_q_filter,

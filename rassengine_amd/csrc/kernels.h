@@ -86,6 +86,13 @@ struct ScanArgs {
     unsigned long long* group_table = nullptr;
     unsigned* group_status = nullptr;
     int group_mask = 0, group_shift = 0, group_n = 0;
+    // Allow-list scan (kAllow; allow != nullptr selects it: narrow rows, <= 32 zero-padded queries, a work list as for an IVF
+    // probe — launch_allow_plan's —, plain or masked filters and the continuation bound; no sample floor).  Query q's word of
+    // tile t is allow[q * allow_q_stride + t] (allow_q_stride = 0: one bitmap shared by every query); bit r of it allows row
+    // 32 t + r.  A row ranks for q when it is live, passes q's filter and bound, and its bit is set.  Each wave reads the two
+    // words of its two queries of a ranking step with scalar loads: they take no vector register and no LDS.
+    const uint32_t* allow = nullptr;
+    int64_t allow_q_stride = 0;
 };
 constexpr int kRangeCountStride = 32;   // one 128-byte line per query's counter: every workgroup adds to all of them
 constexpr int kRangeMaxHits = 4096;     // = RASS_MAX_K_MULTIPASS: 4 096 64-bit sort keys are range_finish's 32 KiB of LDS
@@ -134,6 +141,29 @@ constexpr int kGroupMaxGroups = 1 << 20;  // the exclusive bound of a group key:
 hipError_t launch_group_select(const unsigned long long* table, int nq, int n_groups, int k, int64_t id_base, const int64_t* id_map,
                                float* out_scores, int64_t* out_ids, int32_t* out_groups, int64_t* total, const unsigned* status,
                                int32_t* out_status, hipStream_t stream);
+
+// ---- allow-list search (allow.hip): row bitmaps, their work list, and the store of a pass.  A bitmap is uint32 words, bit
+// (r & 31) of word r >> 5 allows row r.  Plain vector loads, stores and atomics.
+// allow[row >> 5] |= 1 << (row & 31) for the n ids of `rows` that lie in [0, n_rows); duplicates are fine.  The caller zeroes `allow`.
+hipError_t launch_allow_from_rows(const int64_t* rows, int64_t n, int64_t n_rows, uint32_t* allow, hipStream_t stream);
+// The words of rows [0, n_rows): bit set where the row is live (tag != -1) and (tag & mask) is one of the n_values ASCENDING
+// `values` (binary search; the set sits in LDS up to kAllowLdsValues of them).  Every word below ceil(n_rows / 32) is written.
+constexpr int kAllowLdsValues = 2048;
+hipError_t launch_allow_from_tag_values(const int32_t* tags, int64_t n_rows, const int32_t* values, int n_values, int32_t mask,
+                                        uint32_t* allow, hipStream_t stream);
+// The work list of one launch group of nq <= 32 queries over the tiles of n_rows rows, tiles ASCENDING (a workgroup must meet
+// rows in ascending order: the insertion's tie rule): one item per tile in which some query has a bit set below n_rows, its
+// mask the queries that do.  Word of (q, t): allow[q * q_stride + t], q_stride = 0 for a shared bitmap.  *n_work = the count.
+// workspace: allow_plan_workspace_bytes(n_rows).  Two launches; no workgroup waits on another.
+size_t allow_plan_workspace_bytes(int64_t n_rows);
+hipError_t launch_allow_plan(const uint32_t* allow, int64_t q_stride, int nq, int64_t n_rows, int32_t* work_tile, int32_t* work_rows,
+                             uint32_t* work_mask, int32_t* n_work, void* workspace, hipStream_t stream);
+// One pass of a k > 32 search: the pass's merged lists [nq][kk] (scores, slab rows; -1 = none) go to out[q][kdone .. kdone + kk)
+// of the [nq][k] answer, ids = id_map[row] or id_base + row, (-inf, -1) where there is none; after_*[q] = the pass's last hit
+// as the next pass's continuation bound (score, row), or (-inf, INT64_MAX) when the pass came back short.
+hipError_t launch_allow_store(const float* scores, const int64_t* rows, int nq, int kk, int k, int kdone, int64_t id_base,
+                              const int64_t* id_map, float* out_scores, int64_t* out_ids, float* after_s, int64_t* after_i,
+                              hipStream_t stream);
 
 // ---- bf16 candidate scan + exact re-rank (scan_bf16.hip)
 struct ScanBf16Args {

@@ -56,8 +56,12 @@ struct WorkItem {
 // (emit_range below; ScanArgs::range_*), for the score-threshold search.  No sample pass, no floor, no TopList.
 // kGroupMax: a flat scan that ranks nothing either: every matching row is folded into the running maximum of its (query,
 // group) slot (emit_group_max below; ScanArgs::group_*), for the grouped (collapsed) search.  No sample pass, no floor, no TopList.
+// kAllow: the top-k scan within a per-query row bitmap (ScanArgs::allow), under its own kernel name.  It walks a work list
+// as kIvf does — the tiles in which some query of the launch group has a bit set (allow.hip builds it) — and a row ranks for
+// query q only where bit (row & 31) of q's word of the tile is set.  No sample pass and no floor: a floor is only valid under
+// the predicate it was sampled with.
 enum ScanMode { kFlat = 0, kIvf = 1, kMulti = 2, kFlatSample = 3, kFlatGroups = 4, kIvfGroups = 5, kFlatSampleGroups = 6, kRange = 7,
-                kGroupMax = 8 };
+                kGroupMax = 8, kAllow = 9 };
 constexpr bool mode_is_flat(int mode) {
     return mode == kFlat || mode == kFlatSample || mode == kFlatGroups || mode == kFlatSampleGroups || mode == kRange ||
            mode == kGroupMax;

@@ -289,6 +289,15 @@ __global__ __launch_bounds__(kThreads, 2) void scan_topk_f32_kernel(ScanArgs p) 
             ok = row_ok && (qf1 < 0 || qf1 == tag);
         }
         if (IVF) ok = ok && ((w.mask >> q) & 1u);
+        if (MODE == kAllow) {
+            // the row's bit in its query's word of the tile.  The wave's two queries of this part (one per half) and the tile
+            // are wave-uniform, so the two words come by scalar loads: no vector register, no LDS, and no wait on the corpus
+            // loads in flight.  Queries past nq (zero rows, never written) read the last live query's word: in bounds.
+            const int qa = min(pq * 16 + wid, p.nq - 1), qb = min(pq * 16 + 8 + wid, p.nq - 1);
+            const unsigned wa = p.allow[(int64_t)qa * p.allow_q_stride + w.tile];
+            const unsigned wb = p.allow[(int64_t)qb * p.allow_q_stride + w.tile];
+            ok = ok && ((((lane & 32) ? wb : wa) >> r) & 1u);
+        }
         if (MODE == kRange) {   // no ranking: count and emit the rows at or above the query's threshold
             emit_range(ok && s >= sh_thr[q], s, row, p.range_count + q * kRangeCountStride, p.range_hits + (int64_t)q * p.range_cap,
                        p.range_cap);
@@ -868,6 +877,15 @@ hipError_t launch_scan_topk_f32(const ScanArgs& a, int grid, hipStream_t stream)
     if (!scan_supported_stride(a.row_stride)) return hipErrorInvalidValue;
     const int ch = (int)(a.row_stride / 128);
     const bool ext = a.q_filter_mask || a.q_after_score || a.q_after_id;
+    if (a.allow != nullptr) {  // the allow-list scan: narrow rows, a work list, filters and continuation bound, nothing else
+        if (!a.work_tile || !a.work_rows || !a.work_mask || !a.n_work || a.work_base || ch > 8 || a.nq < 1 || a.nq > 32 || a.allow_q_stride < 0)
+            return hipErrorInvalidValue;
+        if (a.range_count || a.group_table || a.sample_pass || a.sample_best || a.wgs_per_group || a.live_nq) return hipErrorInvalidValue;
+        if ((a.q_after_score == nullptr) != (a.q_after_id == nullptr)) return hipErrorInvalidValue;
+        if (a.q_filter_mask != nullptr && a.q_filter == nullptr) return hipErrorInvalidValue;
+        // one variant per stride: 32 (zero-padded) queries, EXT — absent filters and bounds take their neutral values in LDS
+        return launch_ch<2, kAllow, true>(ch, a, grid, stream);
+    }
     if (a.range_count != nullptr) {  // the range scan: flat, every stride, plain or masked filters, nothing else
         if (!a.range_thr || !a.range_hits || a.range_cap < 1 || a.range_cap > kRangeMaxHits || a.nq < 1 || a.nq > 32)
             return hipErrorInvalidValue;

@@ -17,6 +17,29 @@ def _np_ptr(a: Optional[np.ndarray]):
     return None if a is None else a.ctypes.data_as(ctypes.c_void_p)
 
 
+def pack_allow(mask: np.ndarray) -> np.ndarray:
+    """Boolean row mask(s) -> allow-list bitmap words (``FlatIndex.search_allowed``): ``mask`` is bool [n] or [nb, n]; the
+    result is uint32 [ceil(n / 32)] or [nb, ceil(n / 32)] with bit ``r & 31`` of word ``r >> 5`` set where row r is allowed."""
+    m = np.asarray(mask, dtype=bool)
+    if m.ndim not in (1, 2):
+        raise ValueError(f"expected a boolean mask [n] or [nb, n], got shape {m.shape}")
+    n = m.shape[-1]
+    words = (n + 31) // 32
+    padded = np.zeros(m.shape[:-1] + (words * 32,), dtype=bool)
+    padded[..., :n] = m
+    packed = np.packbits(padded, axis=-1, bitorder="little")
+    return np.ascontiguousarray(packed).view("<u4").reshape(m.shape[:-1] + (words,)).astype(np.uint32, copy=False)
+
+
+def unpack_allow(words: np.ndarray, n: int) -> np.ndarray:
+    """The inverse of ``pack_allow``: uint32 words [w] or [nb, w] -> bool [n] or [nb, n] (n <= 32 w)."""
+    w = np.ascontiguousarray(np.asarray(words).astype("<u4", copy=False))
+    if w.ndim not in (1, 2) or int(n) < 0 or int(n) > w.shape[-1] * 32:
+        raise ValueError(f"expected uint32 words [w] or [nb, w] with 32 w >= n, got shape {w.shape} for n = {n}")
+    bits = np.unpackbits(w.view(np.uint8).reshape(w.shape[:-1] + (w.shape[-1] * 4,)), axis=-1, bitorder="little")
+    return bits[..., :int(n)].astype(bool)
+
+
 class Engine:
     """Owns one GPU's corpus slabs for the life of the process (SURVEY §8b ownership)."""
 
@@ -483,6 +506,154 @@ class FlatIndex:
                                                          ctypes.c_void_p(d_out_scores_ptr), ctypes.c_void_p(d_out_ids_ptr),
                                                          ctypes.c_void_p(d_out_groups_ptr), ctypes.c_void_p(d_group_total_ptr),
                                                          ctypes.c_void_p(d_status_ptr)))
+
+    # ---- allow-list search: exact top-k within a per-query row bitmap
+    @property
+    def allow_words(self) -> int:
+        """uint32 words a bitmap of this index needs now: ceil(rows / 32)."""
+        return (self.rows + 31) // 32
+
+    ALLOW_SLACK_WORDS = 64       # words a new bitmap gets beyond ceil(rows / 32): rows appended meanwhile (2 048 of them) still fit
+
+    def _build_bitmap(self, fn: str, call):
+        """A device bitmap sized for the index as it is NOW plus slack, filled by ``call(tensor)`` (a native builder).  The
+        index may grow between reading ``rows`` here and the builder's own check: the slack absorbs that, and a builder that
+        still finds the bitmap too short is given a fresh, longer one.  Surplus words allow nothing."""
+        import torch
+        for _ in range(4):
+            words = self.allow_words + self.ALLOW_SLACK_WORDS
+            out = torch.empty((words,), dtype=torch.int32, device=f"cuda:{self.engine.device}")
+            rc = call(out)
+            if rc < 0 and self.allow_words > words:
+                continue            # the index outgrew the slack meanwhile
+            N.check(fn, rc)
+            return out
+        raise RuntimeError(f"{self.name}: the index kept outgrowing the bitmap under construction")
+
+    def allow_from_rows(self, rows):
+        """A device bitmap (torch int32 CUDA tensor holding the uint32 words, ``allow_words`` of them plus slack) allowing
+        exactly the given row ordinals (``rass_index_allow_from_rows``): ids outside [0, rows) are ignored, duplicates are
+        fine.  It belongs to the layout epoch it was built under; rows appended later are not allowed by it."""
+        r = np.ascontiguousarray(np.asarray(rows).reshape(-1), dtype=np.int64)
+        return self._build_bitmap("rass_index_allow_from_rows", lambda out: self._L.rass_index_allow_from_rows(
+            self._h, _np_ptr(r), r.shape[0], ctypes.c_void_p(out.data_ptr()), out.shape[0]))
+
+    def allow_from_tag_values(self, values, mask: int):
+        """A device bitmap allowing every live row whose ``(tag & mask)`` is one of ``values`` (``rass_index_allow_from_tag_values``):
+        OpenSearch's ``terms`` filter.  ``mask``: ``RASS_TAG_PATIENT_MASK`` (values = patient codes), ``RASS_TAG_DOCTYPE_MASK``
+        (values = codes << 24) or both.  Rows appended after the call are not allowed by it."""
+        v = np.ascontiguousarray(np.asarray(values).reshape(-1), dtype=np.int32)
+        mask = int(mask)
+        if not 0 <= mask <= 0x7FFFFFFF:
+            raise ValueError(f"mask must be within 0x7fffffff, got {mask:#x}")
+        return self._build_bitmap("rass_index_allow_from_tag_values", lambda out: self._L.rass_index_allow_from_tag_values(
+            self._h, _np_ptr(v), v.shape[0], mask, ctypes.c_void_p(out.data_ptr()), out.shape[0]))
+
+    def allow_plan(self, allow, nq: int) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """The work list an allowed search of one launch group of ``nq`` <= 32 queries walks (``rass_index_allow_plan``), for
+        tests and tools: (tile i32 [n], rows i32 [n], mask u32 [n]), tiles ascending.  ``allow``: a device bitmap ([words]
+        shared, or [nq, words])."""
+        n_bitmaps, words = (1, allow.shape[0]) if allow.dim() == 1 else (allow.shape[0], allow.shape[1])
+        cap = max(self.allow_words, 1)
+        tile, rows, mask = np.empty(cap, np.int32), np.empty(cap, np.int32), np.empty(cap, np.uint32)
+        n = ctypes.c_int64(0)
+        N.check("rass_index_allow_plan",
+                self._L.rass_index_allow_plan(self._h, ctypes.c_void_p(allow.data_ptr()), int(n_bitmaps), int(words), int(nq),
+                                              _np_ptr(tile), _np_ptr(rows), _np_ptr(mask), cap, ctypes.byref(n)))
+        return tile[:n.value], rows[:n.value], mask[:n.value]
+
+    def search_allowed(self, queries: np.ndarray, k: int, allow, q_filter: Optional[np.ndarray] = None,
+                       q_filter_mask: Optional[np.ndarray] = None) -> Tuple[np.ndarray, np.ndarray]:
+        """Exact cosine top-k among the rows a bitmap allows (``rass_index_search_allowed``).  ``allow``: uint32 words
+        (``pack_allow``) as a numpy array, or a device bitmap from ``allow_from_rows`` / ``allow_from_tag_values``; shape
+        [words] = one bitmap shared by every query, [nq, words] = one per query; words >= ``allow_words``.  A row matches
+        when it is live, passes ``q_filter`` / ``q_filter_mask`` as in ``search`` and has its bit set.  Returns (scores f32
+        [nq, k], ids i64 [nq, k]) as ``search`` does: best first, ties by id ascending, (-inf, -1) padding; k <= 4096, nq
+        <= 4096.  The scan streams only the 32-row tiles with a bit set.  fp32 indices with dim <= 1024; the prefilter mode
+        is ignored.  A bitmap names rows of one ``layout_epoch``.  Thread-safe."""
+        q = np.ascontiguousarray(queries, dtype=np.float32)
+        if q.ndim != 2 or q.shape[1] != self.dim:
+            raise ValueError(f"expected [nq, {self.dim}] queries, got {q.shape}")
+        nq, k = q.shape[0], int(k)
+        if not 1 <= k <= N.RASS_MAX_K_MULTIPASS:
+            raise ValueError(f"k must be in [1, {N.RASS_MAX_K_MULTIPASS}], got {k}")
+        if nq > N.RASS_MAX_DEVICE_BATCH:
+            raise ValueError(f"at most {N.RASS_MAX_DEVICE_BATCH} queries per call, got {nq}")
+        f = m = None
+        if q_filter is not None:
+            f = np.ascontiguousarray(q_filter, dtype=np.int32)
+            if f.shape != (nq,):
+                raise ValueError("q_filter must be one int32 per query")
+        if q_filter_mask is not None:
+            if f is None:
+                raise ValueError("q_filter_mask needs q_filter")
+            m = np.ascontiguousarray(q_filter_mask, dtype=np.int32)
+            if m.shape != (nq,):
+                raise ValueError("q_filter_mask must be one int32 per query")
+        on_device = not isinstance(allow, np.ndarray) and hasattr(allow, "data_ptr")
+        if not on_device:
+            allow = np.ascontiguousarray(allow, dtype=np.uint32)
+        shape = tuple(allow.shape)
+        if len(shape) not in (1, 2) or (len(shape) == 2 and shape[0] not in (1, nq)):
+            raise ValueError(f"allow must be [words] (shared) or [nq, words], got {shape} for {nq} queries")
+        out_s = np.empty((nq, k), dtype=np.float32)
+        out_i = np.empty((nq, k), dtype=np.int64)
+        if nq == 0:
+            return out_s, out_i
+        if on_device:
+            import torch
+            if not allow.is_cuda or allow.dtype != torch.int32 or not allow.is_contiguous():
+                raise ValueError("a device bitmap must be a contiguous int32 CUDA tensor")
+            dev = allow.device
+            dq = torch.from_numpy(q).to(dev)
+            df = torch.from_numpy(f).to(dev) if f is not None else None
+            dm = torch.from_numpy(m).to(dev) if m is not None else None
+            ds = torch.empty((nq, k), dtype=torch.float32, device=dev)
+            di = torch.empty((nq, k), dtype=torch.int64, device=dev)
+        # A bitmap speaks for the rows the index had when it was made.  Rows appended since (an ingest may land between the
+        # build and this search; the layout epoch does not move on an append) are not allowed by it: the bitmap is extended
+        # with zero words to what the index needs now, plus slack for rows that land before the native call's own check.
+        for _ in range(4):
+            words = int(allow.shape[-1])
+            need = self.allow_words
+            if words < need:
+                pad = need + self.ALLOW_SLACK_WORDS - words
+                if on_device:
+                    allow = torch.cat([allow, torch.zeros(tuple(allow.shape[:-1]) + (pad,), dtype=torch.int32, device=dev)], dim=-1).contiguous()
+                else:
+                    allow = np.ascontiguousarray(np.concatenate([allow, np.zeros(allow.shape[:-1] + (pad,), dtype=np.uint32)], axis=-1))
+                words = int(allow.shape[-1])
+            n_bitmaps = 1 if allow.ndim == 1 else int(allow.shape[0])
+            if on_device:
+                torch.cuda.current_stream(dev).synchronize()     # the engine works on its own stream
+                rc = self._L.rass_index_search_allowed_device(
+                    self._h, ctypes.c_void_p(dq.data_ptr()), nq, k, ctypes.c_void_p(allow.data_ptr()), n_bitmaps, words,
+                    ctypes.c_void_p(df.data_ptr()) if df is not None else None,
+                    ctypes.c_void_p(dm.data_ptr()) if dm is not None else None, 0, ctypes.c_void_p(ds.data_ptr()),
+                    ctypes.c_void_p(di.data_ptr()))
+            else:
+                rc = self._L.rass_index_search_allowed(self._h, _np_ptr(q), nq, k, _np_ptr(allow), n_bitmaps, words, _np_ptr(f),
+                                                       _np_ptr(m), _np_ptr(out_s), _np_ptr(out_i))
+            if rc < 0 and self.allow_words > words:
+                continue            # the index outgrew the slack between the two checks: extend again
+            N.check("rass_index_search_allowed_device" if on_device else "rass_index_search_allowed", rc)
+            if on_device:
+                self.engine.synchronize()
+                return ds.cpu().numpy(), di.cpu().numpy()
+            return out_s, out_i
+        raise RuntimeError(f"{self.name}: the index kept outgrowing the bitmap during the search")
+
+    def search_allowed_device(self, d_queries_ptr: int, nq: int, k: int, d_allow_ptr: int, n_bitmaps: int, words_per_bitmap: int,
+                              d_out_scores_ptr: int, d_out_ids_ptr: int, id_base: int = 0, d_q_filter_ptr: int = 0,
+                              d_q_filter_mask_ptr: int = 0) -> None:
+        """Async, device-resident ``search_allowed`` (``rass_index_search_allowed_device``): nq <= 4096 in launch groups of
+        32, k <= 4096 (every pass enqueued by the one call)."""
+        N.check("rass_index_search_allowed_device",
+                self._L.rass_index_search_allowed_device(self._h, ctypes.c_void_p(d_queries_ptr), int(nq), int(k),
+                                                         ctypes.c_void_p(d_allow_ptr), int(n_bitmaps), int(words_per_bitmap),
+                                                         ctypes.c_void_p(d_q_filter_ptr or 0),
+                                                         ctypes.c_void_p(d_q_filter_mask_ptr or 0), int(id_base),
+                                                         ctypes.c_void_p(d_out_scores_ptr), ctypes.c_void_p(d_out_ids_ptr)))
 
     def search_device(self, d_queries_ptr: int, nq: int, k: int, d_out_scores_ptr: int, d_out_ids_ptr: int,
                       id_base: int = 0, d_q_filter_ptr: int = 0, d_q_filter_mask_ptr: int = 0) -> None:

@@ -46,7 +46,7 @@ from typing import Any, Callable, Dict, List, Optional, Tuple
 import numpy as np
 
 from . import config, prefetch
-from .docstore import REGISTRY, TAG_DOCTYPE_MASK, TAG_PATIENT_MASK, IndexState
+from .docstore import REGISTRY, TAG_DOCTYPE_MASK, TAG_DOCTYPE_SHIFT, TAG_PATIENT_MASK, IndexState
 
 logger = logging.getLogger("rassengine_amd")
 
@@ -218,6 +218,71 @@ class HipIndexer:
             hits = self._hits(st, scores[0], ids[0], 1.0, None, layout)
             if hits is not None:
                 return hits, int(totals[0])
+        raise RuntimeError(f"{self.index_name}: the index was compacted during every one of {LAYOUT_ATTEMPTS} searches")
+
+    def semantic_search_within(self, query_emb: np.ndarray, k: int = TOP_K, patient_ids: Optional[List[Any]] = None,
+                               doc_types: Optional[List[str]] = None, doc_ids: Optional[List[str]] = None,
+                               filter_clause: Optional[Dict] = None, patient_id: Optional[str] = None
+                               ) -> List[Tuple[Dict, float]]:
+        """The k-NN clause under set-valued restrictions: a ``terms`` filter on ``patientId`` (``patient_ids``) and / or
+        ``doc_type`` (``doc_types``), an ``ids`` filter (``doc_ids``: the hit set of a text query, an ACL, a date range
+        resolved elsewhere), next to the single-valued ``filter_clause`` / ``patient_id`` of ``semantic_search``.  The
+        restrictions given are intersected; a value that was never indexed contributes nothing, an overwritten doc is found
+        at its current row only, and an empty intersection gives ``[]``.  With none of the three lists it is
+        ``semantic_search`` that raises.  The allowed rows go to the GPU as a bitmap (``FlatIndex.allow_from_rows`` /
+        ``allow_from_tag_values``) and the scan reads only the 32-row tiles that hold one (``FlatIndex.search_allowed``):
+        every allowed chunk gets its exact cosine, however deep it ranks in the whole index.  Returns ``[(doc_dict,
+        float(score))]`` best first in ``semantic_search``'s score units.  Errors raise (no counterpart in the reference)."""
+        if _empty(query_emb):
+            return []
+        if patient_ids is None and doc_types is None and doc_ids is None:
+            return self._knn(query_emb, k, filter_clause, patient_id, boost=1.0)
+        st: Optional[IndexState] = REGISTRY.get(self.index_name, create=False)
+        if st is None:
+            return []
+        prep = self._prepare(st, query_emb, k, filter_clause, patient_id, None)
+        if prep is None:
+            return []
+        q, k_eff, (fval, fmask) = prep
+        flt = dict(q_filter=np.array([fval], dtype=np.int32), q_filter_mask=np.array([fmask], dtype=np.int32)) if fmask else {}
+        if not hasattr(st.index, "search_allowed"):
+            raise NotImplementedError(f"{self.index_name}: {type(st.index).__name__} has no allow-list search "
+                                      "(IVF-backed and sharded indices cannot restrict by a bitmap; use a flat fp32 index)")
+        for _ in range(LAYOUT_ATTEMPTS):    # the bitmap and the ids belong to ONE layout of the index: built, searched and mapped under one epoch
+            layout = _layout_epoch(st.index)
+            with st.lock:
+                if _layout_epoch(st.index) != layout:
+                    continue
+                # known values only: a value that was never indexed matches no row
+                p_codes = None if patient_ids is None else sorted({c for c in (st.patients.lookup(p) for p in patient_ids) if c is not None})
+                t_codes = None if doc_types is None else sorted({c for c in (st.doc_types.lookup(t) for t in doc_types) if c is not None})
+                rows = None
+                if doc_ids is not None:
+                    rows = sorted({st.doc_row[d] for d in doc_ids if d in st.doc_row})   # keys as add_documents stores them
+                    if p_codes is not None or t_codes is not None:   # intersect on the host: the docs carry both fields
+                        def keeps(r: int) -> bool:
+                            doc = st.row_doc[r] if r < len(st.row_doc) else None
+                            return doc is not None and \
+                                (p_codes is None or st.patients.lookup(doc.get("patientId")) in p_codes) and \
+                                (t_codes is None or st.doc_types.lookup(doc.get("doc_type")) in t_codes)
+                        rows = [r for r in rows if keeps(r)]
+            if rows is not None:
+                if not rows:
+                    return []
+                allow = st.index.allow_from_rows(np.asarray(rows, dtype=np.int64))
+            else:
+                if (p_codes is not None and not p_codes) or (t_codes is not None and not t_codes):
+                    return []
+                mask = (TAG_PATIENT_MASK if p_codes is not None else 0) | (TAG_DOCTYPE_MASK if t_codes is not None else 0)
+                values = [p | (t << TAG_DOCTYPE_SHIFT) for p in (p_codes if p_codes is not None else [0])
+                          for t in (t_codes if t_codes is not None else [0])]
+                allow = st.index.allow_from_tag_values(np.asarray(values, dtype=np.int32), mask)
+            # an ingest may append rows between the build and the search (the epoch does not move on an append): the bitmap
+            # speaks for the rows it was built over, and search_allowed lets it allow nothing past them
+            scores, ids = st.index.search_allowed(q, k_eff, allow, **flt)
+            hits = self._hits(st, scores[0], ids[0], 1.0, None, layout)
+            if hits is not None:
+                return hits
         raise RuntimeError(f"{self.index_name}: the index was compacted during every one of {LAYOUT_ATTEMPTS} searches")
 
     def knn_scores(self, query_emb: np.ndarray, k: int = TOP_K, boost: float = 1.0,
