@@ -230,7 +230,15 @@ int rass_index_search_device_ex(rass_index_t* idx, const float* d_queries,
  * and row ordinal > after_row (-1: every tying row counts).  A multi-GPU front asks every shard for its next 32
  * behind the previous pass's last GLOBAL hit — each rank translates that hit's id into its own row ordinals, which
  * ascend with the ids — and merges; the reference passes the caller's top_k straight through (app/main.py:2882,
- * 3008).  Reported ids are the index's own (caller-assigned ids where rass_index_add_ex gave them, else ordinals). */
+ * 3008).  Reported ids are the index's own (caller-assigned ids where rass_index_add_ex gave them, else ordinals);
+ * the bound's row and the tie order are always in row ORDINALS.
+ * The bound need not be a row's own score, and after_row may be ANY int64: it need not name a live row, a row the
+ * query's filter lets through, or a row at all (-1, or a value at or past the row count: no row tying with
+ * after_score counts).  after_score = +inf: every row ranks (the plain top-k, whatever after_row is); -inf: none;
+ * NaN: none either (both comparisons above are false for every score).  The bound is honoured exactly whatever the
+ * prefilter mode (a bounded request always takes the exact scan) and on RASS_BF16 indices.  1 <= nq <=
+ * RASS_MAX_QBATCH, 1 <= k <= RASS_MAX_K; fewer than k rows behind the bound: (-inf, -1) past the end.
+ * (tests/test_gpu_search_after.py holds all of this to the CPU oracle.) */
 int rass_index_search_device_after(rass_index_t* idx, const float* d_queries, int nq, int k,
                                    const int32_t* d_q_filter, const int32_t* d_q_filter_mask,
                                    const float* d_after_score, const int64_t* d_after_row,
