@@ -381,6 +381,43 @@ int rass_index_allow_from_tag_values(rass_index_t* idx, const int32_t* values, i
 int rass_index_allow_plan(rass_index_t* idx, const uint32_t* d_allow, int n_bitmaps, int64_t words_per_bitmap, int nq,
                           int32_t* out_tile, int32_t* out_rows, uint32_t* out_mask, int64_t capacity, int64_t* out_n);
 
+/* Semantic TERMS AGGREGATION: per-group hit counts above a min_score — OpenSearch's `"aggs": {"x": {"terms": {"field": ...}}}`
+ * under a k-NN clause with a min_score, with a `cardinality` and the hit total thrown in.  The group of a row is a bit field
+ * of its tag, as in rass_index_search_grouped.  A row is a HIT of query q when it is live, passes q_filter (NULL, exact, or
+ * masked by q_filter_mask) and its score is >= min_score[q], as in rass_index_search_range (-inf: every live matching row;
+ * NaN: RASS_ERR_INVALID in the host variant, no hits in the device variant).  ONE corpus pass per launch group counts the
+ * hits of every (query, group) and keeps each group's best hit; a select over the n_groups counters of each query finishes it.
+ * Buckets come in OpenSearch's default order, doc_count descending then group key ascending; the `size` first are listed:
+ * out_groups / out_counts / out_scores / out_ids are [nq][size] — the group key, its number of hits, and the score and id of
+ * its best hit under (score descending, row ordinal ascending) — and (-1, 0, -inf, -1) past the end.  Scores and ids as
+ * rass_index_search_grouped reports them (the flat scan's fp32 scores bit for bit; ordinals or rass_index_add_ex ids).
+ * out_n_buckets[q] is the EXACT number of groups with a hit (the field's cardinality among the hits), out_total_hits[q] the
+ * EXACT number of hits: what rass_index_search_range reports as its total for the same threshold and filter.  Counts are
+ * integers added with atomics: the answer is a function of the index and the arguments alone.
+ * group_mask: non-zero, within 0x7fffffff.  n_groups: the exclusive bound of the group key, 1 .. 1 048 576 (the call keeps
+ * nq x n_groups 12-byte slots on the device — up to 384 MiB for 32 queries at the bound — in the engine-owned block of the
+ * grouped search, grown on demand; RASS_ERR_OOM when it cannot be had, and nothing has changed).
+ * 1 <= size <= RASS_MAX_K_MULTIPASS.  Outside those: RASS_ERR_INVALID.  A hit whose group key is >= n_groups is left out of
+ * the answer: RASS_ERR_INVALID, named in rass_last_error(), and the outputs are unspecified; a row below the threshold never
+ * causes that.  Any nq (scanned in groups of RASS_MAX_QBATCH).  fp32 indices of every dim the engine takes, wide rows
+ * included; a bf16 index answers RASS_ERR_UNSUPPORTED.  The prefilter mode of the index is ignored: a candidate scan cannot
+ * bound a count.  IVF, cross-index batches, the sharded multi-GPU front, the 64-query pair kernel and the allow list have no
+ * aggregate form.  Thread-safety and layout epochs as rass_index_search_grouped. */
+int rass_index_aggregate(rass_index_t* idx, const float* queries, int nq, const float* min_score, int size,
+                         int32_t group_mask, int32_t n_groups,
+                         const int32_t* q_filter, const int32_t* q_filter_mask,
+                         int32_t* out_groups, int64_t* out_counts, float* out_scores, int64_t* out_ids,
+                         int64_t* out_n_buckets, int64_t* out_total_hits);
+/* Device-resident variant: every pointer is device memory, the call is stream-ordered, nothing is synchronised and nothing is
+ * read back; nq <= RASS_MAX_QBATCH.  Ids are id_base + row (ignored on an index with caller-assigned ids, which are
+ * reported), to be paired with the layout epoch read before the call.  *d_status = 1 when a hit's group key was >= n_groups
+ * (that hit is left out of every figure; the rest of the answer is intact), else 0. */
+int rass_index_aggregate_device(rass_index_t* idx, const float* d_queries, int nq, const float* d_min_score, int size,
+                                int32_t group_mask, int32_t n_groups,
+                                const int32_t* d_q_filter, const int32_t* d_q_filter_mask,
+                                int64_t id_base, int32_t* d_out_groups, int64_t* d_out_counts, float* d_out_scores,
+                                int64_t* d_out_ids, int64_t* d_n_buckets, int64_t* d_total_hits, int32_t* d_status);
+
 /* Prefilter mode (SURVEY §8f-4 "bf16 (or int8)"; the reference's own index is approximate, app/main.py:563-572), OFF by
  * default.  `enable` = RASS_PREFILTER_BF16 (1): keep a bf16 copy of the slab, scan IT (half the HBM bytes per pass, bf16
  * MFMA) for the 32 best candidates per query; RASS_PREFILTER_INT8 (2): keep an int8 copy (a quarter of the bytes; per row

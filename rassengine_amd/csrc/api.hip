@@ -267,6 +267,7 @@ void rass_engine_destroy(rass_engine_t* eng) {
         if (sl.h_items) (void)hipHostFree(sl.h_items);
         if (sl.h_range) (void)hipHostFree(sl.h_range);
         if (sl.h_group) (void)hipHostFree(sl.h_group);
+        if (sl.h_agg) (void)hipHostFree(sl.h_agg);
         if (sl.done) (void)hipEventDestroy(sl.done);
     }
     for (hipEvent_t e : eng->ev_pool) (void)hipEventDestroy(e);

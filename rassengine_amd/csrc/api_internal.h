@@ -6,7 +6,7 @@
 //                    stateless wrappers, k-means, peer buffers
 //   api_scan.hip     the tuning switches, the shared launch helpers declared below, and the four flat launch paths
 //   api_search.hip   flat search entry points: one group, the fused batches, the host API with its pinned slots, search_multi,
-//                    the score-threshold (range) search, the grouped (collapsed) search
+//                    the score-threshold (range) search, the grouped (collapsed) search, the terms aggregation
 //   api_ivf.hip      IVF build, persistence, probe, delta and batch
 //   api_allow.hip    the allow-list search (top-k within a per-query row bitmap), its bitmap builders and its plan
 //   api_compact.hip  compaction of a flat index, its layout epoch, the stateless wrappers of compact.hip
@@ -207,6 +207,31 @@ struct GroupIoView {
 };
 GroupIoView group_io_layout(unsigned char* base);
 
+// An aggregation's table block (eng->d_group as well, one launch group): the status word, one 64-bit best-row slot and one
+// 32-bit counter per (query, group).  All adjacent: one memset zeroes the three.  Up to 384 MiB.
+struct AggView {
+    unsigned* status;              // [1] on a 256-byte line
+    unsigned long long* best;      // [nq][n_groups]
+    unsigned* count;               // [nq][n_groups]
+    size_t total;
+};
+AggView agg_layout(unsigned char* base, int nq, int n_groups);
+
+// The host aggregation's device staging (eng->d_group_io as well: the larger of the two layouts is kept): thresholds in,
+// per-query figures, status and bucket lists out, of one launch group.
+struct AggIoView {
+    float* thr;                    // [32]
+    int64_t* n_buckets;            // [32]
+    int64_t* total_hits;           // [32]
+    int32_t* status;               // [1]
+    int32_t* out_groups;           // [32][kGroupMaxK]; a call uses [nq][size]
+    int64_t* out_counts;
+    float* out_scores;
+    int64_t* out_ids;
+    size_t bytes;
+};
+AggIoView agg_io_layout(unsigned char* base);
+
 // A grow-on-demand device block (eng->d_batch, eng->d_cert, rass_ivf::d_batch): at least `need` bytes afterwards.  Growth
 // waits for the stream first: an earlier call on it may still read the old block.
 int grow_block(unsigned char** block, size_t* bytes, size_t need, hipStream_t st);
@@ -226,6 +251,7 @@ struct HostSlot {
     void* h_items = nullptr;       // pinned work list of a cross-index batch (lazily allocated, kMultiMaxItems)
     void* h_range = nullptr;       // pinned image of a RangeIoView: the host range search's group (lazily allocated)
     void* h_group = nullptr;       // pinned image of a GroupIoView: the host grouped search's group (lazily allocated)
+    void* h_agg = nullptr;         // pinned image of an AggIoView: the host aggregation's group (lazily allocated)
     hipEvent_t done = nullptr;
     bool busy = false;
 };

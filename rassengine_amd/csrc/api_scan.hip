@@ -190,6 +190,31 @@ GroupIoView group_io_layout(unsigned char* base) {
     return L;
 }
 
+AggView agg_layout(unsigned char* base, int nq, int n_groups) {
+    Carver c{base};
+    AggView L;
+    L.status = c.take<unsigned>(sizeof(unsigned));
+    L.best = c.take<unsigned long long>((size_t)nq * n_groups * sizeof(unsigned long long));
+    L.count = c.take<unsigned>((size_t)nq * n_groups * sizeof(unsigned));
+    L.total = c.off;
+    return L;
+}
+
+AggIoView agg_io_layout(unsigned char* base) {
+    Carver c{base};
+    AggIoView L;
+    L.thr = c.take<float>(RASS_MAX_QBATCH * sizeof(float));
+    L.n_buckets = c.take<int64_t>(RASS_MAX_QBATCH * sizeof(int64_t));
+    L.total_hits = c.take<int64_t>(RASS_MAX_QBATCH * sizeof(int64_t));
+    L.status = c.take<int32_t>(sizeof(int32_t));
+    L.out_groups = c.take<int32_t>((size_t)RASS_MAX_QBATCH * rass::kGroupMaxK * sizeof(int32_t));
+    L.out_counts = c.take<int64_t>((size_t)RASS_MAX_QBATCH * rass::kGroupMaxK * sizeof(int64_t));
+    L.out_scores = c.take<float>((size_t)RASS_MAX_QBATCH * rass::kGroupMaxK * sizeof(float));
+    L.out_ids = c.take<int64_t>((size_t)RASS_MAX_QBATCH * rass::kGroupMaxK * sizeof(int64_t));
+    L.bytes = c.off;
+    return L;
+}
+
 int grow_block(unsigned char** block, size_t* bytes, size_t need, hipStream_t st) {
     if (*bytes >= need) return RASS_OK;
     HIP_TRY(hipStreamSynchronize(st));   // growth only: the block may still be read by an earlier call

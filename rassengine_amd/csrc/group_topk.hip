@@ -8,6 +8,12 @@
 // with the keys re-read from the table each pass — finds the k-th largest key; rows are distinct, so keys are unique and
 // exactly k slots hold a key >= it.  The taken keys meet their slot indices in LDS (4 096 x 12 bytes), a bitonic network
 // sorts them as range_finish_kernel (merge_topk.hip) sorts its keys, and the rows are translated and written.
+//
+// The same kernel under COUNT finishes a terms aggregation (scan_topk.hip kGroupCount; kernels.h launch_group_count_select):
+// the sort key of slot g is made on the fly from the slot's 32-bit counter, ((uint64)count << 32) | (0xffffffff - g), 0 for an
+// empty slot — doc_count descending, then group key ascending, OpenSearch's default bucket order.  Slots are distinct, so these
+// keys are unique too and the select, the gather and the sort are the ones above.  A listed bucket's score and id come from
+// the slot of the group-max table the scan kept next to the counters; the counters' sum is the query's number of hits.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -31,30 +37,58 @@ __device__ __forceinline__ void hist_add(unsigned* hist, bool on, unsigned digit
     if (on && !same) atomicAdd(&hist[digit], 1u);
 }
 
-__global__ __launch_bounds__(kGroupSelThreads) void group_select_kernel(const unsigned long long* __restrict__ table, int n_groups, int k,
+// COUNT = false: the grouped search (counts, out_counts, total_hits unused).  COUNT = true: the terms aggregation.
+template <bool COUNT>
+__global__ __launch_bounds__(kGroupSelThreads) void group_select_kernel(const unsigned long long* __restrict__ table,
+                                                                        const unsigned* __restrict__ counts, int n_groups, int k,
                                                                         int64_t id_base, const int64_t* __restrict__ id_map,
                                                                         float* __restrict__ out_scores, int64_t* __restrict__ out_ids,
-                                                                        int32_t* __restrict__ out_groups, int64_t* __restrict__ total,
+                                                                        int32_t* __restrict__ out_groups, int64_t* __restrict__ out_counts,
+                                                                        int64_t* __restrict__ total, int64_t* __restrict__ total_hits,
                                                                         const unsigned* __restrict__ status, int32_t* __restrict__ out_status) {
     __shared__ unsigned long long keys[kGroupMaxK];
     __shared__ int grp[kGroupMaxK];
     __shared__ unsigned hist[256];
     __shared__ int sh_digit, sh_rank, n_sel, n_live;
+    __shared__ unsigned long long n_hits;
     const int q = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const unsigned long long* tab = table + (int64_t)q * n_groups;
+    const unsigned* cnt = COUNT ? counts + (int64_t)q * n_groups : nullptr;
+    // the sort key of slot i: the group's best candidate key, or (count, 0xffffffff - i); 0 = an empty slot
+    auto key_of = [&](int i) -> unsigned long long {
+        if (!COUNT) return tab[i];
+        const unsigned c = cnt[i];
+        return c != 0u ? ((unsigned long long)c << 32) | (unsigned long long)(0xffffffffu - (unsigned)i) : 0ull;
+    };
     if (tid == 0) {
         n_sel = 0;
         n_live = 0;
+        n_hits = 0ull;
     }
     __syncthreads();
     int mine = 0;
-    for (int i = tid; i < n_groups; i += kGroupSelThreads) mine += tab[i] != 0ull ? 1 : 0;
+    unsigned long long hits = 0ull;
+    for (int i = tid; i < n_groups; i += kGroupSelThreads) {
+        if (COUNT) {
+            const unsigned c = cnt[i];
+            mine += c != 0u ? 1 : 0;
+            hits += c;
+        } else {
+            mine += tab[i] != 0ull ? 1 : 0;
+        }
+    }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) mine += __shfl_xor(mine, o, 64);
     if (lane == 0 && mine) atomicAdd(&n_live, mine);
+    if (COUNT) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) hits += __shfl_xor(hits, o, 64);
+        if (lane == 0 && hits) atomicAdd(&n_hits, hits);
+    }
     __syncthreads();
     const int live = n_live;
     if (tid == 0) total[q] = (int64_t)live;
+    if (COUNT && tid == 0) total_hits[q] = (int64_t)n_hits;
     if (tid == 0 && q == 0) *out_status = *status != 0u ? 1 : 0;   // the scan's out-of-range flag, handed to the caller
 
     // T: the k-th largest key where more than k slots are taken (selected = keys >= T), else 1 (every non-zero slot)
@@ -68,7 +102,7 @@ __global__ __launch_bounds__(kGroupSelThreads) void group_select_kernel(const un
             // whole rounds of the workgroup: hist_add's ballots need every lane of a wave in the same iteration
             for (int i0 = 0; i0 < n_groups; i0 += kGroupSelThreads) {
                 const int i = i0 + tid;
-                const unsigned long long key = i < n_groups ? tab[i] : 0ull;
+                const unsigned long long key = i < n_groups ? key_of(i) : 0ull;
                 hist_add(hist, key != 0ull && (key & pmask) == prefix, (unsigned)(key >> shift) & 255u);
             }
             __syncthreads();
@@ -110,7 +144,7 @@ __global__ __launch_bounds__(kGroupSelThreads) void group_select_kernel(const un
     int n2 = 1;
     while (n2 < n) n2 <<= 1;
     for (int i = tid; i < n_groups; i += kGroupSelThreads) {
-        const unsigned long long key = tab[i];
+        const unsigned long long key = key_of(i);
         if (key >= T) {
             const int pos = atomicAdd(&n_sel, 1);
             if (pos < kGroupMaxK) {
@@ -142,18 +176,20 @@ __global__ __launch_bounds__(kGroupSelThreads) void group_select_kernel(const un
     int32_t* og = out_groups + (int64_t)q * k;
     for (int i = tid; i < k; i += kGroupSelThreads) {
         float s = -INFINITY;
-        int64_t id = -1;
+        int64_t id = -1, c = 0;
         int32_t g = -1;
         if (i < n) {
-            const unsigned long long key = keys[i];
+            g = grp[i];
+            c = COUNT ? (int64_t)(keys[i] >> 32) : 0;
+            const unsigned long long key = COUNT ? tab[g] : keys[i];   // the bucket's best row: a counted slot has one
             const int64_t row = (int64_t)(0xffffffffu - (unsigned)key);
             s = key_score((unsigned)(key >> 32));
             id = id_map ? id_map[row] : id_base + row;
-            g = grp[i];
         }
         os[i] = s;
         oi[i] = id;
         og[i] = g;
+        if (COUNT) out_counts[(int64_t)q * k + i] = c;
     }
 }
 
@@ -163,8 +199,20 @@ hipError_t launch_group_select(const unsigned long long* table, int nq, int n_gr
     if (nq < 1 || k < 1 || k > kGroupMaxK || n_groups < 1 || n_groups > kGroupMaxGroups || !table || !out_scores || !out_ids ||
         !out_groups || !total || !status || !out_status)
         return hipErrorInvalidValue;
-    hipLaunchKernelGGL(group_select_kernel, dim3(nq), dim3(kGroupSelThreads), 0, stream, table, n_groups, k, id_base, id_map, out_scores,
-                       out_ids, out_groups, total, status, out_status);
+    hipLaunchKernelGGL(group_select_kernel<false>, dim3(nq), dim3(kGroupSelThreads), 0, stream, table, (const unsigned*)nullptr, n_groups, k,
+                       id_base, id_map, out_scores, out_ids, out_groups, (int64_t*)nullptr, total, (int64_t*)nullptr, status, out_status);
+    return hipGetLastError();
+}
+
+hipError_t launch_group_count_select(const unsigned* counts, const unsigned long long* best, int nq, int n_groups, int size, int64_t id_base,
+                                     const int64_t* id_map, int32_t* out_groups, int64_t* out_counts, float* out_scores, int64_t* out_ids,
+                                     int64_t* n_buckets, int64_t* total_hits, const unsigned* status, int32_t* out_status,
+                                     hipStream_t stream) {
+    if (nq < 1 || size < 1 || size > kGroupMaxK || n_groups < 1 || n_groups > kGroupMaxGroups || !counts || !best || !out_groups ||
+        !out_counts || !out_scores || !out_ids || !n_buckets || !total_hits || !status || !out_status)
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(group_select_kernel<true>, dim3(nq), dim3(kGroupSelThreads), 0, stream, best, counts, n_groups, size, id_base,
+                       id_map, out_scores, out_ids, out_groups, out_counts, n_buckets, total_hits, status, out_status);
     return hipGetLastError();
 }
 

@@ -93,6 +93,13 @@ struct ScanArgs {
     // words of its two queries of a ranking step with scalar loads: they take no vector register and no LDS.
     const uint32_t* allow = nullptr;
     int64_t allow_q_stride = 0;
+    // Group-count scan (kGroupCount; count_table != nullptr selects it, with group_table, group_status, group_mask / shift / n
+    // and range_thr set as for the two scans above: flat scans only, no sample floor, no continuation bound, `k` and part_*
+    // unused).  A row that is live, passes query q's filter and scores >= range_thr[q] (a NaN threshold matches nothing) is a
+    // HIT: count_table[q * group_n + key] += 1 and its candidate key is folded into group_table[q * group_n + key] (both
+    // zeroed by the caller).  A hit with key >= group_n is left out and sets *group_status to 1.  launch_group_count_select
+    // turns the two tables into the answer.
+    unsigned* count_table = nullptr;
 };
 constexpr int kRangeCountStride = 32;   // one 128-byte line per query's counter: every workgroup adds to all of them
 constexpr int kRangeMaxHits = 4096;     // = RASS_MAX_K_MULTIPASS: 4 096 64-bit sort keys are range_finish's 32 KiB of LDS
@@ -141,6 +148,15 @@ constexpr int kGroupMaxGroups = 1 << 20;  // the exclusive bound of a group key:
 hipError_t launch_group_select(const unsigned long long* table, int nq, int n_groups, int k, int64_t id_base, const int64_t* id_map,
                                float* out_scores, int64_t* out_ids, int32_t* out_groups, int64_t* total, const unsigned* status,
                                int32_t* out_status, hipStream_t stream);
+// The answer of a group-count scan, by the same kernel.  counts / best [nq][n_groups]: each group's number of hits and its best
+// candidate key.  n_buckets[q] = the number of non-zero counters, total_hits[q] = their sum.  The `size` first buckets (all of
+// them where n_buckets <= size) under (count desc, group asc): out_groups / out_counts / out_scores / out_ids [nq][size] = the
+// slot index, its counter, and the score and id of its best row as above; (-1, 0, -inf, -1) past the end.
+// 1 <= size <= kGroupMaxK.  With both tables a 32-query group at kGroupMaxGroups is 384 MiB.
+hipError_t launch_group_count_select(const unsigned* counts, const unsigned long long* best, int nq, int n_groups, int size, int64_t id_base,
+                                     const int64_t* id_map, int32_t* out_groups, int64_t* out_counts, float* out_scores, int64_t* out_ids,
+                                     int64_t* n_buckets, int64_t* total_hits, const unsigned* status, int32_t* out_status,
+                                     hipStream_t stream);
 
 // ---- allow-list search (allow.hip): row bitmaps, their work list, and the store of a pass.  A bitmap is uint32 words, bit
 // (r & 31) of word r >> 5 allows row r.  Plain vector loads, stores and atomics.

@@ -60,11 +60,14 @@ struct WorkItem {
 // as kIvf does — the tiles in which some query of the launch group has a bit set (allow.hip builds it) — and a row ranks for
 // query q only where bit (row & 31) of q's word of the tile is set.  No sample pass and no floor: a floor is only valid under
 // the predicate it was sampled with.
+// kGroupCount: kRange's hits, emitted as kGroupMax emits: every row scoring >= the query's threshold adds 1 to the counter of
+// its (query, group) slot and is folded into the slot's running maximum (emit_group_count below; ScanArgs::count_table with
+// group_* and range_thr), for the terms aggregation.  No sample pass, no floor, no TopList.
 enum ScanMode { kFlat = 0, kIvf = 1, kMulti = 2, kFlatSample = 3, kFlatGroups = 4, kIvfGroups = 5, kFlatSampleGroups = 6, kRange = 7,
-                kGroupMax = 8, kAllow = 9 };
+                kGroupMax = 8, kAllow = 9, kGroupCount = 10 };
 constexpr bool mode_is_flat(int mode) {
     return mode == kFlat || mode == kFlatSample || mode == kFlatGroups || mode == kFlatSampleGroups || mode == kRange ||
-           mode == kGroupMax;
+           mode == kGroupMax || mode == kGroupCount;
 }
 constexpr bool mode_is_sample(int mode) { return mode == kFlatSample || mode == kFlatSampleGroups; }
 
@@ -271,6 +274,42 @@ __device__ __forceinline__ void emit_group_max(bool ok, float s, int row, int ta
     const unsigned long long key = cand_key(s, row);
     unsigned long long* slot = table_q + g;
     if (key > __hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(slot, key);
+}
+
+// The emission of a group-count scan (kGroupCount), in the place of insert_candidates: a half-wave holds one query's 32 rows
+// of a tile, `hit` says which of them count (live, filters passed, a real query, score >= the query's threshold).  A hit
+// whose group key is >= n_groups is left out and sets *status, as in emit_group_max.  Slot of a hit: q * n_groups + g of
+// `count` (32-bit, zeroed by the caller) and of `best` (emit_group_max's table).  A document's chunks are adjacent rows, so the
+// hits of a half usually share one group: where every hit lane of a half agrees with the half's first hit lane (ballot,
+// readlane), that lane adds the half's number of hits once, as emit_range does; otherwise every hit lane adds 1.  Integer
+// adds commute: the counters are a function of the input alone either way.  The best row is folded in exactly as
+// emit_group_max does it.  Both tables are addressed by one 32-bit slot index (< 2^25) from wave-uniform bases.
+// Plain vector loads, stores and atomics.
+__device__ __forceinline__ void emit_group_count(bool hit, float s, int row, int tag, int q, int group_mask, int group_shift,
+                                                 int n_groups, unsigned long long* best, unsigned* count, unsigned* status) {
+    const unsigned g = (unsigned)(tag & group_mask) >> group_shift;
+    const bool inside = g < (unsigned)n_groups;
+    if (hit && !inside) __hip_atomic_store(status, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    hit = hit && inside;
+    const unsigned long long b = __ballot(hit);
+    if (b == 0) return;   // wave-uniform
+    const unsigned lo = (unsigned)b, hi = (unsigned)(b >> 32);
+    // the first hit lane of each half (a half without hits: any lane of it, nothing is compared with its key)
+    const int f_lo = __builtin_amdgcn_readfirstlane(lo ? __builtin_ctz(lo) : 0);
+    const int f_hi = __builtin_amdgcn_readfirstlane(hi ? 32 + __builtin_ctz(hi) : 32);
+    const unsigned g_lo = (unsigned)__builtin_amdgcn_readlane((int)g, f_lo), g_hi = (unsigned)__builtin_amdgcn_readlane((int)g, f_hi);
+    const int lane = lane_id();
+    const bool upper = (lane & 32) != 0;
+    const unsigned long long d = __ballot(hit && g != (upper ? g_hi : g_lo));
+    const bool shared = (upper ? (unsigned)(d >> 32) : (unsigned)d) == 0u;   // my half's hits are of one group
+    if (!hit) return;
+    const unsigned slot = (unsigned)q * (unsigned)n_groups + g;
+    if (!shared)
+        atomicAdd(count + slot, 1u);
+    else if (lane == (upper ? f_hi : f_lo))
+        atomicAdd(count + slot, (unsigned)__popc(upper ? hi : lo));
+    const unsigned long long key = cand_key(s, row);
+    if (key > __hip_atomic_load(best + slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(best + slot, key);
 }
 
 // Half-wave sorted list: lanes 0..31 hold query A's best-first top-32, lanes 32..63 query B's.

@@ -179,13 +179,13 @@ __global__ __launch_bounds__(kThreads, 2) void scan_topk_f32_kernel(ScanArgs p) 
     __shared__ int sh_qmask[32];
     __shared__ float sh_after_s[32];
     __shared__ int64_t sh_after_i[32];
-    __shared__ float sh_thr[32];    // kRange: the per-query score thresholds (NaN past nq: nothing matches)
+    __shared__ float sh_thr[32];    // kRange, kGroupCount: the per-query score thresholds (NaN past nq: nothing matches)
     if (threadIdx.x < 32) {
         const int q = threadIdx.x;
         const bool live = q < p.nq;
         sh_qfilt[q] = (p.q_filter != nullptr && live) ? p.q_filter[q] : -1;
         sh_floor[q] = -INFINITY;
-        if (MODE == kRange) sh_thr[q] = live ? p.range_thr[q] : __builtin_nanf("");
+        if (MODE == kRange || MODE == kGroupCount) sh_thr[q] = live ? p.range_thr[q] : __builtin_nanf("");
         if (EXT) {
             sh_qmask[q] = (p.q_filter_mask != nullptr && live) ? p.q_filter_mask[q] : -1;
             sh_after_s[q] = (p.q_after_score != nullptr && live) ? p.q_after_score[q] : INFINITY;
@@ -308,6 +308,11 @@ __global__ __launch_bounds__(kThreads, 2) void scan_topk_f32_kernel(ScanArgs p) 
                            p.group_table + (int64_t)q * p.group_n, p.group_status);
             return;
         }
+        if (MODE == kGroupCount) {   // kRange's hits, counted per (query, group) slot; the slot's best row as kGroupMax keeps it
+            emit_group_count(ok && s >= sh_thr[q], s, row, tag, q, p.group_mask, p.group_shift, p.group_n, p.group_table, p.count_table,
+                             p.group_status);
+            return;
+        }
         // the sample floor: k rows of the corpus already score >= floor_q, so a row below it cannot be in the
         // query's top-k (ties are kept: the id order decides them in the merge)
         const float floor_q = MODE == kFlat ? sh_floor[q] : -INFINITY;
@@ -395,7 +400,7 @@ __global__ __launch_bounds__(kThreads, 2) void scan_topk_f32_kernel(ScanArgs p) 
     if (threadIdx.x == 0) g_scan_clocks[2 * blockIdx.x + 1] = wall_clock64();
     if (threadIdx.x == 0 && blockIdx.x == 0) g_scan_core[1] = clock64();
 #endif
-    if (MODE == kRange || MODE == kGroupMax) return;   // everything was emitted on the way
+    if (MODE == kRange || MODE == kGroupMax || MODE == kGroupCount) return;   // everything was emitted on the way
     if (mode_is_sample(MODE)) {
         // The sample pass: this workgroup's best score per query -> part_scores[32][kMaxSampleGroups] (-inf: no row of the
         // sample passed the query's filters); the big scan's waves take the k-th largest over the workgroups.
@@ -641,9 +646,9 @@ __device__ __forceinline__ void wide_panels(TileRegs<CHP>& R0, TileRegs<CHP>& R1
     }
 }
 
-template <int CHP, int P, bool EXT, bool RANGE, bool GROUP>
+template <int CHP, int P, bool EXT, bool RANGE, bool GROUP, bool COUNT>
 __global__ __launch_bounds__(kThreads, 2) void scan_topk_f32_wide_kernel(ScanArgs p) {
-    static_assert(!(RANGE && GROUP), "one emission per kernel");
+    static_assert((int)RANGE + (int)GROUP + (int)COUNT <= 1, "one emission per kernel");
     static_assert(P == 2 || P == 4, "R0 holds the even panels, R1 the odd ones");
     constexpr int NQ = 16, CHT = P * CHP;
     extern __shared__ __attribute__((aligned(16))) float lds[];  // [4][kWaves][NQ][kPitch]
@@ -673,12 +678,12 @@ __global__ __launch_bounds__(kThreads, 2) void scan_topk_f32_wide_kernel(ScanArg
     __shared__ int sh_qmask[16];
     __shared__ float sh_after_s[16];
     __shared__ int64_t sh_after_i[16];
-    __shared__ float sh_thr[16];    // RANGE: the per-query score thresholds (NaN past nq: nothing matches)
+    __shared__ float sh_thr[16];    // RANGE, COUNT: the per-query score thresholds (NaN past nq: nothing matches)
     if (threadIdx.x < 16) {
         const int q = threadIdx.x;
         const bool live = q < p.nq;
         sh_qfilt[q] = (p.q_filter != nullptr && live) ? p.q_filter[q] : -1;
-        if (RANGE) sh_thr[q] = live ? p.range_thr[q] : __builtin_nanf("");
+        if (RANGE || COUNT) sh_thr[q] = live ? p.range_thr[q] : __builtin_nanf("");
         if (EXT) {
             sh_qmask[q] = (p.q_filter_mask != nullptr && live) ? p.q_filter_mask[q] : -1;
             sh_after_s[q] = (p.q_after_score != nullptr && live) ? p.q_after_score[q] : INFINITY;
@@ -733,6 +738,11 @@ __global__ __launch_bounds__(kThreads, 2) void scan_topk_f32_wide_kernel(ScanArg
                            p.group_table + (int64_t)q * p.group_n, p.group_status);
             return;
         }
+        if (COUNT) {   // the emission of scan_topk_f32_kernel's kGroupCount mode
+            emit_group_count(ok && s >= sh_thr[q], s, row, tag, q, p.group_mask, p.group_shift, p.group_n, p.group_table, p.count_table,
+                             p.group_status);
+            return;
+        }
         s = ok ? s : -INFINITY;
         insert_candidates(L, tau, s, row, p.k);
     };
@@ -764,7 +774,7 @@ __global__ __launch_bounds__(kThreads, 2) void scan_topk_f32_wide_kernel(ScanArg
     }
     rank_tile(Pa, pair ^ 2);
     rank_tile(Pb, (pair ^ 2) + 1);
-    if (RANGE || GROUP) return;
+    if (RANGE || GROUP || COUNT) return;
 
     const int lpos = lane & 31;
     const int q = (lane >> 5) * 8 + wid;
@@ -776,27 +786,27 @@ __global__ __launch_bounds__(kThreads, 2) void scan_topk_f32_wide_kernel(ScanArg
     }
 }
 
-template <int CHP, int P, bool EXT, bool RANGE, bool GROUP>
+template <int CHP, int P, bool EXT, bool RANGE, bool GROUP, bool COUNT>
 static hipError_t launch_wide_variant(const ScanArgs& a, int grid, hipStream_t stream) {
     constexpr size_t lds_bytes = (size_t)4 * kWaves * 16 * kPitch * sizeof(float);  // 72 KiB
     static bool attr_set = false;
     if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&scan_topk_f32_wide_kernel<CHP, P, EXT, RANGE, GROUP>),
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&scan_topk_f32_wide_kernel<CHP, P, EXT, RANGE, GROUP, COUNT>),
                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
         if (e != hipSuccess) return e;
         attr_set = true;
     }
-    hipLaunchKernelGGL((scan_topk_f32_wide_kernel<CHP, P, EXT, RANGE, GROUP>), dim3(grid), dim3(kThreads), lds_bytes, stream, a);
+    hipLaunchKernelGGL((scan_topk_f32_wide_kernel<CHP, P, EXT, RANGE, GROUP, COUNT>), dim3(grid), dim3(kThreads), lds_bytes, stream, a);
     return hipGetLastError();
 }
 
-template <bool EXT, bool RANGE = false, bool GROUP = false>
+template <bool EXT, bool RANGE = false, bool GROUP = false, bool COUNT = false>
 static hipError_t launch_wide(int ch_total, const ScanArgs& a, int grid, hipStream_t stream) {
     switch (ch_total) {
-        case 10: return launch_wide_variant<5, 2, EXT, RANGE, GROUP>(a, grid, stream);
-        case 12: return launch_wide_variant<6, 2, EXT, RANGE, GROUP>(a, grid, stream);
-        case 14: return launch_wide_variant<7, 2, EXT, RANGE, GROUP>(a, grid, stream);
-        case 16: return launch_wide_variant<4, 4, EXT, RANGE, GROUP>(a, grid, stream);   // 2 x 8 chunks spill (256 VGPRs at 2 waves per SIMD)
+        case 10: return launch_wide_variant<5, 2, EXT, RANGE, GROUP, COUNT>(a, grid, stream);
+        case 12: return launch_wide_variant<6, 2, EXT, RANGE, GROUP, COUNT>(a, grid, stream);
+        case 14: return launch_wide_variant<7, 2, EXT, RANGE, GROUP, COUNT>(a, grid, stream);
+        case 16: return launch_wide_variant<4, 4, EXT, RANGE, GROUP, COUNT>(a, grid, stream);   // 2 x 8 chunks spill (256 VGPRs at 2 waves per SIMD)
         default: return hipErrorInvalidValue;
     }
 }
@@ -899,6 +909,22 @@ hipError_t launch_scan_topk_f32(const ScanArgs& a, int grid, hipStream_t stream)
         }
         if (a.nq <= 16) return ext ? launch_ch<1, kRange, true>(ch, a, grid, stream) : launch_ch<1, kRange>(ch, a, grid, stream);
         return ext ? launch_ch<2, kRange, true>(ch, a, grid, stream) : launch_ch<2, kRange>(ch, a, grid, stream);
+    }
+    if (a.count_table != nullptr) {  // the group-count scan: flat, every stride, plain or masked filters, nothing else
+        if (!a.group_table || !a.group_status || !a.range_thr || !a.row_tag || a.group_mask <= 0 || a.group_n < 1 ||
+            a.group_n > kGroupMaxGroups || a.nq < 1 || a.nq > 32)
+            return hipErrorInvalidValue;
+        if (a.group_shift != __builtin_ctz((unsigned)a.group_mask)) return hipErrorInvalidValue;
+        if (a.q_after_score || a.q_after_id || a.work_tile || a.work_base || a.sample_pass || a.sample_best || a.wgs_per_group ||
+            a.live_nq)
+            return hipErrorInvalidValue;
+        if (a.q_filter_mask != nullptr && a.q_filter == nullptr) return hipErrorInvalidValue;
+        if (ch > 8) {
+            if (a.nq > 16) return hipErrorInvalidValue;   // the caller splits larger groups, as for the top-k scan
+            return ext ? launch_wide<true, false, false, true>(ch, a, grid, stream) : launch_wide<false, false, false, true>(ch, a, grid, stream);
+        }
+        if (a.nq <= 16) return ext ? launch_ch<1, kGroupCount, true>(ch, a, grid, stream) : launch_ch<1, kGroupCount>(ch, a, grid, stream);
+        return ext ? launch_ch<2, kGroupCount, true>(ch, a, grid, stream) : launch_ch<2, kGroupCount>(ch, a, grid, stream);
     }
     if (a.group_table != nullptr) {  // the group-max scan: flat, every stride, plain or masked filters, nothing else
         if (!a.group_status || !a.row_tag || a.group_mask <= 0 || a.group_n < 1 || a.group_n > kGroupMaxGroups || a.nq < 1 || a.nq > 32)

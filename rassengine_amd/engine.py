@@ -507,6 +507,81 @@ class FlatIndex:
                                                          ctypes.c_void_p(d_out_groups_ptr), ctypes.c_void_p(d_group_total_ptr),
                                                          ctypes.c_void_p(d_status_ptr)))
 
+    @staticmethod
+    def _check_counts(size, group_mask, n_groups) -> Tuple[int, int, int]:
+        size = int(size)
+        if not 1 <= size <= N.RASS_MAX_K_MULTIPASS:
+            raise ValueError(f"size must be in [1, {N.RASS_MAX_K_MULTIPASS}], got {size}")
+        _, group_mask, n_groups = FlatIndex._check_grouped(1, group_mask, n_groups)
+        return size, group_mask, n_groups
+
+    def search_counts(self, queries: np.ndarray, min_score, size: int, group_mask: int, n_groups: int,
+                      q_filter: Optional[np.ndarray] = None, q_filter_mask: Optional[np.ndarray] = None
+                      ) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+        """Semantic terms aggregation, ``rass_index_aggregate``: the hits of query q are ``search_range``'s (live, filter
+        passed, score ``>= min_score[q]``; one float32 per query or one number for all; ``-inf`` allowed, NaN refused), the
+        group of a row is ``search_grouped``'s.  Returns (groups i32 [nq, size], counts i64 [nq, size], scores f32
+        [nq, size], ids i64 [nq, size], n_buckets i64 [nq], total_hits i64 [nq]): the ``size`` first buckets under (count
+        desc, group asc) with the score and id of each bucket's best hit, (-1, 0, -inf, -1) padding, the EXACT number of
+        groups with a hit and the EXACT number of hits (``search_range``'s total).  One corpus pass per 32 queries; always
+        the exact fp32 scan (the prefilter mode is ignored); fp32 indices only.  A hit whose group key is >= ``n_groups``
+        makes the call fail.  Thread-safe."""
+        q = np.ascontiguousarray(queries, dtype=np.float32)
+        if q.ndim != 2 or q.shape[1] != self.dim:
+            raise ValueError(f"expected [nq, {self.dim}] queries, got {q.shape}")
+        nq = q.shape[0]
+        thr = np.asarray(min_score)
+        if thr.dtype.kind not in "fiu":
+            raise ValueError(f"min_score must be real numbers, not {thr.dtype}")
+        if thr.ndim == 0:
+            thr = np.full(nq, thr)
+        thr = np.ascontiguousarray(thr, dtype=np.float32)
+        if thr.shape != (nq,):
+            raise ValueError("min_score must be one number, or one per query")
+        if np.isnan(thr).any():
+            raise ValueError("min_score must not be NaN")
+        size, group_mask, n_groups = self._check_counts(size, group_mask, n_groups)
+        f = m = None
+        if q_filter is not None:
+            f = np.ascontiguousarray(q_filter, dtype=np.int32)
+            if f.shape != (nq,):
+                raise ValueError("q_filter must be one int32 per query")
+        if q_filter_mask is not None:
+            if f is None:
+                raise ValueError("q_filter_mask needs q_filter")
+            m = np.ascontiguousarray(q_filter_mask, dtype=np.int32)
+            if m.shape != (nq,):
+                raise ValueError("q_filter_mask must be one int32 per query")
+        out_g = np.empty((nq, size), dtype=np.int32)
+        out_c = np.empty((nq, size), dtype=np.int64)
+        out_s = np.empty((nq, size), dtype=np.float32)
+        out_i = np.empty((nq, size), dtype=np.int64)
+        n_buckets = np.empty((nq,), dtype=np.int64)
+        total = np.empty((nq,), dtype=np.int64)
+        N.check("rass_index_aggregate",
+                self._L.rass_index_aggregate(self._h, _np_ptr(q), nq, _np_ptr(thr), size, group_mask, n_groups, _np_ptr(f),
+                                             _np_ptr(m), _np_ptr(out_g), _np_ptr(out_c), _np_ptr(out_s), _np_ptr(out_i),
+                                             _np_ptr(n_buckets), _np_ptr(total)))
+        return out_g, out_c, out_s, out_i, n_buckets, total
+
+    def search_counts_device(self, d_queries_ptr: int, nq: int, d_min_score_ptr: int, size: int, group_mask: int, n_groups: int,
+                             d_out_groups_ptr: int, d_out_counts_ptr: int, d_out_scores_ptr: int, d_out_ids_ptr: int,
+                             d_n_buckets_ptr: int, d_total_hits_ptr: int, d_status_ptr: int, id_base: int = 0,
+                             d_q_filter_ptr: int = 0, d_q_filter_mask_ptr: int = 0) -> None:
+        """Async, device-resident ``search_counts`` (``rass_index_aggregate_device``); nq <= 32.  A NaN threshold matches
+        nothing.  ``*d_status`` (one int32) ends as 1 when a hit's group key was >= ``n_groups`` (that hit is left out of
+        every figure), else 0."""
+        size, group_mask, n_groups = self._check_counts(size, group_mask, n_groups)
+        N.check("rass_index_aggregate_device",
+                self._L.rass_index_aggregate_device(self._h, ctypes.c_void_p(d_queries_ptr), int(nq),
+                                                    ctypes.c_void_p(d_min_score_ptr), size, group_mask, n_groups,
+                                                    ctypes.c_void_p(d_q_filter_ptr or 0),
+                                                    ctypes.c_void_p(d_q_filter_mask_ptr or 0), int(id_base),
+                                                    ctypes.c_void_p(d_out_groups_ptr), ctypes.c_void_p(d_out_counts_ptr),
+                                                    ctypes.c_void_p(d_out_scores_ptr), ctypes.c_void_p(d_out_ids_ptr),
+                                                    ctypes.c_void_p(d_n_buckets_ptr), ctypes.c_void_p(d_total_hits_ptr),
+                                                    ctypes.c_void_p(d_status_ptr)))
+
     # ---- allow-list search: exact top-k within a per-query row bitmap
     @property
     def allow_words(self) -> int:

@@ -220,6 +220,64 @@ class HipIndexer:
                 return hits, int(totals[0])
         raise RuntimeError(f"{self.index_name}: the index was compacted during every one of {LAYOUT_ATTEMPTS} searches")
 
+    def semantic_aggregate(self, query_emb: np.ndarray, min_score: float, by: str = "patientId", size: int = 5,
+                           filter_clause: Optional[Dict] = None, patient_id: Optional[str] = None) -> Dict[str, Any]:
+        """A ``terms`` aggregation on ``by`` (``"patientId"`` or ``"doc_type"``) under the k-NN clause with a ``min_score``:
+        how many chunks score at least ``min_score``, of how many distinct values, and the ``size`` values with the most such
+        chunks, in one pass over the index (``FlatIndex.search_counts``).  ``min_score`` is in the units ``semantic_search``
+        returns (``RASS_SCORE_MODE``) and is converted to a cosine once.  Returns the shape of an OpenSearch ``terms``
+        aggregation with two additions::
+
+            {"buckets": [{"key": value (None: chunks without the field), "doc_count": int,
+                          "top_hit": (doc_dict, float(score))}, ...],       # doc_count desc, then first-indexed value first
+             "sum_other_doc_count": total - the listed doc_counts,
+             "cardinality": distinct values among the hits, "total": hits}
+
+        Filters as ``semantic_search``.  An empty embedding or an unindexed patient gives the empty aggregation with zeros;
+        errors raise (this method has no counterpart in the reference to mirror: ``aggregate_search`` ignores the query
+        text and stays with the text engine)."""
+        if by not in ("patientId", "doc_type"):
+            raise ValueError(f"by must be 'patientId' or 'doc_type', not {by!r}")
+        empty = {"buckets": [], "sum_other_doc_count": 0, "cardinality": 0, "total": 0}
+        if _empty(query_emb):
+            return empty
+        st: Optional[IndexState] = REGISTRY.get(self.index_name, create=False)
+        if st is None:
+            return empty
+        prep = self._prepare(st, query_emb, size, filter_clause, patient_id, None)
+        if prep is None:
+            return empty
+        q, size_eff, (fval, fmask) = prep
+        if not hasattr(st.index, "search_counts"):
+            raise NotImplementedError(f"{self.index_name}: {type(st.index).__name__} has no aggregation "
+                                      "(IVF-backed and sharded indices cannot count per group; use a flat fp32 index)")
+        thr = np.array([_cos_of_score(min_score)], dtype=np.float32)
+        if np.isnan(thr[0]):
+            raise ValueError("min_score must not be NaN")
+        group_mask = TAG_PATIENT_MASK if by == "patientId" else TAG_DOCTYPE_MASK
+        flt = dict(q_filter=np.array([fval], dtype=np.int32), q_filter_mask=np.array([fmask], dtype=np.int32)) if fmask else {}
+        for _ in range(LAYOUT_ATTEMPTS):    # top_hit ids belong to one layout of the index, as in _knn
+            layout = _layout_epoch(st.index)
+            # codes run 1 .. len, 0 = none; read per attempt: a concurrent ingest may have added a value
+            names = (st.patients if by == "patientId" else st.doc_types).names()
+            groups, counts, scores, ids, n_buckets, totals = st.index.search_counts(q, thr, size_eff, group_mask, len(names) + 1,
+                                                                                    **flt)
+            buckets = []
+            for g, c, s, i in zip(groups[0], counts[0], scores[0], ids[0]):
+                if g < 0:
+                    break
+                top = self._hits(st, [s], [i], 1.0, None, layout)
+                if top is None:
+                    buckets = None
+                    break
+                buckets.append({"key": names[int(g) - 1] if g > 0 else None, "doc_count": int(c),
+                                "top_hit": top[0] if top else None})
+            if buckets is not None:
+                total = int(totals[0])
+                return {"buckets": buckets, "sum_other_doc_count": total - sum(b["doc_count"] for b in buckets),
+                        "cardinality": int(n_buckets[0]), "total": total}
+        raise RuntimeError(f"{self.index_name}: the index was compacted during every one of {LAYOUT_ATTEMPTS} searches")
+
     def semantic_search_within(self, query_emb: np.ndarray, k: int = TOP_K, patient_ids: Optional[List[Any]] = None,
                                doc_types: Optional[List[str]] = None, doc_ids: Optional[List[str]] = None,
                                filter_clause: Optional[Dict] = None, patient_id: Optional[str] = None
