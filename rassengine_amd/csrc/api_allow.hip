@@ -132,55 +132,41 @@ int check_bitmap_target(const rass_index* idx, const uint32_t* d_allow, int64_t 
     return RASS_OK;
 }
 
-// One attempt of the host allowed search (one_layout runs it again when a compaction landed meanwhile): group by group, the
-// group's queries and filters through a pinned slot as rass_index_search_ex, its bitmaps and its [b][k] answer through the
-// engine's staging block.  The engine lock is held while enqueuing only.
+// One attempt of the host allowed search (host_groups): the group's queries and filters through a pinned slot as
+// rass_index_search_ex, its bitmaps and its [b][k] answer through the engine's own staging block (eng->d_allow_io).
 int search_allowed_once(rass_index_t* idx, const float* queries, int nq, int k, const uint32_t* allow, int n_bitmaps, int64_t words,
                         const int32_t* q_filter, const int32_t* q_filter_mask, float* out_scores, int64_t* out_ids) {
     rass_engine* eng = idx->eng;
-    int rc = set_device(eng);
-    if (rc != RASS_OK) return rc;
-    const int dim = idx->dim;
-    SlotGuard guard(eng);
-    HostSlot* sl = guard.sl;
     const bool shared = n_bitmaps == 1;
-    for (int done = 0; done < nq;) {
-        const int b = std::min(RASS_MAX_QBATCH, nq - done);
-        const size_t cells = (size_t)b * k;
-        slot_fill(sl, dim, queries + (int64_t)done * dim, q_filter ? q_filter + done : nullptr,
-                  q_filter_mask ? q_filter_mask + done : nullptr, b);
-        {
-            std::lock_guard<std::mutex> lk(eng->mu);
+    return host_groups(
+        // io_bytes 0: h_io / d_io are not used.  The staging is sized by the bitmaps, not by a fixed layout, and pageable on
+        // the host side (the caller's own arrays): it stays in eng->d_allow_io, grown below.
+        idx, queries, nq, q_filter, q_filter_mask, /*io_bytes=*/0, no_fill,
+        [&](HostSlot*, int done, int b) -> int {
             hipStream_t st = eng->stream;
+            const size_t cells = (size_t)b * k;
             Carver c{nullptr};
             const size_t bits_bytes = (size_t)(shared ? 1 : b) * words * sizeof(uint32_t);
             c.take<uint32_t>(bits_bytes);
             c.take<float>((size_t)RASS_MAX_QBATCH * k * sizeof(float));
             c.take<int64_t>((size_t)RASS_MAX_QBATCH * k * sizeof(int64_t));
-            rc = grow_block(&eng->d_allow_io, &eng->allow_io_bytes, c.off, st);
-            if (rc != RASS_OK) return rc;
+            if (int rc = grow_block(&eng->d_allow_io, &eng->allow_io_bytes, c.off, st)) return rc;
             Carver d{eng->d_allow_io};
             uint32_t* d_bits = d.take<uint32_t>(bits_bytes);
             float* d_s = d.take<float>((size_t)RASS_MAX_QBATCH * k * sizeof(float));
             int64_t* d_i = d.take<int64_t>((size_t)RASS_MAX_QBATCH * k * sizeof(int64_t));
-            rc = slot_upload(eng, sl, dim, q_filter != nullptr, q_filter_mask != nullptr, b);
-            if (rc != RASS_OK) return rc;
             if (bits_bytes)
                 HIP_TRY(hipMemcpyAsync(d_bits, allow + (shared ? 0 : (int64_t)done * words), bits_bytes, hipMemcpyHostToDevice, st));
             AllowRequest r;
             r.queries = eng->d_qraw, r.nq = b, r.k = k, r.allow = d_bits, r.q_stride = shared ? 0 : words, r.words = words;
             r.q_filter = q_filter ? eng->d_qfilter : nullptr, r.q_filter_mask = q_filter_mask ? eng->d_qmask : nullptr;
             r.out_scores = d_s, r.out_ids = d_i;
-            rc = allow_device_group(idx, r);
-            if (rc != RASS_OK) return rc;
+            if (int rc = allow_device_group(idx, r)) return rc;
             HIP_TRY(hipMemcpyAsync(out_scores + (int64_t)done * k, d_s, cells * sizeof(float), hipMemcpyDeviceToHost, st));
             HIP_TRY(hipMemcpyAsync(out_ids + (int64_t)done * k, d_i, cells * sizeof(int64_t), hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipEventRecord(sl->done, st));
-        }
-        HIP_TRY(hipEventSynchronize(sl->done));
-        done += b;
-    }
-    return RASS_OK;
+            return RASS_OK;
+        },
+        [](HostSlot*, int, int) -> int { return RASS_OK; });   // the answer was copied straight to the caller's arrays
 }
 
 }  // namespace

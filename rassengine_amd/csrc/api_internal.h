@@ -5,8 +5,10 @@
 //   api.hip          errors; the engine and the flat index: create / grow / add / delete / persist / destroy; timers, the
 //                    stateless wrappers, k-means, peer buffers
 //   api_scan.hip     the tuning switches, the shared launch helpers declared below, and the four flat launch paths
-//   api_search.hip   flat search entry points: one group, the fused batches, the host API with its pinned slots, search_multi,
-//                    the score-threshold (range) search, the grouped (collapsed) search, the terms aggregation
+//   api_search.hip   flat top-k search entry points: one group, the fused batches, the candidates hooks, the host API with
+//                    its pinned slots (k > 32 in passes), search_multi
+//   api_emit.hip     the searches that ride the exact scan and emit instead of ranking: the score-threshold (range) search,
+//                    the grouped (collapsed) search, the terms aggregation; their shared device-group driver
 //   api_ivf.hip      IVF build, persistence, probe, delta and batch
 //   api_allow.hip    the allow-list search (top-k within a per-query row bitmap), its bitmap builders and its plan
 //   api_compact.hip  compaction of a flat index, its layout epoch, the stateless wrappers of compact.hip
@@ -177,7 +179,7 @@ struct RangeView {
 };
 RangeView range_layout(unsigned char* base);
 
-// The host range search's device staging (eng->d_range): thresholds in, totals and lists out, of one launch group.
+// The host range search's staging (a view of eng->d_io, and of the slot's h_io): thresholds in, totals and lists out, of one launch group.
 struct RangeIoView {
     float* thr;                    // [32]
     int64_t* total;                // [32]
@@ -196,7 +198,7 @@ struct GroupView {
 };
 GroupView group_layout(unsigned char* base, int nq, int n_groups);
 
-// The host grouped search's device staging (eng->d_group_io): totals, status and lists out, of one launch group.
+// The host grouped search's staging (eng->d_io / the slot's h_io): totals, status and lists out, of one launch group.
 struct GroupIoView {
     int64_t* total;                // [32]
     int32_t* status;               // [1]
@@ -217,7 +219,7 @@ struct AggView {
 };
 AggView agg_layout(unsigned char* base, int nq, int n_groups);
 
-// The host aggregation's device staging (eng->d_group_io as well: the larger of the two layouts is kept): thresholds in,
+// The host aggregation's staging (eng->d_io / the slot's h_io): thresholds in,
 // per-query figures, status and bucket lists out, of one launch group.
 struct AggIoView {
     float* thr;                    // [32]
@@ -249,9 +251,8 @@ struct HostSlot {
     int64_t* h_scanned = nullptr;  // [1]
     void* base = nullptr;          // the one hipHostMalloc behind all of the above
     void* h_items = nullptr;       // pinned work list of a cross-index batch (lazily allocated, kMultiMaxItems)
-    void* h_range = nullptr;       // pinned image of a RangeIoView: the host range search's group (lazily allocated)
-    void* h_group = nullptr;       // pinned image of a GroupIoView: the host grouped search's group (lazily allocated)
-    void* h_agg = nullptr;         // pinned image of an AggIoView: the host aggregation's group (lazily allocated)
+    void* h_io = nullptr;          // pinned image of a Range / Group / AggIoView: the group of the call that owns the slot
+    size_t io_bytes = 0;           // (slot_grow_io: grown to the layout that call needs)
     hipEvent_t done = nullptr;
     bool busy = false;
 };
@@ -276,15 +277,14 @@ struct rass_engine {
     // workspace of the certified int8 search (prefilter mode 3): one pass of kCertQ queries, grown on demand
     unsigned char* d_cert = nullptr;
     size_t cert_bytes = 0;
-    // device staging of the host range search (RangeIoView), allocated by its first call
-    unsigned char* d_range = nullptr;
-    size_t range_bytes = 0;
-    // the grouped search: its table block (GroupView, grown on demand, up to 256 MiB) and the host variant's device staging
-    // (GroupIoView); both used under mu and in stream order, like d_scratch
+    // device staging of the host range / grouped / aggregation searches (Range / Group / AggIoView), grown to the layout a call
+    // needs; used under mu and in stream order, like d_scratch
+    unsigned char* d_io = nullptr;
+    size_t io_bytes = 0;
+    // the table block of the grouped search and the aggregation (GroupView / AggView, grown on demand, up to 384 MiB); used
+    // under mu and in stream order
     unsigned char* d_group = nullptr;
     size_t group_bytes = 0;
-    unsigned char* d_group_io = nullptr;
-    size_t group_io_bytes = 0;
     // the allow-list search (api_allow.hip): the work list and plan workspace of one launch group (AllowView), and the host
     // entry points' device staging (bitmaps, row / value lists in; lists out); both grown on demand, used under mu in stream order
     unsigned char* d_allow = nullptr;
@@ -554,6 +554,51 @@ struct SlotGuard {
 void slot_fill(HostSlot* sl, int dim, const float* queries, const int32_t* q_filter, const int32_t* q_filter_mask, int b);
 int slot_upload(rass_engine* eng, HostSlot* sl, int dim, bool filter, bool mask, int b);
 int slot_download(rass_engine* eng, HostSlot* sl, int b, int k, const int64_t* d_scanned = nullptr);
+// The slot's pinned staging block (h_io) at least `need` bytes.  Only the call that owns the slot touches the block; growth
+// waits for the slot's event first, so the block it frees has no copy in flight.
+int slot_grow_io(HostSlot* sl, size_t need);
+
+// One attempt of a host search that goes group by group (<= 32 queries) through a pinned slot; one_layout runs it again when
+// a compaction landed meanwhile.  Per group: the queries (filters, masks) to the slot and `fill(sl, done, b)` (what else the
+// group uploads from the slot's h_io), then under eng->mu -- held while ENQUEUING only: device staging and scratch are shared
+// by stream order -- their upload, `enqueue(sl, done, b)` (the group's own uploads, its device search, its downloads) and the
+// slot's event; the wait happens on that event without the lock, and `collect(sl, done, b)` hands the group's answer to the
+// caller.  io_bytes > 0: the slot's h_io holds at least that many bytes from the first `fill` on, eng->d_io when `enqueue`
+// runs.  The slot is released on return.
+inline void no_fill(HostSlot*, int, int) {}
+template <class Fill, class Enqueue, class Collect>
+int host_groups(rass_index* idx, const float* queries, int nq, const int32_t* q_filter, const int32_t* q_filter_mask, size_t io_bytes,
+                Fill&& fill, Enqueue&& enqueue, Collect&& collect) {
+    rass_engine* eng = idx->eng;
+    int rc = set_device(eng);
+    if (rc != RASS_OK) return rc;
+    const int dim = idx->dim;
+    SlotGuard guard(eng);
+    HostSlot* sl = guard.sl;
+    if ((rc = slot_grow_io(sl, io_bytes)) != RASS_OK) return rc;
+    for (int done = 0; done < nq;) {
+        const int b = std::min(RASS_MAX_QBATCH, nq - done);
+        slot_fill(sl, dim, queries + (int64_t)done * dim, q_filter ? q_filter + done : nullptr,
+                  q_filter_mask ? q_filter_mask + done : nullptr, b);
+        fill(sl, done, b);
+        {
+            std::lock_guard<std::mutex> lk(eng->mu);
+            if ((rc = grow_block(&eng->d_io, &eng->io_bytes, io_bytes, eng->stream)) != RASS_OK) return rc;
+            if ((rc = slot_upload(eng, sl, dim, q_filter != nullptr, q_filter_mask != nullptr, b)) != RASS_OK) return rc;
+            if ((rc = enqueue(sl, done, b)) != RASS_OK) return rc;
+            HIP_TRY(hipEventRecord(sl->done, eng->stream));
+        }
+        HIP_TRY(hipEventSynchronize(sl->done));
+        if ((rc = collect(sl, done, b)) != RASS_OK) return rc;
+        done += b;
+    }
+    return RASS_OK;
+}
+
+// One attempt of rass_index_search_ex (api_search.hip).  exact = true: every pass on the exact fp32 scan, whatever the index's
+// prefilter mode (the overflow fallback of the range search, whose answer may not depend on a candidate scan).
+int search_ex_once(rass_index* idx, const float* queries, int nq, int k, const int32_t* q_filter, const int32_t* q_filter_mask,
+                   float* out_scores, int64_t* out_ids, bool exact = false);
 
 }  // namespace host
 }  // namespace rass

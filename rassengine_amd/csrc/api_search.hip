@@ -1,8 +1,8 @@
-// api_search.hip — the C ABI of include/rass_engine.h: searching a flat index.  The dispatch of one launch group
+// api_search.hip — the C ABI of include/rass_engine.h: top-k search of a flat index.  The dispatch of one launch group
 // to its launch path (api_scan.hip), the two fused batches (fp32 and prefilter), the device entry points and the
-// candidates hooks, the host search API with its pinned slots (k > 32 in passes), the cross-index batch
-// rass_index_search_multi, the score-threshold search rass_index_search_range(_device), the grouped (collapsed) search
-// rass_index_search_grouped(_device) and the terms aggregation rass_index_aggregate(_device).  Host-side C++ only.  The objects and the threading rules: api_internal.h.
+// candidates hooks, the host search API with its pinned slots (k > 32 in passes) and the cross-index batch
+// rass_index_search_multi.  The searches that emit instead of ranking live in api_emit.hip, the allow-list search in
+// api_allow.hip.  Host-side C++ only.  The objects and the threading rules: api_internal.h.
 
 #include "api_internal.h"
 
@@ -52,12 +52,22 @@ int slot_download(rass_engine* eng, HostSlot* sl, int b, int k, const int64_t* d
     return RASS_OK;
 }
 
+int slot_grow_io(HostSlot* sl, size_t need) {
+    if (sl->io_bytes >= need) return RASS_OK;
+    HIP_TRY(hipEventSynchronize(sl->done));   // growth only: the last group staged through the old block has landed
+    if (sl->h_io) HIP_TRY(hipHostFree(sl->h_io));
+    sl->h_io = nullptr;
+    sl->io_bytes = 0;
+    HIP_TRY(hipHostMalloc(&sl->h_io, need, hipHostMallocDefault));
+    sl->io_bytes = need;
+    return RASS_OK;
+}
+
 namespace {
 
 // One launch group (<= 32 queries) of a device search; the caller holds eng->mu and has set the device.  r.id_base is the
 // caller's; row_tag / id_map come from the index.  one_pass = false: a pass of a k > RASS_MAX_K host search, which stays
-// on the exact scan whatever the prefilter mode.  exact = true: the exact scan whatever the mode and k (the overflow
-// fallback of a range search, whose answer may not depend on a candidate scan).
+// on the exact scan whatever the prefilter mode.  exact = true: the exact scan whatever the mode and k (search_ex_once).
 int search_device_group(rass_index* idx, FlatRequest r, bool one_pass = true, bool exact = false) {
     rass_engine* eng = idx->eng;
     const IndexView iv = index_view(idx, r.q_filter != nullptr, r.id_base, r.after_score != nullptr);
@@ -272,247 +282,6 @@ int prefilter_launch_batch(rass_index* idx, const FlatRequest& r, int64_t gs, in
     return RASS_OK;
 }
 
-// One launch group (<= 32 queries) of a range search: normalise -> zero the counters -> the range scan (two launches for
-// 17..32 queries on wide rows) -> range_finish.  Always the exact fp32 scan: the prefilter mode of the index is not looked
-// at.  Everything is a device pointer; the caller holds eng->mu, has set the device and has checked the arguments.
-struct RangeRequest {
-    const float* queries = nullptr;     // [nq][dim]
-    int nq = 0;
-    const float* min_score = nullptr;   // [nq]
-    int max_hits = 0;
-    const int32_t* q_filter = nullptr;
-    const int32_t* q_filter_mask = nullptr;
-    int64_t id_base = 0;
-    float* out_scores = nullptr;        // [nq][max_hits]
-    int64_t* out_ids = nullptr;
-    int64_t* total = nullptr;           // [nq]
-};
-int range_device_group(rass_index* idx, const RangeRequest& r) {
-    rass_engine* eng = idx->eng;
-    hipStream_t st = eng->stream;
-    const int nq = r.nq;
-    const IndexView iv = index_view(idx, r.q_filter != nullptr, r.id_base);
-    const int64_t stride = idx->stride;
-    if (iv.rows < 0 || iv.rows > 0x7fffffc0LL) return fail(RASS_ERR_INVALID, "n_rows out of range for one scan");
-    if (!rass::scan_supported_stride(stride) || stride > kMaxStride) return fail(RASS_ERR_UNSUPPORTED, kStrideMsg);
-    if (range_layout(nullptr).total > eng->scratch_bytes) return fail(RASS_ERR_INVALID, "scan workspace too small");
-    const RangeView L = range_layout(eng->d_scratch);
-    HIP_TRY(rass::launch_normalize_rows_f32(r.queries, idx->dim, L.q_padded, stride, nq, idx->dim, st, pad_nq(nq)));
-    HIP_TRY(hipMemsetAsync(L.count, 0, (size_t)RASS_MAX_QBATCH * rass::kRangeCountStride * sizeof(unsigned), st));
-    const int grid = scan_grid((iv.rows + 31) / 32, 1, eng->n_cus);
-    // wide rows: 16 queries per launch, as for the top-k scan (scan_launch)
-    const int per_launch = stride > kNarrowStride ? 16 : RASS_MAX_QBATCH;
-    for (int q0 = 0; q0 < nq; q0 += per_launch) {
-        rass::ScanArgs a;
-        a.corpus = iv.corpus;
-        a.row_tag = iv.row_tag;
-        a.q_padded = L.q_padded + (int64_t)q0 * stride;
-        a.q_filter = r.q_filter ? r.q_filter + q0 : nullptr;
-        a.q_filter_mask = r.q_filter_mask ? r.q_filter_mask + q0 : nullptr;
-        a.part_scores = nullptr;
-        a.part_ids = nullptr;
-        a.row_stride = stride;
-        a.id_base = 0;   // the hits name rows of the slab: range_finish translates them
-        a.n_rows = (int)iv.rows;
-        a.nq = std::min(per_launch, nq - q0);
-        a.k = 1;
-        a.xcd_skew = scan_xcd_skew(a.nq, grid, eng->n_cus);
-        a.range_thr = r.min_score + q0;
-        a.range_count = L.count + q0 * rass::kRangeCountStride;
-        a.range_hits = L.hits + (int64_t)q0 * r.max_hits;
-        a.range_cap = r.max_hits;
-        const int rc = timed_launch(eng, st, [&] { return HIP_RC(rass::launch_scan_topk_f32(a, grid, st)); });
-        if (rc != RASS_OK) return rc;
-    }
-    HIP_TRY(rass::launch_range_finish(L.count, L.hits, nq, r.max_hits, iv.id_base, iv.id_map, r.out_scores, r.out_ids, r.total, st));
-    return RASS_OK;
-}
-
-// The argument checks the two range entry points share.
-int check_range(const rass_index* idx, int max_hits, const int32_t* q_filter, const int32_t* q_filter_mask) {
-    if (max_hits < 1 || max_hits > RASS_MAX_K_MULTIPASS) return fail(RASS_ERR_INVALID, "max_hits must be in [1, RASS_MAX_K_MULTIPASS]");
-    if (q_filter_mask && !q_filter) return fail(RASS_ERR_INVALID, "q_filter_mask without q_filter");
-    if (idx->dtype != RASS_F32) return fail(RASS_ERR_UNSUPPORTED, "range search needs an fp32 index");
-    return RASS_OK;
-}
-
-// One launch group (<= 32 queries) of a grouped search: normalise -> zero the status word and the table -> the group-max
-// scan (two launches for 17..32 queries on wide rows) -> group_select.  Always the exact fp32 scan: the prefilter mode of
-// the index is not looked at.  Everything is a device pointer; the caller holds eng->mu, has set the device and has checked
-// the arguments.
-struct GroupRequest {
-    const float* queries = nullptr;     // [nq][dim]
-    int nq = 0;
-    int k = 0;
-    int32_t group_mask = 0;
-    int32_t n_groups = 0;
-    const int32_t* q_filter = nullptr;
-    const int32_t* q_filter_mask = nullptr;
-    int64_t id_base = 0;
-    float* out_scores = nullptr;        // [nq][k]
-    int64_t* out_ids = nullptr;
-    int32_t* out_groups = nullptr;
-    int64_t* total = nullptr;           // [nq]
-    int32_t* status = nullptr;          // [1]
-};
-
-// The table block at least `need` bytes.  The new block is allocated BEFORE the old one is let go: a failure leaves the engine
-// as it was.  Growth waits for the stream first: an earlier call on it may still use the old block.
-int grow_group_table(rass_engine* eng, size_t need, hipStream_t st, const char* who = "grouped search") {
-    if (eng->group_bytes >= need) return RASS_OK;
-    unsigned char* block = nullptr;
-    if (hipMalloc(reinterpret_cast<void**>(&block), need) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(RASS_ERR_OOM, std::string(who) + ": hipMalloc of the group table (" + std::to_string(need) + " bytes) failed");
-    }
-    const int rc = HIP_RC(hipStreamSynchronize(st));
-    if (rc != RASS_OK) {
-        (void)hipFree(block);
-        return rc;
-    }
-    if (eng->d_group) (void)hipFree(eng->d_group);
-    eng->d_group = block;
-    eng->group_bytes = need;
-    return RASS_OK;
-}
-
-int group_device_group(rass_index* idx, const GroupRequest& r) {
-    rass_engine* eng = idx->eng;
-    hipStream_t st = eng->stream;
-    const int nq = r.nq;
-    const IndexView iv = index_view(idx, /*filtered=*/true, r.id_base);   // the group key is in the tag: always read them
-    const int64_t stride = idx->stride;
-    if (iv.rows < 0 || iv.rows > 0x7fffffc0LL) return fail(RASS_ERR_INVALID, "n_rows out of range for one scan");
-    if (!rass::scan_supported_stride(stride) || stride > kMaxStride) return fail(RASS_ERR_UNSUPPORTED, kStrideMsg);
-    if (range_layout(nullptr).total > eng->scratch_bytes) return fail(RASS_ERR_INVALID, "scan workspace too small");
-    if (int rc = grow_group_table(eng, group_layout(nullptr, nq, r.n_groups).total, st)) return rc;
-    const GroupView G = group_layout(eng->d_group, nq, r.n_groups);
-    float* q_padded = range_layout(eng->d_scratch).q_padded;   // where every scan keeps its queries
-    HIP_TRY(rass::launch_normalize_rows_f32(r.queries, idx->dim, q_padded, stride, nq, idx->dim, st, pad_nq(nq)));
-    HIP_TRY(hipMemsetAsync(G.status, 0, G.total, st));
-    const int grid = scan_grid((iv.rows + 31) / 32, 1, eng->n_cus);
-    // wide rows: 16 queries per launch, as for the top-k scan (scan_launch)
-    const int per_launch = stride > kNarrowStride ? 16 : RASS_MAX_QBATCH;
-    for (int q0 = 0; q0 < nq && iv.rows > 0; q0 += per_launch) {
-        rass::ScanArgs a;
-        a.corpus = iv.corpus;
-        a.row_tag = iv.row_tag;
-        a.q_padded = q_padded + (int64_t)q0 * stride;
-        a.q_filter = r.q_filter ? r.q_filter + q0 : nullptr;
-        a.q_filter_mask = r.q_filter_mask ? r.q_filter_mask + q0 : nullptr;
-        a.part_scores = nullptr;
-        a.part_ids = nullptr;
-        a.row_stride = stride;
-        a.id_base = 0;   // the keys name rows of the slab: group_select translates them
-        a.n_rows = (int)iv.rows;
-        a.nq = std::min(per_launch, nq - q0);
-        a.k = 1;
-        a.xcd_skew = scan_xcd_skew(a.nq, grid, eng->n_cus);
-        a.group_table = G.table + (int64_t)q0 * r.n_groups;
-        a.group_status = G.status;
-        a.group_mask = r.group_mask;
-        a.group_shift = __builtin_ctz((unsigned)r.group_mask);
-        a.group_n = r.n_groups;
-        const int rc = timed_launch(eng, st, [&] { return HIP_RC(rass::launch_scan_topk_f32(a, grid, st)); });
-        if (rc != RASS_OK) return rc;
-    }
-    HIP_TRY(rass::launch_group_select(G.table, nq, r.n_groups, r.k, iv.id_base, iv.id_map, r.out_scores, r.out_ids, r.out_groups,
-                                      r.total, G.status, r.status, st));
-    return RASS_OK;
-}
-
-// The argument checks the two grouped entry points share.
-int check_grouped(const rass_index* idx, int k, int32_t group_mask, int32_t n_groups, const int32_t* q_filter,
-                  const int32_t* q_filter_mask) {
-    if (k < 1 || k > RASS_MAX_K_MULTIPASS) return fail(RASS_ERR_INVALID, "k must be in [1, RASS_MAX_K_MULTIPASS]");
-    if (group_mask <= 0) return fail(RASS_ERR_INVALID, "group_mask must be non-zero and within 0x7fffffff");
-    if (n_groups < 1 || n_groups > rass::kGroupMaxGroups) return fail(RASS_ERR_INVALID, "n_groups must be in [1, 1048576]");
-    if (q_filter_mask && !q_filter) return fail(RASS_ERR_INVALID, "q_filter_mask without q_filter");
-    if (idx->dtype != RASS_F32) return fail(RASS_ERR_UNSUPPORTED, "grouped search needs an fp32 index");
-    return RASS_OK;
-}
-
-// One launch group (<= 32 queries) of a terms aggregation: normalise -> ONE memset over the status word, the best-row table
-// and the counters -> the group-count scan (two launches for 17..32 queries on wide rows) -> the select over the counters.
-// Always the exact fp32 scan: the prefilter mode of the index is not looked at.  Everything is a device pointer; the caller
-// holds eng->mu, has set the device and has checked the arguments.
-struct AggRequest {
-    const float* queries = nullptr;     // [nq][dim]
-    int nq = 0;
-    const float* min_score = nullptr;   // [nq]
-    int size = 0;
-    int32_t group_mask = 0;
-    int32_t n_groups = 0;
-    const int32_t* q_filter = nullptr;
-    const int32_t* q_filter_mask = nullptr;
-    int64_t id_base = 0;
-    int32_t* out_groups = nullptr;      // [nq][size]
-    int64_t* out_counts = nullptr;
-    float* out_scores = nullptr;
-    int64_t* out_ids = nullptr;
-    int64_t* n_buckets = nullptr;       // [nq]
-    int64_t* total_hits = nullptr;      // [nq]
-    int32_t* status = nullptr;          // [1]
-};
-
-int agg_device_group(rass_index* idx, const AggRequest& r) {
-    rass_engine* eng = idx->eng;
-    hipStream_t st = eng->stream;
-    const int nq = r.nq;
-    const IndexView iv = index_view(idx, /*filtered=*/true, r.id_base);   // the group key is in the tag: always read them
-    const int64_t stride = idx->stride;
-    if (iv.rows < 0 || iv.rows > 0x7fffffc0LL) return fail(RASS_ERR_INVALID, "n_rows out of range for one scan");
-    if (!rass::scan_supported_stride(stride) || stride > kMaxStride) return fail(RASS_ERR_UNSUPPORTED, kStrideMsg);
-    if (range_layout(nullptr).total > eng->scratch_bytes) return fail(RASS_ERR_INVALID, "scan workspace too small");
-    if (int rc = grow_group_table(eng, agg_layout(nullptr, nq, r.n_groups).total, st, "aggregation")) return rc;
-    const AggView G = agg_layout(eng->d_group, nq, r.n_groups);
-    float* q_padded = range_layout(eng->d_scratch).q_padded;   // where every scan keeps its queries
-    HIP_TRY(rass::launch_normalize_rows_f32(r.queries, idx->dim, q_padded, stride, nq, idx->dim, st, pad_nq(nq)));
-    HIP_TRY(hipMemsetAsync(G.status, 0, G.total, st));
-    const int grid = scan_grid((iv.rows + 31) / 32, 1, eng->n_cus);
-    // wide rows: 16 queries per launch, as for the top-k scan (scan_launch)
-    const int per_launch = stride > kNarrowStride ? 16 : RASS_MAX_QBATCH;
-    for (int q0 = 0; q0 < nq && iv.rows > 0; q0 += per_launch) {
-        rass::ScanArgs a;
-        a.corpus = iv.corpus;
-        a.row_tag = iv.row_tag;
-        a.q_padded = q_padded + (int64_t)q0 * stride;
-        a.q_filter = r.q_filter ? r.q_filter + q0 : nullptr;
-        a.q_filter_mask = r.q_filter_mask ? r.q_filter_mask + q0 : nullptr;
-        a.part_scores = nullptr;
-        a.part_ids = nullptr;
-        a.row_stride = stride;
-        a.id_base = 0;   // the keys name rows of the slab: the select translates them
-        a.n_rows = (int)iv.rows;
-        a.nq = std::min(per_launch, nq - q0);
-        a.k = 1;
-        a.xcd_skew = scan_xcd_skew(a.nq, grid, eng->n_cus);
-        a.range_thr = r.min_score + q0;
-        a.group_table = G.best + (int64_t)q0 * r.n_groups;
-        a.count_table = G.count + (int64_t)q0 * r.n_groups;
-        a.group_status = G.status;
-        a.group_mask = r.group_mask;
-        a.group_shift = __builtin_ctz((unsigned)r.group_mask);
-        a.group_n = r.n_groups;
-        const int rc = timed_launch(eng, st, [&] { return HIP_RC(rass::launch_scan_topk_f32(a, grid, st)); });
-        if (rc != RASS_OK) return rc;
-    }
-    HIP_TRY(rass::launch_group_count_select(G.count, G.best, nq, r.n_groups, r.size, iv.id_base, iv.id_map, r.out_groups, r.out_counts,
-                                            r.out_scores, r.out_ids, r.n_buckets, r.total_hits, G.status, r.status, st));
-    return RASS_OK;
-}
-
-// The argument checks the two aggregation entry points share.
-int check_aggregate(const rass_index* idx, int size, int32_t group_mask, int32_t n_groups, const int32_t* q_filter,
-                    const int32_t* q_filter_mask) {
-    if (size < 1 || size > rass::kGroupMaxK) return fail(RASS_ERR_INVALID, "size must be in [1, RASS_MAX_K_MULTIPASS]");
-    if (group_mask <= 0) return fail(RASS_ERR_INVALID, "group_mask must be non-zero and within 0x7fffffff");
-    if (n_groups < 1 || n_groups > rass::kGroupMaxGroups) return fail(RASS_ERR_INVALID, "n_groups must be in [1, 1048576]");
-    if (q_filter_mask && !q_filter) return fail(RASS_ERR_INVALID, "q_filter_mask without q_filter");
-    if (idx->dtype != RASS_F32) return fail(RASS_ERR_UNSUPPORTED, "aggregation needs an fp32 index");
-    return RASS_OK;
-}
-
 // What the device entry points of one launch group share: argument checks, the engine lock, the device.
 int search_device_locked(rass_index_t* idx, const FlatRequest& r) {
     if (!idx || !r.queries || !r.out_scores || !r.out_ids) return fail(RASS_ERR_INVALID, "NULL argument");
@@ -525,6 +294,65 @@ int search_device_locked(rass_index_t* idx, const FlatRequest& r) {
 }
 
 }  // namespace
+
+// One attempt of rass_index_search_ex.  Not on host_groups (nor is search_multi_once): its groups run PASSES, each with its own
+// lock, upload and wait, and the cross-index batch builds a work list under the lock — folding either in would add flags there.
+int search_ex_once(rass_index* idx, const float* queries, int nq, int k, const int32_t* q_filter, const int32_t* q_filter_mask,
+                   float* out_scores, int64_t* out_ids, bool exact) {
+    rass_engine* eng = idx->eng;
+    int rc = set_device(eng);
+    if (rc != RASS_OK) return rc;
+    const int dim = idx->dim;
+    SlotGuard guard(eng);
+    HostSlot* sl = guard.sl;
+    for (int done = 0; done < nq;) {
+        const int b = std::min(RASS_MAX_QBATCH, nq - done);
+        slot_fill(sl, dim, queries + (int64_t)done * dim, q_filter ? q_filter + done : nullptr,
+                  q_filter_mask ? q_filter_mask + done : nullptr, b);
+        // k > RASS_MAX_K: passes of <= 32; pass p ranks only the rows strictly AFTER pass p-1's last hit
+        for (int kdone = 0; kdone < k;) {
+            const int kk = std::min(RASS_MAX_K, k - kdone);
+            const bool cont = kdone > 0;
+            {
+                // the engine lock is held while ENQUEUING only: device staging and scratch are shared by
+                // stream order, the wait happens on this call's own event
+                std::lock_guard<std::mutex> lk(eng->mu);
+                hipStream_t st = eng->stream;
+                rc = slot_upload(eng, sl, dim, q_filter != nullptr, q_filter_mask != nullptr, b);
+                if (rc != RASS_OK) return rc;
+                FlatRequest r;
+                r.queries = eng->d_qraw, r.nq = b, r.k = kk;
+                r.q_filter = q_filter ? eng->d_qfilter : nullptr, r.q_filter_mask = q_filter_mask ? eng->d_qmask : nullptr;
+                r.out_scores = eng->d_out_scores, r.out_ids = eng->d_out_ids;
+                if (cont) {
+                    HIP_TRY(hipMemcpyAsync(eng->d_after_s, sl->h_after_s, (size_t)b * sizeof(float), hipMemcpyHostToDevice, st));
+                    HIP_TRY(hipMemcpyAsync(eng->d_after_i, sl->h_after_i, (size_t)b * sizeof(int64_t), hipMemcpyHostToDevice, st));
+                    r.after_score = eng->d_after_s, r.after_row = eng->d_after_i;
+                }
+                if (cont && idx->has_gid.load(std::memory_order_acquire))  // the continuation bound compares row ordinals, the caller would hand back global ids
+                    return fail(RASS_ERR_UNSUPPORTED, "k > RASS_MAX_K on an index with caller-assigned row ids");
+                rc = search_device_group(idx, r, /*one_pass=*/k <= RASS_MAX_K, exact);
+                if (rc != RASS_OK) return rc;
+                rc = slot_download(eng, sl, b, kk);
+                if (rc != RASS_OK) return rc;
+            }
+            HIP_TRY(hipEventSynchronize(sl->done));
+            for (int q = 0; q < b; ++q) {
+                memcpy(out_scores + (int64_t)(done + q) * k + kdone, sl->h_out_s + (int64_t)q * kk, (size_t)kk * sizeof(float));
+                memcpy(out_ids + (int64_t)(done + q) * k + kdone, sl->h_out_i + (int64_t)q * kk, (size_t)kk * sizeof(int64_t));
+                // continuation bound for the next pass: this pass's last hit, or "nothing left" (-inf) when the
+                // pass came back short
+                const int64_t last_id = sl->h_out_i[(int64_t)q * kk + kk - 1];
+                sl->h_after_s[q] = last_id >= 0 ? sl->h_out_s[(int64_t)q * kk + kk - 1] : -INFINITY;
+                sl->h_after_i[q] = last_id >= 0 ? last_id : INT64_MAX;
+            }
+            kdone += kk;
+        }
+        done += b;
+    }
+    return RASS_OK;
+}
+
 }  // namespace host
 }  // namespace rass
 
@@ -646,63 +474,6 @@ int rass_index_candidates_exact_device(rass_index_t* idx, const float* d_queries
     r.row_tag = index_view(idx, d_q_filter != nullptr).row_tag;
     r.cand_scores = d_cand_scores, r.cand_rows = d_cand_rows, r.tau = d_tau, r.certified = d_certified;
     return cert_launch(idx, r);
-}
-
-// exact = true: every pass on the exact fp32 scan, whatever the index's prefilter mode (search_device_group).
-static int search_ex_once(rass_index_t* idx, const float* queries, int nq, int k, const int32_t* q_filter,
-                          const int32_t* q_filter_mask, float* out_scores, int64_t* out_ids, bool exact = false) {
-    rass_engine* eng = idx->eng;
-    int rc = set_device(eng);
-    if (rc != RASS_OK) return rc;
-    const int dim = idx->dim;
-    SlotGuard guard(eng);
-    HostSlot* sl = guard.sl;
-    for (int done = 0; done < nq;) {
-        const int b = std::min(RASS_MAX_QBATCH, nq - done);
-        slot_fill(sl, dim, queries + (int64_t)done * dim, q_filter ? q_filter + done : nullptr,
-                  q_filter_mask ? q_filter_mask + done : nullptr, b);
-        // k > RASS_MAX_K: passes of <= 32; pass p ranks only the rows strictly AFTER pass p-1's last hit
-        for (int kdone = 0; kdone < k;) {
-            const int kk = std::min(RASS_MAX_K, k - kdone);
-            const bool cont = kdone > 0;
-            {
-                // the engine lock is held while ENQUEUING only: device staging and scratch are shared by
-                // stream order, the wait happens on this call's own event
-                std::lock_guard<std::mutex> lk(eng->mu);
-                hipStream_t st = eng->stream;
-                rc = slot_upload(eng, sl, dim, q_filter != nullptr, q_filter_mask != nullptr, b);
-                if (rc != RASS_OK) return rc;
-                FlatRequest r;
-                r.queries = eng->d_qraw, r.nq = b, r.k = kk;
-                r.q_filter = q_filter ? eng->d_qfilter : nullptr, r.q_filter_mask = q_filter_mask ? eng->d_qmask : nullptr;
-                r.out_scores = eng->d_out_scores, r.out_ids = eng->d_out_ids;
-                if (cont) {
-                    HIP_TRY(hipMemcpyAsync(eng->d_after_s, sl->h_after_s, (size_t)b * sizeof(float), hipMemcpyHostToDevice, st));
-                    HIP_TRY(hipMemcpyAsync(eng->d_after_i, sl->h_after_i, (size_t)b * sizeof(int64_t), hipMemcpyHostToDevice, st));
-                    r.after_score = eng->d_after_s, r.after_row = eng->d_after_i;
-                }
-                if (cont && idx->has_gid.load(std::memory_order_acquire))  // the continuation bound compares row ordinals, the caller would hand back global ids
-                    return fail(RASS_ERR_UNSUPPORTED, "k > RASS_MAX_K on an index with caller-assigned row ids");
-                rc = search_device_group(idx, r, /*one_pass=*/k <= RASS_MAX_K, exact);
-                if (rc != RASS_OK) return rc;
-                rc = slot_download(eng, sl, b, kk);
-                if (rc != RASS_OK) return rc;
-            }
-            HIP_TRY(hipEventSynchronize(sl->done));
-            for (int q = 0; q < b; ++q) {
-                memcpy(out_scores + (int64_t)(done + q) * k + kdone, sl->h_out_s + (int64_t)q * kk, (size_t)kk * sizeof(float));
-                memcpy(out_ids + (int64_t)(done + q) * k + kdone, sl->h_out_i + (int64_t)q * kk, (size_t)kk * sizeof(int64_t));
-                // continuation bound for the next pass: this pass's last hit, or "nothing left" (-inf) when the
-                // pass came back short
-                const int64_t last_id = sl->h_out_i[(int64_t)q * kk + kk - 1];
-                sl->h_after_s[q] = last_id >= 0 ? sl->h_out_s[(int64_t)q * kk + kk - 1] : -INFINITY;
-                sl->h_after_i[q] = last_id >= 0 ? last_id : INT64_MAX;
-            }
-            kdone += kk;
-        }
-        done += b;
-    }
-    return RASS_OK;
 }
 
 int rass_index_search_ex(rass_index_t* idx, const float* queries, int nq, int k, const int32_t* q_filter,
@@ -838,287 +609,6 @@ int rass_index_search_multi(rass_index_t* const* idxs, const float* queries, int
         return sum;
     };
     return one_layout(epochs, [&] { return search_multi_once(eng, idxs, queries, nq, k, q_filter, q_filter_mask, out_scores, out_ids); });
-}
-
-int rass_index_search_range_device(rass_index_t* idx, const float* d_queries, int nq, const float* d_min_score, int max_hits,
-                                   const int32_t* d_q_filter, const int32_t* d_q_filter_mask, int64_t id_base,
-                                   float* d_out_scores, int64_t* d_out_ids, int64_t* d_total) {
-    if (!idx || !d_queries || !d_min_score || !d_out_scores || !d_out_ids || !d_total) return fail(RASS_ERR_INVALID, "NULL argument");
-    if (int rc = check_nq(nq)) return rc;
-    if (int rc = check_range(idx, max_hits, d_q_filter, d_q_filter_mask)) return rc;
-    rass_engine* eng = idx->eng;
-    std::lock_guard<std::mutex> lk(eng->mu);
-    int rc = set_device(eng);
-    if (rc != RASS_OK) return rc;
-    RangeRequest r;
-    r.queries = d_queries, r.nq = nq, r.min_score = d_min_score, r.max_hits = max_hits;
-    r.q_filter = d_q_filter, r.q_filter_mask = d_q_filter_mask, r.id_base = id_base;
-    r.out_scores = d_out_scores, r.out_ids = d_out_ids, r.total = d_total;
-    return range_device_group(idx, r);
-}
-
-// One attempt of the host range search (one_layout runs it again when a compaction landed meanwhile).  Phase 1: group by
-// group through a pinned slot, as search_ex_once.  Phase 2, with the slot released: the queries whose total exceeds max_hits
-// get the best max_hits matching rows — more than max_hits rows reach the threshold, so those are the plain top max_hits
-// under the query's filter — from the multipass top-k path itself, pinned to the exact scan.
-static int search_range_once(rass_index_t* idx, const float* queries, int nq, const float* min_score, int max_hits,
-                             const int32_t* q_filter, const int32_t* q_filter_mask, float* out_scores, int64_t* out_ids,
-                             int64_t* out_total) {
-    rass_engine* eng = idx->eng;
-    int rc = set_device(eng);
-    if (rc != RASS_OK) return rc;
-    const int dim = idx->dim;
-    {
-        SlotGuard guard(eng);
-        HostSlot* sl = guard.sl;
-        if (!sl->h_range) HIP_TRY(hipHostMalloc(&sl->h_range, range_io_layout(nullptr).bytes, hipHostMallocDefault));
-        const RangeIoView H = range_io_layout(static_cast<unsigned char*>(sl->h_range));
-        for (int done = 0; done < nq;) {
-            const int b = std::min(RASS_MAX_QBATCH, nq - done);
-            const size_t cells = (size_t)b * max_hits;
-            slot_fill(sl, dim, queries + (int64_t)done * dim, q_filter ? q_filter + done : nullptr,
-                      q_filter_mask ? q_filter_mask + done : nullptr, b);
-            memcpy(H.thr, min_score + done, (size_t)b * sizeof(float));
-            {
-                std::lock_guard<std::mutex> lk(eng->mu);   // while enqueuing only, as rass_index_search_ex
-                hipStream_t st = eng->stream;
-                rc = grow_block(&eng->d_range, &eng->range_bytes, range_io_layout(nullptr).bytes, st);
-                if (rc != RASS_OK) return rc;
-                const RangeIoView D = range_io_layout(eng->d_range);
-                rc = slot_upload(eng, sl, dim, q_filter != nullptr, q_filter_mask != nullptr, b);
-                if (rc != RASS_OK) return rc;
-                HIP_TRY(hipMemcpyAsync(D.thr, H.thr, (size_t)b * sizeof(float), hipMemcpyHostToDevice, st));
-                RangeRequest r;
-                r.queries = eng->d_qraw, r.nq = b, r.min_score = D.thr, r.max_hits = max_hits;
-                r.q_filter = q_filter ? eng->d_qfilter : nullptr, r.q_filter_mask = q_filter_mask ? eng->d_qmask : nullptr;
-                r.out_scores = D.out_scores, r.out_ids = D.out_ids, r.total = D.total;
-                rc = range_device_group(idx, r);
-                if (rc != RASS_OK) return rc;
-                HIP_TRY(hipMemcpyAsync(H.total, D.total, (size_t)b * sizeof(int64_t), hipMemcpyDeviceToHost, st));
-                HIP_TRY(hipMemcpyAsync(H.out_scores, D.out_scores, cells * sizeof(float), hipMemcpyDeviceToHost, st));
-                HIP_TRY(hipMemcpyAsync(H.out_ids, D.out_ids, cells * sizeof(int64_t), hipMemcpyDeviceToHost, st));
-                HIP_TRY(hipEventRecord(sl->done, st));
-            }
-            HIP_TRY(hipEventSynchronize(sl->done));
-            memcpy(out_total + done, H.total, (size_t)b * sizeof(int64_t));
-            memcpy(out_scores + (int64_t)done * max_hits, H.out_scores, cells * sizeof(float));
-            memcpy(out_ids + (int64_t)done * max_hits, H.out_ids, cells * sizeof(int64_t));
-            done += b;
-        }
-    }
-    std::vector<int> over;
-    for (int q = 0; q < nq; ++q)
-        if (out_total[q] > max_hits) over.push_back(q);
-    if (over.empty()) return RASS_OK;
-    const int no = (int)over.size();
-    std::vector<float> oq((size_t)no * dim), os((size_t)no * max_hits);
-    std::vector<int32_t> of(q_filter ? no : 0), om(q_filter_mask ? no : 0);
-    std::vector<int64_t> oi((size_t)no * max_hits);
-    for (int j = 0; j < no; ++j) {
-        memcpy(oq.data() + (size_t)j * dim, queries + (int64_t)over[j] * dim, (size_t)dim * sizeof(float));
-        if (q_filter) of[j] = q_filter[over[j]];
-        if (q_filter_mask) om[j] = q_filter_mask[over[j]];
-    }
-    rc = search_ex_once(idx, oq.data(), no, max_hits, q_filter ? of.data() : nullptr, q_filter_mask ? om.data() : nullptr, os.data(),
-                        oi.data(), /*exact=*/true);
-    if (rc != RASS_OK) return rc;
-    for (int j = 0; j < no; ++j) {
-        memcpy(out_scores + (int64_t)over[j] * max_hits, os.data() + (size_t)j * max_hits, (size_t)max_hits * sizeof(float));
-        memcpy(out_ids + (int64_t)over[j] * max_hits, oi.data() + (size_t)j * max_hits, (size_t)max_hits * sizeof(int64_t));
-    }
-    return RASS_OK;
-}
-
-int rass_index_search_range(rass_index_t* idx, const float* queries, int nq, const float* min_score, int max_hits,
-                            const int32_t* q_filter, const int32_t* q_filter_mask, float* out_scores, int64_t* out_ids,
-                            int64_t* out_total) {
-    if (!idx || !out_scores || !out_ids || !out_total) return fail(RASS_ERR_INVALID, "NULL argument");
-    if (nq < 0 || (nq > 0 && (!queries || !min_score))) return fail(RASS_ERR_INVALID, "bad queries / min_score / nq");
-    if (int rc = check_range(idx, max_hits, q_filter, q_filter_mask)) return rc;
-    for (int q = 0; q < nq; ++q)
-        if (min_score[q] != min_score[q]) return fail(RASS_ERR_INVALID, "min_score is NaN");
-    if (nq == 0) return RASS_OK;
-    return one_layout([&] { return idx->layout_epoch.load(std::memory_order_acquire); }, [&] {
-        return search_range_once(idx, queries, nq, min_score, max_hits, q_filter, q_filter_mask, out_scores, out_ids, out_total);
-    });
-}
-
-int rass_index_search_grouped_device(rass_index_t* idx, const float* d_queries, int nq, int k, int32_t group_mask, int32_t n_groups,
-                                     const int32_t* d_q_filter, const int32_t* d_q_filter_mask, int64_t id_base,
-                                     float* d_out_scores, int64_t* d_out_ids, int32_t* d_out_groups, int64_t* d_group_total,
-                                     int32_t* d_status) {
-    if (!idx || !d_queries || !d_out_scores || !d_out_ids || !d_out_groups || !d_group_total || !d_status)
-        return fail(RASS_ERR_INVALID, "NULL argument");
-    if (int rc = check_nq(nq)) return rc;
-    if (int rc = check_grouped(idx, k, group_mask, n_groups, d_q_filter, d_q_filter_mask)) return rc;
-    rass_engine* eng = idx->eng;
-    std::lock_guard<std::mutex> lk(eng->mu);
-    int rc = set_device(eng);
-    if (rc != RASS_OK) return rc;
-    GroupRequest r;
-    r.queries = d_queries, r.nq = nq, r.k = k, r.group_mask = group_mask, r.n_groups = n_groups;
-    r.q_filter = d_q_filter, r.q_filter_mask = d_q_filter_mask, r.id_base = id_base;
-    r.out_scores = d_out_scores, r.out_ids = d_out_ids, r.out_groups = d_out_groups, r.total = d_group_total, r.status = d_status;
-    return group_device_group(idx, r);
-}
-
-// One attempt of the host grouped search (one_layout runs it again when a compaction landed meanwhile): group by group
-// through a pinned slot, as search_range_once.  A group whose scan met a group key >= n_groups ends the call.
-static int search_grouped_once(rass_index_t* idx, const float* queries, int nq, int k, int32_t group_mask, int32_t n_groups,
-                               const int32_t* q_filter, const int32_t* q_filter_mask, float* out_scores, int64_t* out_ids,
-                               int32_t* out_groups, int64_t* out_total) {
-    rass_engine* eng = idx->eng;
-    int rc = set_device(eng);
-    if (rc != RASS_OK) return rc;
-    const int dim = idx->dim;
-    SlotGuard guard(eng);
-    HostSlot* sl = guard.sl;
-    if (!sl->h_group) HIP_TRY(hipHostMalloc(&sl->h_group, group_io_layout(nullptr).bytes, hipHostMallocDefault));
-    const GroupIoView H = group_io_layout(static_cast<unsigned char*>(sl->h_group));
-    for (int done = 0; done < nq;) {
-        const int b = std::min(RASS_MAX_QBATCH, nq - done);
-        const size_t cells = (size_t)b * k;
-        slot_fill(sl, dim, queries + (int64_t)done * dim, q_filter ? q_filter + done : nullptr,
-                  q_filter_mask ? q_filter_mask + done : nullptr, b);
-        {
-            std::lock_guard<std::mutex> lk(eng->mu);   // while enqueuing only, as rass_index_search_ex
-            hipStream_t st = eng->stream;
-            rc = grow_block(&eng->d_group_io, &eng->group_io_bytes, group_io_layout(nullptr).bytes, st);
-            if (rc != RASS_OK) return rc;
-            const GroupIoView D = group_io_layout(eng->d_group_io);
-            rc = slot_upload(eng, sl, dim, q_filter != nullptr, q_filter_mask != nullptr, b);
-            if (rc != RASS_OK) return rc;
-            GroupRequest r;
-            r.queries = eng->d_qraw, r.nq = b, r.k = k, r.group_mask = group_mask, r.n_groups = n_groups;
-            r.q_filter = q_filter ? eng->d_qfilter : nullptr, r.q_filter_mask = q_filter_mask ? eng->d_qmask : nullptr;
-            r.out_scores = D.out_scores, r.out_ids = D.out_ids, r.out_groups = D.out_groups, r.total = D.total, r.status = D.status;
-            rc = group_device_group(idx, r);
-            if (rc != RASS_OK) return rc;
-            HIP_TRY(hipMemcpyAsync(H.total, D.total, (size_t)b * sizeof(int64_t), hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipMemcpyAsync(H.status, D.status, sizeof(int32_t), hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipMemcpyAsync(H.out_scores, D.out_scores, cells * sizeof(float), hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipMemcpyAsync(H.out_ids, D.out_ids, cells * sizeof(int64_t), hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipMemcpyAsync(H.out_groups, D.out_groups, cells * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipEventRecord(sl->done, st));
-        }
-        HIP_TRY(hipEventSynchronize(sl->done));
-        if (*H.status != 0)
-            return fail(RASS_ERR_INVALID, "grouped search: a matching row's group key is >= n_groups (" + std::to_string(n_groups) + ")");
-        memcpy(out_total + done, H.total, (size_t)b * sizeof(int64_t));
-        memcpy(out_scores + (int64_t)done * k, H.out_scores, cells * sizeof(float));
-        memcpy(out_ids + (int64_t)done * k, H.out_ids, cells * sizeof(int64_t));
-        memcpy(out_groups + (int64_t)done * k, H.out_groups, cells * sizeof(int32_t));
-        done += b;
-    }
-    return RASS_OK;
-}
-
-int rass_index_search_grouped(rass_index_t* idx, const float* queries, int nq, int k, int32_t group_mask, int32_t n_groups,
-                              const int32_t* q_filter, const int32_t* q_filter_mask, float* out_scores, int64_t* out_ids,
-                              int32_t* out_groups, int64_t* out_group_total) {
-    if (!idx || !out_scores || !out_ids || !out_groups || !out_group_total) return fail(RASS_ERR_INVALID, "NULL argument");
-    if (nq < 0 || (nq > 0 && !queries)) return fail(RASS_ERR_INVALID, "bad queries / nq");
-    if (int rc = check_grouped(idx, k, group_mask, n_groups, q_filter, q_filter_mask)) return rc;
-    if (nq == 0) return RASS_OK;
-    return one_layout([&] { return idx->layout_epoch.load(std::memory_order_acquire); }, [&] {
-        return search_grouped_once(idx, queries, nq, k, group_mask, n_groups, q_filter, q_filter_mask, out_scores, out_ids, out_groups,
-                                   out_group_total);
-    });
-}
-
-int rass_index_aggregate_device(rass_index_t* idx, const float* d_queries, int nq, const float* d_min_score, int size,
-                                int32_t group_mask, int32_t n_groups, const int32_t* d_q_filter, const int32_t* d_q_filter_mask,
-                                int64_t id_base, int32_t* d_out_groups, int64_t* d_out_counts, float* d_out_scores,
-                                int64_t* d_out_ids, int64_t* d_n_buckets, int64_t* d_total_hits, int32_t* d_status) {
-    if (!idx || !d_queries || !d_min_score || !d_out_groups || !d_out_counts || !d_out_scores || !d_out_ids || !d_n_buckets ||
-        !d_total_hits || !d_status)
-        return fail(RASS_ERR_INVALID, "NULL argument");
-    if (int rc = check_nq(nq)) return rc;
-    if (int rc = check_aggregate(idx, size, group_mask, n_groups, d_q_filter, d_q_filter_mask)) return rc;
-    rass_engine* eng = idx->eng;
-    std::lock_guard<std::mutex> lk(eng->mu);
-    int rc = set_device(eng);
-    if (rc != RASS_OK) return rc;
-    AggRequest r;
-    r.queries = d_queries, r.nq = nq, r.min_score = d_min_score, r.size = size, r.group_mask = group_mask, r.n_groups = n_groups;
-    r.q_filter = d_q_filter, r.q_filter_mask = d_q_filter_mask, r.id_base = id_base;
-    r.out_groups = d_out_groups, r.out_counts = d_out_counts, r.out_scores = d_out_scores, r.out_ids = d_out_ids;
-    r.n_buckets = d_n_buckets, r.total_hits = d_total_hits, r.status = d_status;
-    return agg_device_group(idx, r);
-}
-
-// One attempt of the host aggregation (one_layout runs it again when a compaction landed meanwhile): group by group through
-// a pinned slot, as search_grouped_once.  A group whose scan met a hit with a group key >= n_groups ends the call.
-static int aggregate_once(rass_index_t* idx, const float* queries, int nq, const float* min_score, int size, int32_t group_mask,
-                          int32_t n_groups, const int32_t* q_filter, const int32_t* q_filter_mask, int32_t* out_groups,
-                          int64_t* out_counts, float* out_scores, int64_t* out_ids, int64_t* out_n_buckets, int64_t* out_total_hits) {
-    rass_engine* eng = idx->eng;
-    int rc = set_device(eng);
-    if (rc != RASS_OK) return rc;
-    const int dim = idx->dim;
-    SlotGuard guard(eng);
-    HostSlot* sl = guard.sl;
-    if (!sl->h_agg) HIP_TRY(hipHostMalloc(&sl->h_agg, agg_io_layout(nullptr).bytes, hipHostMallocDefault));
-    const AggIoView H = agg_io_layout(static_cast<unsigned char*>(sl->h_agg));
-    for (int done = 0; done < nq;) {
-        const int b = std::min(RASS_MAX_QBATCH, nq - done);
-        const size_t cells = (size_t)b * size;
-        slot_fill(sl, dim, queries + (int64_t)done * dim, q_filter ? q_filter + done : nullptr,
-                  q_filter_mask ? q_filter_mask + done : nullptr, b);
-        memcpy(H.thr, min_score + done, (size_t)b * sizeof(float));
-        {
-            std::lock_guard<std::mutex> lk(eng->mu);   // while enqueuing only, as rass_index_search_ex
-            hipStream_t st = eng->stream;
-            rc = grow_block(&eng->d_group_io, &eng->group_io_bytes, agg_io_layout(nullptr).bytes, st);
-            if (rc != RASS_OK) return rc;
-            const AggIoView D = agg_io_layout(eng->d_group_io);
-            rc = slot_upload(eng, sl, dim, q_filter != nullptr, q_filter_mask != nullptr, b);
-            if (rc != RASS_OK) return rc;
-            HIP_TRY(hipMemcpyAsync(D.thr, H.thr, (size_t)b * sizeof(float), hipMemcpyHostToDevice, st));
-            AggRequest r;
-            r.queries = eng->d_qraw, r.nq = b, r.min_score = D.thr, r.size = size, r.group_mask = group_mask, r.n_groups = n_groups;
-            r.q_filter = q_filter ? eng->d_qfilter : nullptr, r.q_filter_mask = q_filter_mask ? eng->d_qmask : nullptr;
-            r.out_groups = D.out_groups, r.out_counts = D.out_counts, r.out_scores = D.out_scores, r.out_ids = D.out_ids;
-            r.n_buckets = D.n_buckets, r.total_hits = D.total_hits, r.status = D.status;
-            rc = agg_device_group(idx, r);
-            if (rc != RASS_OK) return rc;
-            HIP_TRY(hipMemcpyAsync(H.n_buckets, D.n_buckets, (size_t)b * sizeof(int64_t), hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipMemcpyAsync(H.total_hits, D.total_hits, (size_t)b * sizeof(int64_t), hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipMemcpyAsync(H.status, D.status, sizeof(int32_t), hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipMemcpyAsync(H.out_groups, D.out_groups, cells * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipMemcpyAsync(H.out_counts, D.out_counts, cells * sizeof(int64_t), hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipMemcpyAsync(H.out_scores, D.out_scores, cells * sizeof(float), hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipMemcpyAsync(H.out_ids, D.out_ids, cells * sizeof(int64_t), hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipEventRecord(sl->done, st));
-        }
-        HIP_TRY(hipEventSynchronize(sl->done));
-        if (*H.status != 0)
-            return fail(RASS_ERR_INVALID, "aggregation: a hit's group key is >= n_groups (" + std::to_string(n_groups) + ")");
-        memcpy(out_n_buckets + done, H.n_buckets, (size_t)b * sizeof(int64_t));
-        memcpy(out_total_hits + done, H.total_hits, (size_t)b * sizeof(int64_t));
-        memcpy(out_groups + (int64_t)done * size, H.out_groups, cells * sizeof(int32_t));
-        memcpy(out_counts + (int64_t)done * size, H.out_counts, cells * sizeof(int64_t));
-        memcpy(out_scores + (int64_t)done * size, H.out_scores, cells * sizeof(float));
-        memcpy(out_ids + (int64_t)done * size, H.out_ids, cells * sizeof(int64_t));
-        done += b;
-    }
-    return RASS_OK;
-}
-
-int rass_index_aggregate(rass_index_t* idx, const float* queries, int nq, const float* min_score, int size, int32_t group_mask,
-                         int32_t n_groups, const int32_t* q_filter, const int32_t* q_filter_mask, int32_t* out_groups,
-                         int64_t* out_counts, float* out_scores, int64_t* out_ids, int64_t* out_n_buckets, int64_t* out_total_hits) {
-    if (!idx || !out_groups || !out_counts || !out_scores || !out_ids || !out_n_buckets || !out_total_hits)
-        return fail(RASS_ERR_INVALID, "NULL argument");
-    if (nq < 0 || (nq > 0 && (!queries || !min_score))) return fail(RASS_ERR_INVALID, "bad queries / min_score / nq");
-    if (int rc = check_aggregate(idx, size, group_mask, n_groups, q_filter, q_filter_mask)) return rc;
-    for (int q = 0; q < nq; ++q)
-        if (min_score[q] != min_score[q]) return fail(RASS_ERR_INVALID, "min_score is NaN");
-    if (nq == 0) return RASS_OK;
-    return one_layout([&] { return idx->layout_epoch.load(std::memory_order_acquire); }, [&] {
-        return aggregate_once(idx, queries, nq, min_score, size, group_mask, n_groups, q_filter, q_filter_mask, out_groups, out_counts,
-                              out_scores, out_ids, out_n_buckets, out_total_hits);
-    });
 }
 
 int rass_index_search(rass_index_t* idx, const float* queries, int nq, int k, const int32_t* q_filter,

@@ -883,6 +883,24 @@ bool scan_supported_stride(int64_t row_stride) {
     return (ch >= 1 && ch <= 8) || (ch >= 10 && ch <= 16 && ch % 2 == 0);  // wide rows: whole 256-column units
 }
 
+// The scans that emit instead of ranking (kRange, kGroupMax, kGroupCount): flat, every stride, plain or masked filters, nothing
+// else.  The mode's own fields are the caller's to check.
+template <int MODE>
+static hipError_t launch_emit(int ch, bool ext, const ScanArgs& a, int grid, hipStream_t stream) {
+    constexpr bool R = MODE == kRange, G = MODE == kGroupMax, C = MODE == kGroupCount;
+    if (a.nq < 1 || a.nq > 32) return hipErrorInvalidValue;
+    if (a.q_after_score || a.q_after_id || a.work_tile || a.work_base || a.sample_pass || a.sample_best || a.wgs_per_group ||
+        a.live_nq)
+        return hipErrorInvalidValue;
+    if (a.q_filter_mask != nullptr && a.q_filter == nullptr) return hipErrorInvalidValue;
+    if (ch > 8) {
+        if (a.nq > 16) return hipErrorInvalidValue;   // the caller splits larger groups, as for the top-k scan
+        return ext ? launch_wide<true, R, G, C>(ch, a, grid, stream) : launch_wide<false, R, G, C>(ch, a, grid, stream);
+    }
+    if (a.nq <= 16) return ext ? launch_ch<1, MODE, true>(ch, a, grid, stream) : launch_ch<1, MODE>(ch, a, grid, stream);
+    return ext ? launch_ch<2, MODE, true>(ch, a, grid, stream) : launch_ch<2, MODE>(ch, a, grid, stream);
+}
+
 hipError_t launch_scan_topk_f32(const ScanArgs& a, int grid, hipStream_t stream) {
     if (!scan_supported_stride(a.row_stride)) return hipErrorInvalidValue;
     const int ch = (int)(a.row_stride / 128);
@@ -896,50 +914,19 @@ hipError_t launch_scan_topk_f32(const ScanArgs& a, int grid, hipStream_t stream)
         // one variant per stride: 32 (zero-padded) queries, EXT — absent filters and bounds take their neutral values in LDS
         return launch_ch<2, kAllow, true>(ch, a, grid, stream);
     }
-    if (a.range_count != nullptr) {  // the range scan: flat, every stride, plain or masked filters, nothing else
-        if (!a.range_thr || !a.range_hits || a.range_cap < 1 || a.range_cap > kRangeMaxHits || a.nq < 1 || a.nq > 32)
-            return hipErrorInvalidValue;
-        if (a.q_after_score || a.q_after_id || a.work_tile || a.work_base || a.sample_pass || a.sample_best || a.wgs_per_group ||
-            a.live_nq)
-            return hipErrorInvalidValue;
-        if (a.q_filter_mask != nullptr && a.q_filter == nullptr) return hipErrorInvalidValue;
-        if (ch > 8) {
-            if (a.nq > 16) return hipErrorInvalidValue;   // the caller splits larger groups, as for the top-k scan
-            return ext ? launch_wide<true, true>(ch, a, grid, stream) : launch_wide<false, true>(ch, a, grid, stream);
-        }
-        if (a.nq <= 16) return ext ? launch_ch<1, kRange, true>(ch, a, grid, stream) : launch_ch<1, kRange>(ch, a, grid, stream);
-        return ext ? launch_ch<2, kRange, true>(ch, a, grid, stream) : launch_ch<2, kRange>(ch, a, grid, stream);
+    if (a.range_count != nullptr) {  // the range scan
+        if (!a.range_thr || !a.range_hits || a.range_cap < 1 || a.range_cap > kRangeMaxHits) return hipErrorInvalidValue;
+        return launch_emit<kRange>(ch, ext, a, grid, stream);
     }
-    if (a.count_table != nullptr) {  // the group-count scan: flat, every stride, plain or masked filters, nothing else
-        if (!a.group_table || !a.group_status || !a.range_thr || !a.row_tag || a.group_mask <= 0 || a.group_n < 1 ||
-            a.group_n > kGroupMaxGroups || a.nq < 1 || a.nq > 32)
-            return hipErrorInvalidValue;
-        if (a.group_shift != __builtin_ctz((unsigned)a.group_mask)) return hipErrorInvalidValue;
-        if (a.q_after_score || a.q_after_id || a.work_tile || a.work_base || a.sample_pass || a.sample_best || a.wgs_per_group ||
-            a.live_nq)
-            return hipErrorInvalidValue;
-        if (a.q_filter_mask != nullptr && a.q_filter == nullptr) return hipErrorInvalidValue;
-        if (ch > 8) {
-            if (a.nq > 16) return hipErrorInvalidValue;   // the caller splits larger groups, as for the top-k scan
-            return ext ? launch_wide<true, false, false, true>(ch, a, grid, stream) : launch_wide<false, false, false, true>(ch, a, grid, stream);
-        }
-        if (a.nq <= 16) return ext ? launch_ch<1, kGroupCount, true>(ch, a, grid, stream) : launch_ch<1, kGroupCount>(ch, a, grid, stream);
-        return ext ? launch_ch<2, kGroupCount, true>(ch, a, grid, stream) : launch_ch<2, kGroupCount>(ch, a, grid, stream);
+    const bool groups_ok = a.group_table && a.group_status && a.row_tag && a.group_mask > 0 && a.group_n >= 1 &&
+                           a.group_n <= kGroupMaxGroups && a.group_shift == __builtin_ctz((unsigned)a.group_mask);
+    if (a.count_table != nullptr) {  // the group-count scan
+        if (!groups_ok || !a.range_thr) return hipErrorInvalidValue;
+        return launch_emit<kGroupCount>(ch, ext, a, grid, stream);
     }
-    if (a.group_table != nullptr) {  // the group-max scan: flat, every stride, plain or masked filters, nothing else
-        if (!a.group_status || !a.row_tag || a.group_mask <= 0 || a.group_n < 1 || a.group_n > kGroupMaxGroups || a.nq < 1 || a.nq > 32)
-            return hipErrorInvalidValue;
-        if (a.group_shift != __builtin_ctz((unsigned)a.group_mask)) return hipErrorInvalidValue;
-        if (a.q_after_score || a.q_after_id || a.work_tile || a.work_base || a.sample_pass || a.sample_best || a.wgs_per_group ||
-            a.live_nq)
-            return hipErrorInvalidValue;
-        if (a.q_filter_mask != nullptr && a.q_filter == nullptr) return hipErrorInvalidValue;
-        if (ch > 8) {
-            if (a.nq > 16) return hipErrorInvalidValue;   // the caller splits larger groups, as for the top-k scan
-            return ext ? launch_wide<true, false, true>(ch, a, grid, stream) : launch_wide<false, false, true>(ch, a, grid, stream);
-        }
-        if (a.nq <= 16) return ext ? launch_ch<1, kGroupMax, true>(ch, a, grid, stream) : launch_ch<1, kGroupMax>(ch, a, grid, stream);
-        return ext ? launch_ch<2, kGroupMax, true>(ch, a, grid, stream) : launch_ch<2, kGroupMax>(ch, a, grid, stream);
+    if (a.group_table != nullptr) {  // the group-max scan
+        if (!groups_ok) return hipErrorInvalidValue;
+        return launch_emit<kGroupMax>(ch, ext, a, grid, stream);
     }
     if (a.wgs_per_group > 0 && (ext || ch > 8 || a.work_base)) return hipErrorInvalidValue;
     if (a.wgs_per_group > 0 && a.work_tile != nullptr) {  // the fine scans of several IVF launch groups in one launch

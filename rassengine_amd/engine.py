@@ -358,26 +358,52 @@ class FlatIndex:
         N.check("rass_index_save", self._L.rass_index_save(self._h, path.encode()))
 
     # ---- read path
+    def _queries(self, queries) -> np.ndarray:
+        """The queries of a host search as contiguous float32 [nq, dim]."""
+        q = np.ascontiguousarray(queries, dtype=np.float32)
+        if q.ndim != 2 or q.shape[1] != self.dim:
+            raise ValueError(f"expected [nq, {self.dim}] queries, got {q.shape}")
+        return q
+
+    @staticmethod
+    def _thresholds(min_score, nq: int) -> np.ndarray:
+        """``min_score`` (one number, or one per query) as float32 [nq]; NaN refused."""
+        thr = np.asarray(min_score)
+        if thr.dtype.kind not in "fiu":
+            raise ValueError(f"min_score must be real numbers, not {thr.dtype}")
+        if thr.ndim == 0:
+            thr = np.full(nq, thr)
+        thr = np.ascontiguousarray(thr, dtype=np.float32)
+        if thr.shape != (nq,):
+            raise ValueError("min_score must be one number, or one per query")
+        if np.isnan(thr).any():
+            raise ValueError("min_score must not be NaN")
+        return thr
+
+    @staticmethod
+    def _filters(q_filter, q_filter_mask, nq: int) -> Tuple[Optional[np.ndarray], Optional[np.ndarray]]:
+        """``q_filter`` / ``q_filter_mask`` as int32 [nq] each, or None where not given (a mask needs a filter)."""
+        f = m = None
+        if q_filter is not None:
+            f = np.ascontiguousarray(q_filter, dtype=np.int32)
+            if f.shape != (nq,):
+                raise ValueError("q_filter must be one int32 per query")
+        if q_filter_mask is not None:
+            if f is None:
+                raise ValueError("q_filter_mask needs q_filter")
+            m = np.ascontiguousarray(q_filter_mask, dtype=np.int32)
+            if m.shape != (nq,):
+                raise ValueError("q_filter_mask must be one int32 per query")
+        return f, m
+
     def search(self, queries: np.ndarray, k: int, q_filter: Optional[np.ndarray] = None,
                q_filter_mask: Optional[np.ndarray] = None) -> Tuple[np.ndarray, np.ndarray]:
         """Exact cosine top-k.  Returns (scores f32 [nq,k], ids i64 [nq,k]); raw cosine, best
         first, ties by id ascending, (-inf, -1) padding.  ``q_filter`` restricts query q to rows whose
         tag equals it (-1 = no filter); with ``q_filter_mask`` to rows with ``(tag & mask) == filter``.
         Any k >= 1: k > 32 is served exactly in passes of 32 (``rass_index_search_ex``).  Thread-safe."""
-        q = np.ascontiguousarray(queries, dtype=np.float32)
-        if q.ndim != 2 or q.shape[1] != self.dim:
-            raise ValueError(f"expected [nq, {self.dim}] queries, got {q.shape}")
-        f = m = None
-        if q_filter is not None:
-            f = np.ascontiguousarray(q_filter, dtype=np.int32)
-            if f.shape != (q.shape[0],):
-                raise ValueError("q_filter must be one int32 per query")
-        if q_filter_mask is not None:
-            if f is None:
-                raise ValueError("q_filter_mask needs q_filter")
-            m = np.ascontiguousarray(q_filter_mask, dtype=np.int32)
-            if m.shape != (q.shape[0],):
-                raise ValueError("q_filter_mask must be one int32 per query")
+        q = self._queries(queries)
+        f, m = self._filters(q_filter, q_filter_mask, q.shape[0])
         k = int(k)
         out_s = np.empty((q.shape[0], k), dtype=np.float32)
         out_i = np.empty((q.shape[0], k), dtype=np.int64)
@@ -395,34 +421,13 @@ class FlatIndex:
         first, ties by id ascending, (-inf, -1) padding, and the EXACT number of matching rows — where that exceeds
         ``max_hits`` (<= 4096) the list is the best ``max_hits`` of them.  One corpus pass per 32 queries whatever the
         number of hits; always the exact fp32 scan (the prefilter mode is ignored); fp32 indices only.  Thread-safe."""
-        q = np.ascontiguousarray(queries, dtype=np.float32)
-        if q.ndim != 2 or q.shape[1] != self.dim:
-            raise ValueError(f"expected [nq, {self.dim}] queries, got {q.shape}")
+        q = self._queries(queries)
         nq = q.shape[0]
-        thr = np.asarray(min_score)
-        if thr.dtype.kind not in "fiu":
-            raise ValueError(f"min_score must be real numbers, not {thr.dtype}")
-        if thr.ndim == 0:
-            thr = np.full(nq, thr)
-        thr = np.ascontiguousarray(thr, dtype=np.float32)
-        if thr.shape != (nq,):
-            raise ValueError("min_score must be one number, or one per query")
-        if np.isnan(thr).any():
-            raise ValueError("min_score must not be NaN")
+        thr = self._thresholds(min_score, nq)
         max_hits = int(max_hits)
         if not 1 <= max_hits <= self.MAX_HITS:
             raise ValueError(f"max_hits must be in [1, {self.MAX_HITS}], got {max_hits}")
-        f = m = None
-        if q_filter is not None:
-            f = np.ascontiguousarray(q_filter, dtype=np.int32)
-            if f.shape != (nq,):
-                raise ValueError("q_filter must be one int32 per query")
-        if q_filter_mask is not None:
-            if f is None:
-                raise ValueError("q_filter_mask needs q_filter")
-            m = np.ascontiguousarray(q_filter_mask, dtype=np.int32)
-            if m.shape != (nq,):
-                raise ValueError("q_filter_mask must be one int32 per query")
+        f, m = self._filters(q_filter, q_filter_mask, nq)
         out_s = np.empty((nq, max_hits), dtype=np.float32)
         out_i = np.empty((nq, max_hits), dtype=np.int64)
         total = np.empty((nq,), dtype=np.int64)
@@ -468,22 +473,10 @@ class FlatIndex:
         groups, best first, (-inf, -1, -1) padding, and the EXACT number of distinct groups with a matching row.  One corpus
         pass per 32 queries whatever k (<= 4096) is; always the exact fp32 scan (the prefilter mode is ignored); fp32
         indices only.  A matching row whose group key is >= ``n_groups`` makes the call fail.  Thread-safe."""
-        q = np.ascontiguousarray(queries, dtype=np.float32)
-        if q.ndim != 2 or q.shape[1] != self.dim:
-            raise ValueError(f"expected [nq, {self.dim}] queries, got {q.shape}")
+        q = self._queries(queries)
         nq = q.shape[0]
         k, group_mask, n_groups = self._check_grouped(k, group_mask, n_groups)
-        f = m = None
-        if q_filter is not None:
-            f = np.ascontiguousarray(q_filter, dtype=np.int32)
-            if f.shape != (nq,):
-                raise ValueError("q_filter must be one int32 per query")
-        if q_filter_mask is not None:
-            if f is None:
-                raise ValueError("q_filter_mask needs q_filter")
-            m = np.ascontiguousarray(q_filter_mask, dtype=np.int32)
-            if m.shape != (nq,):
-                raise ValueError("q_filter_mask must be one int32 per query")
+        f, m = self._filters(q_filter, q_filter_mask, nq)
         out_s = np.empty((nq, k), dtype=np.float32)
         out_i = np.empty((nq, k), dtype=np.int64)
         out_g = np.empty((nq, k), dtype=np.int32)
@@ -526,32 +519,11 @@ class FlatIndex:
         groups with a hit and the EXACT number of hits (``search_range``'s total).  One corpus pass per 32 queries; always
         the exact fp32 scan (the prefilter mode is ignored); fp32 indices only.  A hit whose group key is >= ``n_groups``
         makes the call fail.  Thread-safe."""
-        q = np.ascontiguousarray(queries, dtype=np.float32)
-        if q.ndim != 2 or q.shape[1] != self.dim:
-            raise ValueError(f"expected [nq, {self.dim}] queries, got {q.shape}")
+        q = self._queries(queries)
         nq = q.shape[0]
-        thr = np.asarray(min_score)
-        if thr.dtype.kind not in "fiu":
-            raise ValueError(f"min_score must be real numbers, not {thr.dtype}")
-        if thr.ndim == 0:
-            thr = np.full(nq, thr)
-        thr = np.ascontiguousarray(thr, dtype=np.float32)
-        if thr.shape != (nq,):
-            raise ValueError("min_score must be one number, or one per query")
-        if np.isnan(thr).any():
-            raise ValueError("min_score must not be NaN")
+        thr = self._thresholds(min_score, nq)
         size, group_mask, n_groups = self._check_counts(size, group_mask, n_groups)
-        f = m = None
-        if q_filter is not None:
-            f = np.ascontiguousarray(q_filter, dtype=np.int32)
-            if f.shape != (nq,):
-                raise ValueError("q_filter must be one int32 per query")
-        if q_filter_mask is not None:
-            if f is None:
-                raise ValueError("q_filter_mask needs q_filter")
-            m = np.ascontiguousarray(q_filter_mask, dtype=np.int32)
-            if m.shape != (nq,):
-                raise ValueError("q_filter_mask must be one int32 per query")
+        f, m = self._filters(q_filter, q_filter_mask, nq)
         out_g = np.empty((nq, size), dtype=np.int32)
         out_c = np.empty((nq, size), dtype=np.int64)
         out_s = np.empty((nq, size), dtype=np.float32)
@@ -646,25 +618,13 @@ class FlatIndex:
         [nq, k], ids i64 [nq, k]) as ``search`` does: best first, ties by id ascending, (-inf, -1) padding; k <= 4096, nq
         <= 4096.  The scan streams only the 32-row tiles with a bit set.  fp32 indices with dim <= 1024; the prefilter mode
         is ignored.  A bitmap names rows of one ``layout_epoch``.  Thread-safe."""
-        q = np.ascontiguousarray(queries, dtype=np.float32)
-        if q.ndim != 2 or q.shape[1] != self.dim:
-            raise ValueError(f"expected [nq, {self.dim}] queries, got {q.shape}")
+        q = self._queries(queries)
         nq, k = q.shape[0], int(k)
         if not 1 <= k <= N.RASS_MAX_K_MULTIPASS:
             raise ValueError(f"k must be in [1, {N.RASS_MAX_K_MULTIPASS}], got {k}")
         if nq > N.RASS_MAX_DEVICE_BATCH:
             raise ValueError(f"at most {N.RASS_MAX_DEVICE_BATCH} queries per call, got {nq}")
-        f = m = None
-        if q_filter is not None:
-            f = np.ascontiguousarray(q_filter, dtype=np.int32)
-            if f.shape != (nq,):
-                raise ValueError("q_filter must be one int32 per query")
-        if q_filter_mask is not None:
-            if f is None:
-                raise ValueError("q_filter_mask needs q_filter")
-            m = np.ascontiguousarray(q_filter_mask, dtype=np.int32)
-            if m.shape != (nq,):
-                raise ValueError("q_filter_mask must be one int32 per query")
+        f, m = self._filters(q_filter, q_filter_mask, nq)
         on_device = not isinstance(allow, np.ndarray) and hasattr(allow, "data_ptr")
         if not on_device:
             allow = np.ascontiguousarray(allow, dtype=np.uint32)

@@ -1,13 +1,14 @@
 #!/usr/bin/env python3
-"""Are the encoder GEMM kernels of two source trees the same device code?  (CPU: cross-compiles, runs nothing.)
+"""Are the kernels of two source trees the same device code?  (CPU: cross-compiles, runs nothing.)
 
-    python scripts/compare_gemm_device_code.py OLD/rassengine_amd/csrc NEW/rassengine_amd/csrc
+    python scripts/compare_device_code.py OLD/rassengine_amd/csrc NEW/rassengine_amd/csrc [UNIT ...]
 
-Compiles every GEMM unit of each tree (encoder_gemm.hip and gemm_*.hip, whichever exist) with the Makefile's flags plus
---cuda-device-only -S and compares, kernel by kernel: the instruction text of the function (local labels .LBB* / .Ltmp*
-renumbered in order of appearance, comments and debug directives dropped) and the .amdhsa_ resource lines of its kernel
-descriptor (VGPR / AGPR / SGPR counts, scratch, LDS).  One line per kernel; exit status 1 if a kernel differs or the two
-sets of kernel symbols differ."""
+Compiles the named units of each tree (scan_topk group_topk ...: UNIT.hip; by default every encoder GEMM unit,
+encoder_gemm.hip and gemm_*.hip, whichever exist) with the Makefile's flags for that unit, its own "FLAGS +=" line
+included, plus --cuda-device-only -S and compares, kernel by kernel: the instruction text of the function (local labels
+.LBB* / .Ltmp* renumbered in order of appearance, comments and debug directives dropped) and the .amdhsa_ resource lines
+of its kernel descriptor (VGPR / AGPR / SGPR counts, scratch, LDS).  One line per kernel; exit status 1 if a kernel
+differs or the two sets of kernel symbols differ."""
 import glob
 import os
 import re
@@ -17,21 +18,27 @@ import tempfile
 from concurrent.futures import ThreadPoolExecutor
 
 
-def flags(csrc):
+def flags(csrc, unit):
     text = open(os.path.join(csrc, "Makefile"), encoding="utf-8").read()
     arch = re.search(r"^ARCH \?= (\S+)", text, flags=re.M).group(1)
     base = re.search(r"^FLAGS := (.*)$", text, flags=re.M).group(1)
-    return base.replace("$(ARCH)", arch).replace("$(EXTRA)", "").split()
+    own = re.findall(r"^\$\(OBJDIR\)/%s\.o: FLAGS \+= (.*)$" % re.escape(unit), text, flags=re.M)
+    return " ".join([base] + own).replace("$(ARCH)", arch).replace("$(EXTRA)", "").split()
 
 
-def units(csrc):
+def units(csrc, names=()):
+    """The named units' sources (missing ones are left out: their kernels then show as ONLY IN the other tree); no names: the
+    encoder GEMM units."""
+    if names:
+        return [p for p in (os.path.join(csrc, n + ".hip") for n in sorted(names)) if os.path.exists(p)]
     return sorted(p for p in glob.glob(os.path.join(csrc, "*.hip"))
                   if os.path.basename(p) == "encoder_gemm.hip" or os.path.basename(p).startswith("gemm_"))
 
 
 def compile_unit(args):
     csrc, path, out = args
-    cmd = [os.environ.get("HIPCC", "hipcc")] + flags(csrc) + ["--cuda-device-only", "-S", "-o", out, path]
+    unit = os.path.splitext(os.path.basename(path))[0]
+    cmd = [os.environ.get("HIPCC", "hipcc")] + flags(csrc, unit) + ["--cuda-device-only", "-S", "-o", out, path]
     subprocess.run(cmd, check=True, capture_output=True, cwd=csrc)
     return open(out, encoding="utf-8").read()
 
@@ -74,8 +81,8 @@ def kernels(asm):
     return out
 
 
-def tree(csrc, tmp, tag):
-    us = units(csrc)
+def tree(csrc, tmp, tag, names):
+    us = units(csrc, names)
     jobs = [(csrc, u, os.path.join(tmp, "%s_%s.s" % (tag, os.path.basename(u)))) for u in us]
     with ThreadPoolExecutor(max(1, len(jobs))) as ex:
         asms = list(ex.map(compile_unit, jobs))
@@ -90,7 +97,7 @@ def tree(csrc, tmp, tag):
 def main():
     old_csrc, new_csrc = os.path.abspath(sys.argv[1]), os.path.abspath(sys.argv[2])
     with tempfile.TemporaryDirectory() as tmp:
-        old, new = tree(old_csrc, tmp, "old"), tree(new_csrc, tmp, "new")
+        old, new = tree(old_csrc, tmp, "old", sys.argv[3:]), tree(new_csrc, tmp, "new", sys.argv[3:])
     bad = 0
     for k in sorted(set(old) | set(new)):
         if k not in old or k not in new:
