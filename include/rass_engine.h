@@ -61,6 +61,7 @@ typedef enum rass_dtype {
 #define RASS_MAX_QBATCH 32   /* queries per scan launch (two 16-wide MFMA N tiles) */
 #define RASS_MAX_K_MULTIPASS 4096 /* rass_index_search_ex: k > RASS_MAX_K is served in passes of RASS_MAX_K */
 #define RASS_MAX_DEVICE_BATCH 4096 /* queries per rass_index_search_device_batch call */
+#define RASS_MAX_MMR_FETCH 128 /* rass_index_search_mmr: candidates per query; rass_index_rows_gram: rows per list */
 /* Row tag layout used by the Python shim (the engine itself only compares integers): bits 0..23 the
  * patientId dictionary code (0 = none), bits 24..30 the doc_type code (0 = none).  A masked filter
  * (rass_index_search_ex) selects on either field or both with one compare. */
@@ -417,6 +418,59 @@ int rass_index_aggregate_device(rass_index_t* idx, const float* d_queries, int n
                                 const int32_t* d_q_filter, const int32_t* d_q_filter_mask,
                                 int64_t id_base, int32_t* d_out_groups, int64_t* d_out_counts, float* d_out_scores,
                                 int64_t* d_out_ids, int64_t* d_n_buckets, int64_t* d_total_hits, int32_t* d_status);
+
+/* GRAM matrices of short row lists: out[l][i][j] = the fp32 dot product of stored rows rows[l][i] and rows[l][j], as they lie
+ * in the slab (normalised at add time: their cosine).  The similarity structure of a result set, duplicate detection over an
+ * appended batch, and the candidate x candidate input of rass_index_search_mmr.
+ * rows is [n_lists][list_len] row ORDINALS of one layout of the index, 1 <= list_len <= RASS_MAX_MMR_FETCH, n_lists >= 1
+ * (staged in groups; no upper bound); out is [n_lists][list_len][list_len].  PADDING is an ordinal < 0 or >= the row count,
+ * or a tombstoned row: +0.0 in its whole row and column.  An ordinal may repeat.
+ * Every element is ONE v_mfma_f32_16x16x4_f32 chain over the columns (a k-ordered fp32 fma chain from zero, in the kernel's
+ * own column order), the same whatever n_lists, list_len and the position in the list are, and the same inside
+ * rass_index_search_mmr: equal bits everywhere.  out is bitwise symmetric.  The rows are read straight out of the slab (the
+ * gather is fused into the MFMA operand loads): no workspace beyond the 2 MiB staging of the host variant.
+ * fp32 indices of every dim the engine takes, wide rows included; a bf16 index answers RASS_ERR_UNSUPPORTED.  Synchronises. */
+int rass_index_rows_gram(rass_index_t* idx, const int64_t* rows, int n_lists, int list_len, float* out);
+/* Device-resident variant: d_rows and d_out are device memory, the call is stream-ordered on the engine's stream, nothing is
+ * synchronised and nothing is read back. */
+int rass_index_rows_gram_device(rass_index_t* idx, const int64_t* d_rows, int n_lists, int list_len, float* d_out);
+
+/* DIVERSIFIED (MMR) search: a greedy maximal-marginal-relevance re-rank of the exact top fetch_k — what a RAG caller asks for
+ * when near-identical chunks would otherwise fill the prompt.  For query q, with 1 <= k <= fetch_k <= RASS_MAX_MMR_FETCH and
+ * lambda[q] in [0, 1]:
+ * CANDIDATES: the list rass_index_search_ex(k = fetch_k) returns for q on the exact fp32 scan — the same filter semantics
+ * (q_filter NULL, exact, or (tag & q_filter_mask[q]) == q_filter[q]), live rows only, score descending, id ascending.
+ * Candidate i (its RANK) has score s_i, bit-identical to what rass_index_search_ex reports; c <= fetch_k is the number of
+ * real candidates.  The prefilter mode of the index is ignored, as in the range and grouped searches: always the exact scan.
+ * SIMILARITY: G[i][j] = what rass_index_rows_gram reports for the candidates' rows (bit for bit: the same kernel).
+ * SELECTION, all in fp32, every operation rounded on its own (no fused multiply-add): l = lambda[q], m = 1 - l; pen_i is
+ * undefined while nothing is selected.  At each of min(k, c) steps, for every unselected i < c:
+ *     obj_i = (l * s_i) - (m * pen_i)          the second product taken as +0.0 at the first step
+ * the largest obj_i is picked, ties to the lowest rank i.  After picking p: pen_i = G[p][i] if it was undefined, else
+ * G[p][i] where G[p][i] > pen_i, else pen_i (the maximum; negative similarities are NOT clipped to zero).
+ * OUTPUT, in selection order: out_scores[q][t] = s_p (the raw cosine to the query, not the objective), out_ids[q][t] = p's id
+ * as rass_index_search_ex reports it, out_rank[q][t] = p (int32; out_rank may be NULL); (-inf, -1, -1) past min(k, c).
+ * lambda = 1 reproduces rass_index_search_ex(k) bit for bit; lambda = 0 picks the best hit, then always the candidate least
+ * similar to everything picked so far.
+ * Host pointers, any nq (in groups of RASS_MAX_QBATCH); lambda is nq floats.  A NaN or out-of-range lambda, k > fetch_k or
+ * fetch_k > RASS_MAX_MMR_FETCH: RASS_ERR_INVALID.  Cost: ceil(fetch_k / 32) corpus passes per group (chained on the device by
+ * the continuation bound), then one Gram launch and one selection launch.
+ * fp32 indices of every dim the engine takes, wide rows included; a bf16 index answers RASS_ERR_UNSUPPORTED.  An index with
+ * caller-assigned ids (rass_index_add_ex) is served with the limit rass_index_search_ex has: fetch_k <= RASS_MAX_K, beyond:
+ * RASS_ERR_UNSUPPORTED.  IVF, cross-index batches and the sharded multi-GPU front have no MMR form.
+ * Thread-safety and layout epochs as rass_index_search_ex: the engine lock is held while enqueuing only, and the answer
+ * comes from ONE layout of the index. */
+int rass_index_search_mmr(rass_index_t* idx, const float* queries, int nq, int k, int fetch_k,
+                          const float* lambda, const int32_t* q_filter, const int32_t* q_filter_mask,
+                          float* out_scores, int64_t* out_ids, int32_t* out_rank);
+/* Device-resident variant: every pointer is device memory, the call is stream-ordered, nothing is synchronised and nothing is
+ * read back; nq <= RASS_MAX_QBATCH.  Every pass of the candidate search is enqueued by the one call.  Ids are id_base + row
+ * (ignored on an index with caller-assigned ids, which are reported), to be paired with the layout epoch read before the
+ * call.  A query whose lambda is NaN or outside [0, 1] gets the EMPTY list (every slot (-inf, -1, -1)): it cannot be refused
+ * without reading it back.  d_out_rank may be NULL. */
+int rass_index_search_mmr_device(rass_index_t* idx, const float* d_queries, int nq, int k, int fetch_k,
+                                 const float* d_lambda, const int32_t* d_q_filter, const int32_t* d_q_filter_mask,
+                                 int64_t id_base, float* d_out_scores, int64_t* d_out_ids, int32_t* d_out_rank);
 
 /* Prefilter mode (SURVEY §8f-4 "bf16 (or int8)"; the reference's own index is approximate, app/main.py:563-572), OFF by
  * default.  `enable` = RASS_PREFILTER_BF16 (1): keep a bf16 copy of the slab, scan IT (half the HBM bytes per pass, bf16

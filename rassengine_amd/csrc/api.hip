@@ -257,7 +257,7 @@ void rass_engine_destroy(rass_engine_t* eng) {
         delete idx;
     }
     eng->indices.clear();
-    for (void* p : {(void*)eng->d_scratch, (void*)eng->d_batch, (void*)eng->d_cert, (void*)eng->d_io, (void*)eng->d_group, (void*)eng->d_allow, (void*)eng->d_allow_io, (void*)eng->d_qraw, (void*)eng->d_qfilter,
+    for (void* p : {(void*)eng->d_scratch, (void*)eng->d_batch, (void*)eng->d_cert, (void*)eng->d_io, (void*)eng->d_group, (void*)eng->d_allow, (void*)eng->d_allow_io, (void*)eng->d_mmr, (void*)eng->d_qraw, (void*)eng->d_qfilter,
                     (void*)eng->d_out_scores, (void*)eng->d_out_ids, (void*)eng->d_stage, (void*)eng->d_stage_tags,
                     (void*)eng->d_stage_t16, (void*)eng->d_mw_tile, (void*)eng->d_mw_rows, (void*)eng->d_mw_n, (void*)eng->d_mw_mask,
                     (void*)eng->d_mw_base, (void*)eng->d_mw_tags, (void*)eng->d_qmask, (void*)eng->d_after_s, (void*)eng->d_after_i})

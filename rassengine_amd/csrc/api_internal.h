@@ -11,6 +11,7 @@
 //                    the grouped (collapsed) search, the terms aggregation; their shared device-group driver
 //   api_ivf.hip      IVF build, persistence, probe, delta and batch
 //   api_allow.hip    the allow-list search (top-k within a per-query row bitmap), its bitmap builders and its plan
+//   api_mmr.hip      the diversified (MMR) search and the Gram matrices of row lists
 //   api_compact.hip  compaction of a flat index, its layout epoch, the stateless wrappers of compact.hip
 //
 // Ownership model: the engine singleton of a process owns the corpus slabs
@@ -291,6 +292,10 @@ struct rass_engine {
     size_t allow_bytes = 0;
     unsigned char* d_allow_io = nullptr;
     size_t allow_io_bytes = 0;
+    // the diversified (MMR) search and rass_index_rows_gram (api_mmr.hip): the candidates, Gram matrices and staging of one
+    // launch group (MmrView, 2.3 MiB), allocated on first use; used under mu in stream order
+    unsigned char* d_mmr = nullptr;
+    size_t mmr_bytes = 0;
     // host-API staging
     float* d_qraw = nullptr;        // [32][dim]
     int32_t* d_qfilter = nullptr;   // [32]

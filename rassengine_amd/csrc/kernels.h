@@ -181,6 +181,22 @@ hipError_t launch_allow_store(const float* scores, const int64_t* rows, int nq, 
                               const int64_t* id_map, float* out_scores, int64_t* out_ids, float* after_s, int64_t* after_i,
                               hipStream_t stream);
 
+// ---- diversified (MMR) search (mmr.hip): the Gram matrices of short row lists and the greedy selection
+constexpr int kMmrMaxFetch = 128;   // = RASS_MAX_MMR_FETCH: rows per list, candidates per query (two per lane of one wave)
+// out[l][i][j] = the fp32 dot product of slab rows rows[l][i] and rows[l][j] (whole rows: `stride` columns, the padding is
+// zero), l < n_lists, i, j < list_len <= kMmrMaxFetch.  An ordinal < 0 or >= n_rows, or a row whose tag is -1 (tags may be
+// nullptr: no tombstones), is padding: +0.0 in its whole row and column.  One k-ordered v_mfma_f32_16x16x4_f32 chain per
+// element, the same whatever n_lists and list_len are; out is bitwise symmetric.  The rows are read straight from the tile16
+// slab: no workspace.
+hipError_t launch_rows_gram(const float* slab, int64_t stride, const int32_t* tags, int64_t n_rows, const int64_t* rows,
+                            int64_t n_lists, int list_len, float* out, hipStream_t stream);
+// The greedy MMR selection of include/rass_engine.h (rass_index_search_mmr), one wave per query: cand_s / cand_rows
+// [nq][fetch_k] (score desc; rows -1 past the candidates), gram [nq][fetch_k][fetch_k], lambda [nq] -> out_scores / out_ids /
+// out_rank (may be nullptr) [nq][k] in selection order, ids = id_map[row] or id_base + row, (-inf, -1, -1) past the end.
+hipError_t launch_mmr_select(const float* cand_s, const int64_t* cand_rows, const float* gram, const float* lambda, int nq,
+                             int fetch_k, int k, int64_t id_base, const int64_t* id_map, float* out_scores, int64_t* out_ids,
+                             int32_t* out_rank, hipStream_t stream);
+
 // ---- bf16 candidate scan + exact re-rank (scan_bf16.hip)
 struct ScanBf16Args {
     const unsigned short* corpus;   // tile16b bf16 slab

@@ -690,6 +690,88 @@ class FlatIndex:
                                                          ctypes.c_void_p(d_q_filter_mask_ptr or 0), int(id_base),
                                                          ctypes.c_void_p(d_out_scores_ptr), ctypes.c_void_p(d_out_ids_ptr)))
 
+    MAX_MMR_FETCH = N.RASS_MAX_MMR_FETCH   # search_mmr: candidates per query; rows_gram: rows per list
+
+    def rows_gram(self, rows) -> np.ndarray:
+        """Gram matrices of short row lists, ``rass_index_rows_gram``: ``rows`` is int64 [n_lists, L] (or [L]: one list) row
+        ordinals, 1 <= L <= 128.  Returns float32 [n_lists, L, L]: the fp32 dot products of the stored (normalised) rows,
+        bitwise symmetric.  An ordinal < 0 or >= ``rows``, or a tombstoned row, is padding: zeros in its row and column.
+        fp32 indices only."""
+        r = np.ascontiguousarray(rows, dtype=np.int64)
+        if r.ndim == 1:
+            r = r[None, :]
+        if r.ndim != 2 or not 1 <= r.shape[1] <= self.MAX_MMR_FETCH:
+            raise ValueError(f"expected [n_lists, 1..{self.MAX_MMR_FETCH}] row ordinals, got {r.shape}")
+        out = np.empty((r.shape[0], r.shape[1], r.shape[1]), dtype=np.float32)
+        if r.shape[0] == 0:
+            return out
+        N.check("rass_index_rows_gram", self._L.rass_index_rows_gram(self._h, _np_ptr(r), r.shape[0], r.shape[1], _np_ptr(out)))
+        return out
+
+    def rows_gram_device(self, d_rows_ptr: int, n_lists: int, list_len: int, d_out_ptr: int) -> None:
+        """Async, device-resident ``rows_gram`` (``rass_index_rows_gram_device``): int64 [n_lists][list_len] ordinals in,
+        float32 [n_lists][list_len][list_len] out, stream-ordered, nothing read back."""
+        N.check("rass_index_rows_gram_device",
+                self._L.rass_index_rows_gram_device(self._h, ctypes.c_void_p(d_rows_ptr), int(n_lists), int(list_len),
+                                                    ctypes.c_void_p(d_out_ptr)))
+
+    @classmethod
+    def _check_mmr(cls, k, fetch_k) -> Tuple[int, int]:
+        k = int(k)
+        fetch_k = min(cls.MAX_MMR_FETCH, max(4 * k, 16)) if fetch_k is None else int(fetch_k)
+        if not 1 <= fetch_k <= cls.MAX_MMR_FETCH:
+            raise ValueError(f"fetch_k must be in [1, {cls.MAX_MMR_FETCH}], got {fetch_k}")
+        if not 1 <= k <= fetch_k:
+            raise ValueError(f"k must be in [1, fetch_k = {fetch_k}], got {k}")
+        return k, fetch_k
+
+    def search_mmr(self, queries: np.ndarray, k: int, fetch_k: Optional[int] = None, lambda_mult=0.5,
+                   q_filter: Optional[np.ndarray] = None, q_filter_mask: Optional[np.ndarray] = None
+                   ) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """Diversified (MMR) search, ``rass_index_search_mmr``: a greedy maximal-marginal-relevance re-rank of the exact
+        top ``fetch_k`` (default ``min(128, max(4 k, 16))``; 1 <= k <= fetch_k <= 128).  At every step the candidate with
+        the largest ``lambda * cos(query, row) - (1 - lambda) * max(cos(row, picked))`` is picked, ties to the better
+        rank; ``lambda_mult`` is one number in [0, 1] or one per query (1: plain top-k; 0: the best hit, then the least
+        similar).  Returns (scores f32 [nq, k], ids i64 [nq, k], ranks i32 [nq, k]) in selection order: the raw cosine to
+        the query, the row id, and the row's rank in the plain top ``fetch_k``; (-inf, -1, -1) padding.  Filters as
+        ``search``.  Always the exact fp32 scan (the prefilter mode is ignored); fp32 indices only.  Thread-safe."""
+        q = self._queries(queries)
+        nq = q.shape[0]
+        k, fetch_k = self._check_mmr(k, fetch_k)
+        lam = np.asarray(lambda_mult)
+        if lam.dtype.kind not in "fiu":
+            raise ValueError(f"lambda_mult must be real numbers, not {lam.dtype}")
+        if lam.ndim == 0:
+            lam = np.full(nq, lam)
+        lam = np.ascontiguousarray(lam, dtype=np.float32)
+        if lam.shape != (nq,):
+            raise ValueError("lambda_mult must be one number, or one per query")
+        if not np.all((lam >= 0.0) & (lam <= 1.0)):     # False for NaN
+            raise ValueError("lambda_mult must be in [0, 1]")
+        f, m = self._filters(q_filter, q_filter_mask, nq)
+        out_s = np.empty((nq, k), dtype=np.float32)
+        out_i = np.empty((nq, k), dtype=np.int64)
+        out_r = np.empty((nq, k), dtype=np.int32)
+        if nq == 0:
+            return out_s, out_i, out_r
+        N.check("rass_index_search_mmr",
+                self._L.rass_index_search_mmr(self._h, _np_ptr(q), nq, k, fetch_k, _np_ptr(lam), _np_ptr(f), _np_ptr(m),
+                                              _np_ptr(out_s), _np_ptr(out_i), _np_ptr(out_r)))
+        return out_s, out_i, out_r
+
+    def search_mmr_device(self, d_queries_ptr: int, nq: int, k: int, fetch_k: int, d_lambda_ptr: int, d_out_scores_ptr: int,
+                          d_out_ids_ptr: int, d_out_rank_ptr: int = 0, id_base: int = 0, d_q_filter_ptr: int = 0,
+                          d_q_filter_mask_ptr: int = 0) -> None:
+        """Async, device-resident ``search_mmr`` (``rass_index_search_mmr_device``); nq <= 32, every candidate pass enqueued
+        by the one call.  A query whose lambda is NaN or outside [0, 1] gets the empty list."""
+        k, fetch_k = self._check_mmr(k, fetch_k)
+        N.check("rass_index_search_mmr_device",
+                self._L.rass_index_search_mmr_device(self._h, ctypes.c_void_p(d_queries_ptr), int(nq), k, fetch_k,
+                                                     ctypes.c_void_p(d_lambda_ptr), ctypes.c_void_p(d_q_filter_ptr or 0),
+                                                     ctypes.c_void_p(d_q_filter_mask_ptr or 0), int(id_base),
+                                                     ctypes.c_void_p(d_out_scores_ptr), ctypes.c_void_p(d_out_ids_ptr),
+                                                     ctypes.c_void_p(d_out_rank_ptr or 0)))
+
     def search_device(self, d_queries_ptr: int, nq: int, k: int, d_out_scores_ptr: int, d_out_ids_ptr: int,
                       id_base: int = 0, d_q_filter_ptr: int = 0, d_q_filter_mask_ptr: int = 0) -> None:
         """Async, device-resident variant (multi-GPU path, benchmark); nq <= 32."""

@@ -220,6 +220,38 @@ class HipIndexer:
                 return hits, int(totals[0])
         raise RuntimeError(f"{self.index_name}: the index was compacted during every one of {LAYOUT_ATTEMPTS} searches")
 
+    def semantic_search_diverse(self, query_emb: np.ndarray, k: int = TOP_K, fetch_k: Optional[int] = None,
+                                lambda_mult: float = 0.5, filter_clause: Optional[Dict] = None,
+                                patient_id: Optional[str] = None) -> List[Tuple[Dict, float]]:
+        """``semantic_search`` with maximal-marginal-relevance re-ranking (``FlatIndex.search_mmr``): of the exact top
+        ``fetch_k`` chunks (default ``min(128, max(4 k, 16))``) the k that a greedy selection picks, each time the chunk
+        with the largest ``lambda_mult * cos(query, chunk) - (1 - lambda_mult) * max cos(chunk, picked)``: near-identical
+        chunks (a re-issued condition, a note uploaded twice) do not fill the answer while different ones remain among
+        the candidates.  ``lambda_mult`` in [0, 1]: 1 is ``semantic_search``, 0 diversity alone.  Returns
+        ``[(doc_dict, float(score))]`` in selection order (NOT score order); scores are the chunk's similarity to the
+        query in ``semantic_search``'s units (``RASS_SCORE_MODE``).  Filters as ``semantic_search``.  An empty embedding or
+        an unindexed patient gives ``[]``; errors raise (this method has no counterpart in the reference to mirror)."""
+        if _empty(query_emb):
+            return []
+        st: Optional[IndexState] = REGISTRY.get(self.index_name, create=False)
+        if st is None:
+            return []
+        prep = self._prepare(st, query_emb, k, filter_clause, patient_id, None)
+        if prep is None:
+            return []
+        q, k_eff, (fval, fmask) = prep
+        if not hasattr(st.index, "search_mmr"):
+            raise NotImplementedError(f"{self.index_name}: {type(st.index).__name__} has no diversified (MMR) search "
+                                      "(IVF-backed and sharded indices cannot re-rank on the device; use a flat fp32 index)")
+        flt = dict(q_filter=np.array([fval], dtype=np.int32), q_filter_mask=np.array([fmask], dtype=np.int32)) if fmask else {}
+        for _ in range(LAYOUT_ATTEMPTS):    # row ids belong to one layout of the index, as in _knn
+            layout = _layout_epoch(st.index)
+            scores, ids, _ranks = st.index.search_mmr(q, k_eff, fetch_k=fetch_k, lambda_mult=float(lambda_mult), **flt)
+            hits = self._hits(st, scores[0], ids[0], 1.0, None, layout)
+            if hits is not None:
+                return hits
+        raise RuntimeError(f"{self.index_name}: the index was compacted during every one of {LAYOUT_ATTEMPTS} searches")
+
     def semantic_aggregate(self, query_emb: np.ndarray, min_score: float, by: str = "patientId", size: int = 5,
                            filter_clause: Optional[Dict] = None, patient_id: Optional[str] = None) -> Dict[str, Any]:
         """A ``terms`` aggregation on ``by`` (``"patientId"`` or ``"doc_type"``) under the k-NN clause with a ``min_score``:
