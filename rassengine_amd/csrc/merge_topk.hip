@@ -19,6 +19,7 @@
 #include <stdint.h>
 
 #include "kernels.h"
+#include "scan_core.h"   // xor_lane
 
 namespace rass {
 
@@ -33,31 +34,6 @@ struct Cand {
 
 __device__ __forceinline__ bool cand_better(const Cand& a, const Cand& b) {
     return (a.s > b.s) || (a.s == b.s && a.id < b.id);
-}
-
-// One dword of lane (lane ^ STRIDE), in registers: DPP moves inside a row of 16 lanes (quad permutes for 1 and 2; 4 and 8 as a
-// mirror of a mirror: half_mirror(i) = i ^ 7, quad_reverse(i) = i ^ 3, row_mirror(i) = i ^ 15), v_permlane16_swap /
-// v_permlane32_swap across rows (swap(x, x) leaves the even rows / the lower half of x in every row of the first result and
-// the odd rows / the upper half in the second: a lane's partner value is in the result its own row does not name).  Round 3:
-// the 34 compare-exchange stages of a merge were 102 ds_bpermute round trips through the LDS crossbar.
-template <int STRIDE>
-__device__ __forceinline__ int xor_lane(int v, int lane) {
-    static_assert(STRIDE == 1 || STRIDE == 2 || STRIDE == 4 || STRIDE == 8 || STRIDE == 16 || STRIDE == 32, "stride");
-    if constexpr (STRIDE == 1) return __builtin_amdgcn_mov_dpp(v, 0xB1, 0xf, 0xf, true);          // quad_perm [1,0,3,2]
-    if constexpr (STRIDE == 2) return __builtin_amdgcn_mov_dpp(v, 0x4E, 0xf, 0xf, true);          // quad_perm [2,3,0,1]
-    if constexpr (STRIDE == 4)
-        return __builtin_amdgcn_mov_dpp(__builtin_amdgcn_mov_dpp(v, 0x1B, 0xf, 0xf, true), 0x141, 0xf, 0xf, true);
-    if constexpr (STRIDE == 8)
-        return __builtin_amdgcn_mov_dpp(__builtin_amdgcn_mov_dpp(v, 0x141, 0xf, 0xf, true), 0x140, 0xf, 0xf, true);
-    if constexpr (STRIDE == 16) {
-        const auto sw = __builtin_amdgcn_permlane16_swap((unsigned)v, (unsigned)v, false, false);
-        return (int)((lane & 16) ? sw[0] : sw[1]);
-    }
-    if constexpr (STRIDE == 32) {
-        const auto sw = __builtin_amdgcn_permlane32_swap((unsigned)v, (unsigned)v, false, false);
-        return (int)((lane & 32) ? sw[0] : sw[1]);
-    }
-    return v;
 }
 
 template <int STRIDE>

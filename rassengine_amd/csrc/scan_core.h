@@ -1,6 +1,8 @@
 // scan_core.h — device-side building blocks shared by the kernels that stream a tile16 fp32 slab through
 // v_mfma_f32_16x16x4_f32 with the K axis split over 8 waves: the fused scan + top-k (scan_topk.hip) and the
-// k-means assignment of the IVF build (kmeans.hip).  Not part of any ABI.
+// k-means assignment of the IVF build (kmeans.hip).  The pieces that do not depend on the element type — buffer
+// resources (make_rsrc), the lane exchange (xor_lane) and the half-wave lists — also serve the bf16 / int8 scans
+// (scan_bf16.hip, scan_i8.hip) and the merge (merge_topk.hip).  Not part of any ABI.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -70,6 +72,14 @@ constexpr bool mode_is_flat(int mode) {
            mode == kGroupMax || mode == kGroupCount;
 }
 constexpr bool mode_is_sample(int mode) { return mode == kFlatSample || mode == kFlatSampleGroups; }
+
+// A raw buffer resource of `bytes` records at `addr`.  The descriptor must be PROVABLY wave-uniform or hipcc wraps every
+// buffer op in a waterfall loop: pin its inputs with readfirstlane (guide T20).
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(uint64_t addr, unsigned bytes) {
+    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)addr), hi = __builtin_amdgcn_readfirstlane((uint32_t)(addr >> 32));
+    const unsigned nb = __builtin_amdgcn_readfirstlane(bytes);
+    return __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(((uint64_t)hi << 32) | lo), /*stride*/ 0, (int)nb, 0x00020000);
+}
 
 __device__ __forceinline__ TileDesc make_tile_desc(const float* __restrict__ X, int64_t row_stride,
                                                    const int32_t* __restrict__ row_tag, const WorkItem& w) {
@@ -233,6 +243,10 @@ __device__ __forceinline__ float key_score(unsigned k) {
     return __uint_as_float((k & 0x80000000u) ? (k ^ 0x80000000u) : ~k);
 }
 
+// The sample floor's radix selection (scan_topk.hip, scan_bf16.hip, scan_i8.hip) runs over the top kFloorBits bits of the
+// order-preserving keys: the truncation only LOWERS the floor, by < 2^-11 of its value.
+constexpr int kFloorBits = 20;
+
 // The emission of a range scan (kRange), in the place of insert_candidates: a half-wave holds one query's 32 rows of a tile.
 // One ballot; where a half has hits, its first lane adds their number to the query's counter (one vector atomic per (tile,
 // query) at the most) and every hitting lane stores (score bits, local row) at counter + its rank among the half's hits while
@@ -375,23 +389,37 @@ __device__ __forceinline__ void insert_candidates(TopList& L, float& tau, float 
 // the wave at once), compared lane by lane with the running list (best first: list ++ candidates is a bitonic sequence and the
 // lane-wise winner its best 32) and re-sorted by the 5-stage bitonic merge: ~21 compare-exchange stages whatever the number of
 // candidates — the same list the one-by-one insertion ends with ((score desc, row asc) is a total order).
+
+// The lane exchange of that network and of the merge's (merge_topk.hip).
+// One dword of lane (lane ^ STRIDE), in registers: DPP moves inside a row of 16 lanes (quad permutes for 1 and 2; 4 and 8 as a
+// mirror of a mirror: half_mirror(i) = i ^ 7, quad_reverse(i) = i ^ 3, row_mirror(i) = i ^ 15), v_permlane16_swap /
+// v_permlane32_swap across rows (swap(x, x) leaves the even rows / the lower half of x in every row of the first result and
+// the odd rows / the upper half in the second: a lane's partner value is in the result its own row does not name).  Round 3:
+// the 34 compare-exchange stages of a merge (merge_topk.hip) were 102 ds_bpermute round trips through the LDS crossbar.
 template <int STRIDE>
-__device__ __forceinline__ int half_xor_lane(int v, int lane) {   // the dword of lane ^ STRIDE (STRIDE <= 16: inside a half-wave)
-    static_assert(STRIDE == 1 || STRIDE == 2 || STRIDE == 4 || STRIDE == 8 || STRIDE == 16, "stride");
+__device__ __forceinline__ int xor_lane(int v, int lane) {
+    static_assert(STRIDE == 1 || STRIDE == 2 || STRIDE == 4 || STRIDE == 8 || STRIDE == 16 || STRIDE == 32, "stride");
     if constexpr (STRIDE == 1) return __builtin_amdgcn_mov_dpp(v, 0xB1, 0xf, 0xf, true);          // quad_perm [1,0,3,2]
     if constexpr (STRIDE == 2) return __builtin_amdgcn_mov_dpp(v, 0x4E, 0xf, 0xf, true);          // quad_perm [2,3,0,1]
     if constexpr (STRIDE == 4)   // i ^ 4 = half_mirror(quad_reverse(i)): (i ^ 3) ^ 7
         return __builtin_amdgcn_mov_dpp(__builtin_amdgcn_mov_dpp(v, 0x1B, 0xf, 0xf, true), 0x141, 0xf, 0xf, true);
     if constexpr (STRIDE == 8)   // i ^ 8 = row_mirror(half_mirror(i)): (i ^ 7) ^ 15
         return __builtin_amdgcn_mov_dpp(__builtin_amdgcn_mov_dpp(v, 0x141, 0xf, 0xf, true), 0x140, 0xf, 0xf, true);
-    const auto sw = __builtin_amdgcn_permlane16_swap((unsigned)v, (unsigned)v, false, false);
-    return (int)((lane & 16) ? sw[0] : sw[1]);
+    if constexpr (STRIDE == 16) {
+        const auto sw = __builtin_amdgcn_permlane16_swap((unsigned)v, (unsigned)v, false, false);
+        return (int)((lane & 16) ? sw[0] : sw[1]);
+    }
+    if constexpr (STRIDE == 32) {
+        const auto sw = __builtin_amdgcn_permlane32_swap((unsigned)v, (unsigned)v, false, false);
+        return (int)((lane & 32) ? sw[0] : sw[1]);
+    }
+    return v;
 }
 
 template <int STRIDE>
 __device__ __forceinline__ void top_cmpx(float& s, int& i, int lane, bool keep_better) {
-    const float os = __int_as_float(half_xor_lane<STRIDE>(__float_as_int(s), lane));
-    const int oi = half_xor_lane<STRIDE>(i, lane);
+    const float os = __int_as_float(xor_lane<STRIDE>(__float_as_int(s), lane));
+    const int oi = xor_lane<STRIDE>(i, lane);
     const bool mine_better = (s > os) | ((s == os) & (i < oi));
     const bool take = mine_better != keep_better;
     s = take ? os : s;

@@ -44,12 +44,6 @@ struct IDesc {
     __amdgpu_buffer_rsrc_t scales;
 };
 
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(uint64_t addr, unsigned bytes) {
-    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)addr), hi = __builtin_amdgcn_readfirstlane((uint32_t)(addr >> 32));
-    const unsigned nb = __builtin_amdgcn_readfirstlane(bytes);
-    return __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(((uint64_t)hi << 32) | lo), 0, (int)nb, 0x00020000);
-}
-
 // tile t of the slab: rows past n_rows read as zero bytes / scale 0 / tag 0 (and are masked by `rows`); a tile past the end of
 // the slab has zero rows and a zero-sized descriptor on tile 0
 __device__ __forceinline__ IDesc make_idesc(const ScanI8Args& p, int tile, int rows) {
@@ -143,7 +137,6 @@ __global__ __launch_bounds__(kIThreads, kINBuf == 1 ? 4 : 2) void scan_i8_topk_k
                     const float v = (grp < p.sample_groups && q < p.nq) ? p.sample_best[(int64_t)grp * p.nq + q] : -INFINITY;
                     key[pq][half][j] = v == -INFINITY ? 0u : score_key(v);
                 }
-        constexpr int kFloorBits = 20;   // the truncation only lowers the floor
         unsigned T[NT][2] = {};
 #pragma unroll 1
         for (int b = 31; b >= 32 - kFloorBits; --b) {
@@ -530,7 +523,6 @@ __global__ __launch_bounds__(kIThreads, 1) void scan_i8_cert_kernel(ScanI8CertAr
                 const float v = (sg < p.sample_groups && qq < p.nq) ? p.sample_best[(int64_t)sg * kCertQ + qq] : -INFINITY;
                 key[half][j] = v == -INFINITY ? 0u : score_key(v);
             }
-        constexpr int kFloorBits = 20;   // the truncation only lowers the floor
         unsigned T[2] = {0u, 0u};
 #pragma unroll 1
         for (int b = 31; b >= 32 - kFloorBits; --b)

@@ -225,9 +225,8 @@ __global__ __launch_bounds__(kThreads, 2) void scan_topk_f32_kernel(ScanArgs p) 
     // The sample floor of each of this wave's queries: the k-th largest of the sample pass's per-workgroup bests
     // (those workgroups scanned disjoint rows, so k rows of the slab reach it under the query's filters, and so
     // does the final k-th best; fewer than k finite entries: no floor).  Radix selection over the keys' top
-    // kFloorBits bits by ballot counts — the truncation only lowers the floor by < 2^-11 of its value.
+    // kFloorBits bits (scan_core.h) by ballot counts.
     if (MODE == kFlat && p.sample_best != nullptr) {
-        constexpr int kFloorBits = 20;
         unsigned T[NT][2] = {};
         // bit by bit, the wave's 2 x NT selections side by side (each is a chain of dependent scalar steps)
 #pragma unroll 1
@@ -505,7 +504,6 @@ __global__ __launch_bounds__(kThreads, 2) void scan_topk_f32_pair_kernel(ScanArg
     // The sample floors of this wave's 8 queries, as in the kernel above (same keys, same selection, same floors), one
     // launch group after the other: the keys of 4 queries take 16 registers next to the 128 of the query fragments.
     if (p.sample_best != nullptr) {
-        constexpr int kFloorBits = 20;
 #pragma unroll 1
         for (int h = 0; h < 2; ++h) {
             unsigned best_key[2][2][kMaxSampleGroups / 64];

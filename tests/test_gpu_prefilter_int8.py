@@ -207,6 +207,55 @@ def test_int8_prefilter_on_wide_rows_matches_the_flat_scan(gpu, dim):
         eng.close()
 
 
+@pytest.mark.parametrize("dim", [100, 600, 800, 900])
+def test_int8_prefilter_rerank_at_odd_narrow_strides_matches_the_flat_scan(gpu, dim):
+    """The narrow re-rank at fp32 strides 128, 640 and 896 (1, 5 and 7 chunks per K slice; dims 100, 600 and 800 — 900 pads to
+    1 024, the 8-chunk case, next to it), which no other test reaches: ids and scores ≡ the exact flat scan, bit for bit, for a
+    filtered call, a single unfiltered query and the batch call.  Inputs built as in the wide-row test above with seed = dim,
+    picked on the CPU with the oracle's int8 restatement (oracle.candidates_i8 against oracle.search on normalize_c rows, the
+    tombstone applied, once with the filters and once with all six queries unfiltered, which covers the single-query and the
+    batch call): every query's flat top-10 lies inside its int8 top-11 of the 32 candidates kept, so a mismatch here is the
+    re-rank's, never a candidate miss."""
+    from rassengine_amd.engine import Engine
+    torch = gpu
+    eng = Engine(0, dim)
+    try:
+        eng.set_stream(int(torch.cuda.current_stream().cuda_stream))
+        rng = np.random.default_rng(dim)
+        idx = eng.open_index("pf8-odd")
+        n = 3000 + 13
+        x = rng.standard_normal((n, dim)).astype(np.float32)
+        tags = rng.integers(1, 4, size=n).astype(np.int32)
+        idx.add(x[:2000], tags=tags[:2000])
+        idx.add(x[2000:], tags=tags[2000:])
+        idx.delete(11)
+        q = rng.standard_normal((6, dim)).astype(np.float32)
+        qf = rng.integers(-1, 4, size=6).astype(np.int32)
+        assert idx.row_stride == {100: 128, 600: 640, 800: 896, 900: 1024}[dim]
+        k = 10
+        idx.set_prefilter("int8")
+        a = idx.search(q, k, q_filter=qf)
+        a1 = idx.search(q[:1], k)
+        idx.set_prefilter(False)
+        b = idx.search(q, k, q_filter=qf)
+        b1 = idx.search(q[:1], k)
+        assert np.array_equal(a[1], b[1]) and np.array_equal(a[0], b[0]), dim
+        assert np.array_equal(a1[1], b1[1]) and np.array_equal(a1[0], b1[0]), dim
+        assert np.all(a1[1] >= 0)                       # ten real rows, not an empty answer on both sides
+        qd = torch.from_numpy(q).cuda().contiguous()
+        outs = []
+        for mode in ("int8", False):
+            idx.set_prefilter(mode)
+            s = torch.empty((6, k), dtype=torch.float32, device="cuda")
+            i = torch.empty((6, k), dtype=torch.int64, device="cuda")
+            idx.search_device_batch(qd.data_ptr(), 6, k, s.data_ptr(), i.data_ptr())
+            torch.cuda.synchronize()
+            outs.append((s.cpu().numpy(), i.cpu().numpy()))
+        assert np.array_equal(outs[0][1], outs[1][1]) and np.array_equal(outs[0][0], outs[1][0]), dim
+    finally:
+        eng.close()
+
+
 def test_knn_prefetch_on_a_prefilter_index_shares_the_candidate_scan(gpu, monkeypatch):
     """RASS_PREFILTER + the k-NN prefetch: concurrent ask()-shaped requests on one index share ONE candidate-scan launch of
     depth 16 (a quarter of the bytes of the exact scan); the synchronous searches of k <= 16 answer from it with exactly what
