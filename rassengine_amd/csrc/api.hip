@@ -53,7 +53,7 @@ int set_device(const rass_engine* eng) {
 int index_reserve(rass_index* idx, int64_t need_rows) {
     if (need_rows <= idx->capacity) return RASS_OK;
     int64_t cap = std::max<int64_t>(idx->capacity * 2, std::max<int64_t>(need_rows, 1024));
-    cap = (cap + 15) / 16 * 16;  // tile16: whole 16-row blocks
+    cap = pad16(cap);  // tile16: whole 16-row blocks
     float* nrows = nullptr;
     int32_t* ntags = nullptr;
     hipStream_t st = idx->eng->stream;
@@ -65,7 +65,7 @@ int index_reserve(rass_index* idx, int64_t need_rows) {
     hipError_t e = hipMalloc(&nmain, (size_t)cap * idx->stride * elem);
     if (e != hipSuccess) {
         // retry with the exact size before giving up
-        cap = (need_rows + 15) / 16 * 16;
+        cap = pad16(need_rows);
         e = hipMalloc(&nmain, (size_t)cap * idx->stride * elem);
         if (e != hipSuccess) return fail(RASS_ERR_OOM, "index grow: hipMalloc of corpus slab failed");
     }
@@ -80,7 +80,7 @@ int index_reserve(rass_index* idx, int64_t need_rows) {
     }
     // rows of a block past the last appended one must read as finite zeros (they are masked,
     // never ranked): zero the part of the slab the copy below does not overwrite
-    const int64_t used_rows = (idx->rows + 15) / 16 * 16;
+    const int64_t used_rows = pad16(idx->rows);
     unsigned short* nb16 = want_f32 ? nullptr : static_cast<unsigned short*>(nmain);
     signed char* ni8 = nullptr;
     float* nscale = nullptr;
@@ -400,7 +400,7 @@ int rass_index_set_prefilter(rass_index_t* idx, int enable) {
         HIP_TRY(hipMemsetAsync(idx->d_cert_counts, 0, 3 * sizeof(unsigned long long), st));
     }
     if (enable >= 2) {
-        idx->stride_i8 = (idx->stride + 511) / 512 * 512;
+        idx->stride_i8 = pad512(idx->stride);
         if (idx->capacity > 0) {
             HIP_TRY(hipMalloc(reinterpret_cast<void**>(&idx->d_rows_i8), (size_t)idx->capacity * idx->stride_i8));
             HIP_TRY(hipMalloc(reinterpret_cast<void**>(&idx->d_row_scale), (size_t)idx->capacity * sizeof(float)));

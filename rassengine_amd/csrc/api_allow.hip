@@ -63,7 +63,7 @@ int allow_device_group(rass_index* idx, const AllowRequest& r) {
     // the scan reports slab rows (the continuation bound names rows): the store translates them
     const IndexView iv = index_view(idx, r.q_filter != nullptr, 0, /*continued=*/true);
     const int64_t stride = idx->stride;
-    if (iv.rows < 0 || iv.rows > 0x7fffffc0LL) return fail(RASS_ERR_INVALID, "n_rows out of range for one scan");
+    if (iv.rows < 0 || iv.rows > kMaxScanRows) return fail(RASS_ERR_INVALID, "n_rows out of range for one scan");
     if (int rc = check_words(iv.rows, r.words)) return rc;
     if (scratch_layout(nullptr, RASS_MAX_QBATCH, RASS_MAX_K).total > eng->scratch_bytes)
         return fail(RASS_ERR_INVALID, "scan workspace too small");
@@ -273,7 +273,7 @@ int rass_index_allow_plan(rass_index_t* idx, const uint32_t* d_allow, int n_bitm
     if (rc != RASS_OK) return rc;
     hipStream_t st = eng->stream;
     const int64_t n_rows = idx->rows.load(std::memory_order_acquire);
-    if (n_rows > 0x7fffffc0LL) return fail(RASS_ERR_INVALID, "n_rows out of range for one scan");
+    if (n_rows > kMaxScanRows) return fail(RASS_ERR_INVALID, "n_rows out of range for one scan");
     if ((rc = check_words(n_rows, words_per_bitmap)) != RASS_OK) return rc;
     *out_n = 0;
     if (n_rows == 0) return RASS_OK;

@@ -63,7 +63,7 @@ int rass_index_compact(rass_index_t* idx, int64_t* new_row_of, int64_t map_capac
     const bool want_b16 = f32 && idx->prefilter == 1;
     const bool want_i8 = idx->prefilter >= 2;
     const size_t elem = f32 ? sizeof(float) : 2;
-    const int64_t used = (live + 15) / 16 * 16;
+    const int64_t used = pad16(live);
     const int64_t cap = std::max<int64_t>(used, 1024);   // what index_reserve starts from; growth afterwards is its own
 
     // the whole enqueue + synchronise + swap under the engine lock: a search sees the old layout or the new one

@@ -29,7 +29,7 @@ float* emit_queries(const rass_engine* eng) { return range_layout(eng->d_scratch
 // emit_begin: the refusals, before the caller grows or zeroes anything, and the queries normalised into the scratch.
 int emit_begin(rass_index* idx, const EmitRequest& r, const IndexView& iv) {
     const rass_engine* eng = idx->eng;
-    if (iv.rows < 0 || iv.rows > 0x7fffffc0LL) return fail(RASS_ERR_INVALID, "n_rows out of range for one scan");
+    if (iv.rows < 0 || iv.rows > kMaxScanRows) return fail(RASS_ERR_INVALID, "n_rows out of range for one scan");
     if (!rass::scan_supported_stride(idx->stride) || idx->stride > kMaxStride) return fail(RASS_ERR_UNSUPPORTED, kStrideMsg);
     if (range_layout(nullptr).total > eng->scratch_bytes) return fail(RASS_ERR_INVALID, "scan workspace too small");
     HIP_TRY(rass::launch_normalize_rows_f32(r.queries, idx->dim, emit_queries(eng), idx->stride, r.nq, idx->dim, eng->stream, pad_nq(r.nq)));

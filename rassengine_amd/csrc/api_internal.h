@@ -9,7 +9,8 @@
 //                    its pinned slots (k > 32 in passes), search_multi
 //   api_emit.hip     the searches that ride the exact scan and emit instead of ranking: the score-threshold (range) search,
 //                    the grouped (collapsed) search, the terms aggregation; their shared device-group driver
-//   api_ivf.hip      IVF build, persistence, probe, delta and batch
+//   api_ivf.hip      IVF: the host-planned and the device-planned build on one build tail, persistence over one section
+//                    list, the probe and the batch on one fine scan, the delta, the host API (host_groups)
 //   api_allow.hip    the allow-list search (top-k within a per-query row bitmap), its bitmap builders and its plan
 //   api_mmr.hip      the diversified (MMR) search and the Gram matrices of row lists
 //   api_compact.hip  compaction of a flat index, its layout epoch, the stateless wrappers of compact.hip
@@ -38,6 +39,7 @@
 #include <mutex>
 #include <new>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/rass_engine.h"
@@ -65,12 +67,16 @@ constexpr int kNarrowStride = 1024;   // above it a row is "wide": flat fp32 sca
 constexpr int64_t kStageRows = 8192;  // host -> device staging granule for add()
 constexpr int kHostSlots = 8;
 constexpr int kMultiMaxItems = 65536;  // 32-row tiles per cross-index batch (2 M rows over all its indices)
+constexpr int kIvfMaxLists = 32768;    // lists of one IVF
+constexpr int64_t kMaxScanRows = 0x7fffffc0LL;   // rows of one scan / one IVF slab (ivf_build.hip: kSlabLimit)
 
 inline int64_t pad128(int64_t d) { return (d + 127) / 128 * 128; }
 // The row stride of an index of `dim` columns: whole 128-column units (8 waves x one 16-column chunk); above 1 024
 // columns whole 256-column units (the wide-row scan walks a wave's slice in an even number of chunks per panel).
 inline int64_t pad_stride(int64_t d) { return d <= kNarrowStride ? pad128(d) : (d + 255) / 256 * 256; }
 constexpr const char* kStrideMsg = "row_stride must be 128*{1..8} elements (dim <= 1024) or 256*{5..8} (dim <= 2048)";
+inline int64_t pad512(int64_t d) { return (d + 511) / 512 * 512; }   // bytes per row of an int8 copy (stride_i8)
+inline int64_t pad16(int64_t rows) { return (rows + 15) / 16 * 16; }  // rows of a tile16 slab: whole 16-row blocks
 inline int pad_nq(int nq) { return nq <= 16 ? 16 : 32; }   // query rows a launch group's kernels read: whole 16-wide MFMA N tiles
 
 int device_cus(int device);   // compute units of a device, asked once per device (one cache, api.hip)
@@ -93,6 +99,20 @@ void set_plan(Args& a, const IvfPlan& p) {
     a.work_rows = p.work_rows;
     a.work_mask = p.work_mask;
     a.n_work = p.n_work;
+}
+
+// What every bf16 / int8 candidate scan adds per launch group to bf16_args / i8_args (declared below): the converted queries,
+// the filters (mask: nullptr = exact compare), the per-workgroup lists and nq.
+template <class Args>
+void set_group(Args& a, const void* q, const int32_t* q_filter, const int32_t* q_filter_mask, float* part_scores, int64_t* part_ids,
+               int nq) {
+    if constexpr (std::is_same<Args, rass::ScanBf16Args>::value) a.q_bf16 = static_cast<const unsigned short*>(q);
+    else a.q_i8 = static_cast<const signed char*>(q);
+    a.q_filter = q_filter;
+    a.q_filter_mask = q_filter_mask;
+    a.part_scores = part_scores;
+    a.part_ids = part_ids;
+    a.nq = nq;
 }
 
 // Extended per-query filters of a scan (kernels.h ScanArgs): all-null = the plain kernel variant.
@@ -554,8 +574,8 @@ struct SlotGuard {
     ~SlotGuard() { slot_release(eng, sl); }
 };
 // The host API's round trip of one launch group through the slot `sl`: the caller's queries (and filters / masks, where
-// given) to the slot and on to the engine's device staging; the group's k results per query back to the slot, with the
-// slot's event recorded behind them.  The caller holds eng->mu for both enqueues.
+// given) to the slot and on to the engine's device staging; the group's k results per query (and a probe's scanned rows)
+// back to the slot.  The caller holds eng->mu for both enqueues and records the slot's event behind them (host_groups does).
 void slot_fill(HostSlot* sl, int dim, const float* queries, const int32_t* q_filter, const int32_t* q_filter_mask, int b);
 int slot_upload(rass_engine* eng, HostSlot* sl, int dim, bool filter, bool mask, int b);
 int slot_download(rass_engine* eng, HostSlot* sl, int b, int k, const int64_t* d_scanned = nullptr);
@@ -569,15 +589,14 @@ int slot_grow_io(HostSlot* sl, size_t need);
 // by stream order -- their upload, `enqueue(sl, done, b)` (the group's own uploads, its device search, its downloads) and the
 // slot's event; the wait happens on that event without the lock, and `collect(sl, done, b)` hands the group's answer to the
 // caller.  io_bytes > 0: the slot's h_io holds at least that many bytes from the first `fill` on, eng->d_io when `enqueue`
-// runs.  The slot is released on return.
+// runs (0: neither block is touched).  The slot is released on return.  The (engine, dim) form serves a search that has no
+// flat index of its own (the IVF); the index form forwards to it.
 inline void no_fill(HostSlot*, int, int) {}
 template <class Fill, class Enqueue, class Collect>
-int host_groups(rass_index* idx, const float* queries, int nq, const int32_t* q_filter, const int32_t* q_filter_mask, size_t io_bytes,
-                Fill&& fill, Enqueue&& enqueue, Collect&& collect) {
-    rass_engine* eng = idx->eng;
+int host_groups(rass_engine* eng, int dim, const float* queries, int nq, const int32_t* q_filter, const int32_t* q_filter_mask,
+                size_t io_bytes, Fill&& fill, Enqueue&& enqueue, Collect&& collect) {
     int rc = set_device(eng);
     if (rc != RASS_OK) return rc;
-    const int dim = idx->dim;
     SlotGuard guard(eng);
     HostSlot* sl = guard.sl;
     if ((rc = slot_grow_io(sl, io_bytes)) != RASS_OK) return rc;
@@ -598,6 +617,11 @@ int host_groups(rass_index* idx, const float* queries, int nq, const int32_t* q_
         done += b;
     }
     return RASS_OK;
+}
+template <class Fill, class Enqueue, class Collect>
+int host_groups(rass_index* idx, const float* queries, int nq, const int32_t* q_filter, const int32_t* q_filter_mask, size_t io_bytes,
+                Fill&& fill, Enqueue&& enqueue, Collect&& collect) {
+    return host_groups(idx->eng, idx->dim, queries, nq, q_filter, q_filter_mask, io_bytes, fill, enqueue, collect);
 }
 
 // One attempt of rass_index_search_ex (api_search.hip).  exact = true: every pass on the exact fp32 scan, whatever the index's

@@ -301,7 +301,7 @@ int scan_launch(const ScanRequest& r) {
     hipStream_t st = r.st;
     if (int rc = check_nq(nq)) return rc;
     if (int rc = check_k(k)) return rc;
-    if (r.n_rows < 0 || r.n_rows > 0x7fffffc0LL) return fail(RASS_ERR_INVALID, "n_rows out of range for one scan");
+    if (r.n_rows < 0 || r.n_rows > kMaxScanRows) return fail(RASS_ERR_INVALID, "n_rows out of range for one scan");
     if (!rass::scan_supported_stride(stride) || stride > kMaxStride)
         return fail(RASS_ERR_UNSUPPORTED, kStrideMsg);
     if (r.q_dim > stride) return fail(RASS_ERR_INVALID, "dim exceeds row_stride");
@@ -383,13 +383,8 @@ int bf16_scan_launch(rass_index* idx, const FlatRequest& r) {
     HIP_TRY(rass::launch_queries_to_bf16(L.q_padded, L.q_bf16, (int64_t)pad_nq(nq) * stride, st));
     const int grid = scan_grid((rows + 63) / 64, k, eng->n_cus);
     rass::ScanBf16Args a = bf16_args(idx, rows, r.row_tag, k);
-    a.q_bf16 = L.q_bf16;
-    a.q_filter = r.q_filter;
-    a.part_scores = L.part_scores;
-    a.part_ids = L.part_ids;
-    a.nq = nq;
+    set_group(a, L.q_bf16, r.q_filter, r.q_filter_mask, L.part_scores, L.part_ids, nq);
     a.id_base = r.id_map ? 0 : r.id_base;
-    a.q_filter_mask = r.q_filter_mask;
     a.q_after_score = r.after_score;
     a.q_after_id = r.after_row;
     // the sample floor pays where many candidates are kept (k = 10: 96.1 k queries/s without it, 89.9 k with its extra launch;
@@ -426,12 +421,7 @@ int prefilter_launch(rass_index* idx, const FlatRequest& r) {
     if (idx->prefilter == 2) {
         HIP_TRY(rass::launch_queries_to_i8(L.q_padded, L.q_bf16, nq_pad, stride, idx->stride_i8, st));
         rass::ScanI8Args a = i8_args(idx, rows, r.row_tag, kc);
-        a.q_i8 = reinterpret_cast<const signed char*>(L.q_bf16);
-        a.q_filter = r.q_filter;
-        a.q_filter_mask = r.q_filter_mask;
-        a.part_scores = L.part_scores;
-        a.part_ids = L.part_ids;
-        a.nq = nq;
+        set_group(a, L.q_bf16, r.q_filter, r.q_filter_mask, L.part_scores, L.part_ids, nq);
         if (i8_sample_floor(rows, grid)) {   // the sample launch: the first 64 * grid rows, the best score per workgroup
             rc = sample_prelaunch(a, grid, L.sample_best, rass::launch_scan_i8_topk, st);
             if (rc != RASS_OK) return rc;
@@ -440,12 +430,7 @@ int prefilter_launch(rass_index* idx, const FlatRequest& r) {
     } else {
         HIP_TRY(rass::launch_queries_to_bf16(L.q_padded, L.q_bf16, (int64_t)nq_pad * stride, st));
         rass::ScanBf16Args a = bf16_args(idx, rows, r.row_tag, kc);
-        a.q_bf16 = L.q_bf16;
-        a.q_filter = r.q_filter;
-        a.q_filter_mask = r.q_filter_mask;
-        a.part_scores = L.part_scores;
-        a.part_ids = L.part_ids;
-        a.nq = nq;
+        set_group(a, L.q_bf16, r.q_filter, r.q_filter_mask, L.part_scores, L.part_ids, nq);
         if (!r.q_filter_mask && i8_sample_floor(rows, grid)) {
             rc = sample_prelaunch(a, grid, L.sample_best, rass::launch_scan_bf16_topk, st);
             if (rc != RASS_OK) return rc;

@@ -48,7 +48,6 @@ int slot_download(rass_engine* eng, HostSlot* sl, int b, int k, const int64_t* d
     HIP_TRY(hipMemcpyAsync(sl->h_out_s, eng->d_out_scores, (size_t)b * k * sizeof(float), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(sl->h_out_i, eng->d_out_ids, (size_t)b * k * sizeof(int64_t), hipMemcpyDeviceToHost, st));
     if (d_scanned) HIP_TRY(hipMemcpyAsync(sl->h_scanned, d_scanned, 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipEventRecord(sl->done, st));
     return RASS_OK;
 }
 
@@ -111,7 +110,7 @@ int scan_launch_batch(rass_index* idx, const FlatRequest& r, int64_t gs, int64_t
     const int64_t rows = iv.rows;
     const int64_t stride = idx->stride;
     if (int rc = check_k(k)) return rc;
-    if (rows < 0 || rows > 0x7fffffc0LL) return fail(RASS_ERR_INVALID, "n_rows out of range for one scan");
+    if (rows < 0 || rows > kMaxScanRows) return fail(RASS_ERR_INVALID, "n_rows out of range for one scan");
     if (!rass::scan_supported_stride(stride) || stride > kMaxStride)
         return fail(RASS_ERR_UNSUPPORTED, kStrideMsg);
     const int groups = (nq + RASS_MAX_QBATCH - 1) / RASS_MAX_QBATCH;
@@ -243,15 +242,14 @@ int prefilter_launch_batch(rass_index* idx, const FlatRequest& r, int64_t gs, in
     for (int g = 0; g < groups; ++g) {
         const int b = std::min(RASS_MAX_QBATCH, nq - g * 32);
         const unsigned char* q_g = L.q_small + (int64_t)g * 32 * qs_stride;
+        const int32_t* q_filter_g = r.q_filter ? r.q_filter + g * 32 : nullptr;   // (a batch takes no filter mask)
+        float* part_scores_g = L.part_scores + (int64_t)g * L.part_per_group;
+        int64_t* part_ids_g = L.part_ids + (int64_t)g * L.part_per_group;
         // the bracket holds a group's own sample launch too
         rc = timed_launch(eng, st, [&]() -> int {
             if (i8) {
                 rass::ScanI8Args a = i8_args(idx, rows, iv.row_tag, kc);
-                a.q_i8 = reinterpret_cast<const signed char*>(q_g);
-                a.q_filter = r.q_filter ? r.q_filter + g * 32 : nullptr;
-                a.part_scores = L.part_scores + (int64_t)g * L.part_per_group;
-                a.part_ids = L.part_ids + (int64_t)g * L.part_per_group;
-                a.nq = b;
+                set_group(a, q_g, q_filter_g, nullptr, part_scores_g, part_ids_g, b);
                 if (one_sample) {
                     a.sample_best = L.group_sample(g);
                     a.sample_groups = grid;
@@ -262,11 +260,7 @@ int prefilter_launch_batch(rass_index* idx, const FlatRequest& r, int64_t gs, in
                 return HIP_RC(rass::launch_scan_i8_topk(a, grid, st));
             }
             rass::ScanBf16Args a = bf16_args(idx, rows, iv.row_tag, kc);
-            a.q_bf16 = reinterpret_cast<const unsigned short*>(q_g);
-            a.q_filter = r.q_filter ? r.q_filter + g * 32 : nullptr;
-            a.part_scores = L.part_scores + (int64_t)g * L.part_per_group;
-            a.part_ids = L.part_ids + (int64_t)g * L.part_per_group;
-            a.nq = b;
+            set_group(a, q_g, q_filter_g, nullptr, part_scores_g, part_ids_g, b);
             if (floor_on) {
                 const int src = sample_prelaunch(a, grid, L.group_sample(g), rass::launch_scan_bf16_topk, st);
                 if (src != RASS_OK) return src;
@@ -295,8 +289,9 @@ int search_device_locked(rass_index_t* idx, const FlatRequest& r) {
 
 }  // namespace
 
-// One attempt of rass_index_search_ex.  Not on host_groups (nor is search_multi_once): its groups run PASSES, each with its own
-// lock, upload and wait, and the cross-index batch builds a work list under the lock — folding either in would add flags there.
+// One attempt of rass_index_search_ex.  Not on host_groups, and with search_multi_once the only host search that is not (the
+// IVF's host round trip rides it too): its groups run PASSES, each with its own lock, upload and wait, and the cross-index batch
+// builds a work list under the lock — folding either in would add flags there.  Both record the slot's event themselves.
 int search_ex_once(rass_index* idx, const float* queries, int nq, int k, const int32_t* q_filter, const int32_t* q_filter_mask,
                    float* out_scores, int64_t* out_ids, bool exact) {
     rass_engine* eng = idx->eng;
@@ -335,6 +330,7 @@ int search_ex_once(rass_index* idx, const float* queries, int nq, int k, const i
                 if (rc != RASS_OK) return rc;
                 rc = slot_download(eng, sl, b, kk);
                 if (rc != RASS_OK) return rc;
+                HIP_TRY(hipEventRecord(sl->done, st));
             }
             HIP_TRY(hipEventSynchronize(sl->done));
             for (int q = 0; q < b; ++q) {
@@ -577,6 +573,7 @@ static int search_multi_once(rass_engine* eng, rass_index_t* const* idxs, const 
             HIP_TRY(rass::launch_merge_topk(L.part_scores, L.part_ids, grid, b, k, eng->d_out_scores, eng->d_out_ids, st));
             rc = slot_download(eng, sl, b, k);
             if (rc != RASS_OK) return rc;
+            HIP_TRY(hipEventRecord(sl->done, st));
         }
         HIP_TRY(hipEventSynchronize(sl->done));
         memcpy(out_scores + (int64_t)done * k, sl->h_out_s, (size_t)b * k * sizeof(float));

@@ -234,6 +234,64 @@ def test_device_build_equals_host_build(gpu, tmp_path, n, dim):
         eng.close()
 
 
+def test_both_builds_agree_on_degenerate_slabs(gpu, tmp_path):
+    """97 rows (no multiple of a tile) over 3 lists of which one stays empty, down to a prefix whose every row is dead: zero
+    tiles, the slab is the single padding tile.  At dim 128 a bf16 slab is refused, by both builders alike."""
+    from rassengine_amd.engine import Engine
+    from rassengine_amd.ivf import IvfIndex
+    torch = gpu
+    dim, nlist, n = 128, 3, 97
+    rng = np.random.default_rng(97)
+    centres = rng.standard_normal((nlist, dim)).astype(np.float32)
+    x, tags = _clustered(rng, n, centres), _tags(rng, n)
+    q = _clustered(rng, 8, centres, sigma=0.7)
+    h_assign = rng.choice(np.array([0, 2], dtype=np.int32), size=n)          # list 1 receives no row
+    eng = Engine(0, dim)
+    try:
+        flat = eng.open_index("degenerate")
+        flat.add(x, tags=tags)
+        dead = {3, 40, 63, 64, 96}
+        for r in sorted(dead):
+            flat.delete(r)
+        cent = torch.from_numpy(centres).cuda()
+        d_assign = torch.zeros(128, dtype=torch.int32, device="cuda")
+        d_assign[:n] = torch.from_numpy(h_assign).cuda()
+        for n_rows in (-1, 64, 32):
+            if n_rows == 32:
+                for r in sorted(set(range(32)) - dead):                      # every covered row is dead
+                    flat.delete(r)
+            for dtype in ("f32", "bf16", "int8"):
+                where = (dtype, n_rows)
+                if dtype == "bf16":
+                    with pytest.raises(Exception, match="multiple of 256"):
+                        IvfIndex.build(flat, nlist=nlist, centroids=cent, dtype=dtype, assign=h_assign, n_rows=n_rows)
+                    with pytest.raises(Exception, match="multiple of 256"):
+                        IvfIndex.build_device(flat, cent, d_assign, dtype=dtype, n_rows=n_rows)
+                    continue
+                host = IvfIndex.build(flat, nlist=nlist, centroids=cent, dtype=dtype, assign=h_assign, n_rows=n_rows)
+                dev = IvfIndex.build_device(flat, cent, d_assign, dtype=dtype, n_rows=n_rows)
+                try:
+                    assert dev.covered_rows == host.covered_rows == (n if n_rows < 0 else n_rows), where
+                    assert dev.rows == host.rows and np.array_equal(dev.list_sizes, host.list_sizes), where
+                    if n_rows == 32:
+                        assert host.rows == 0, where
+                    host_path = _saved(host, str(tmp_path / "host.ivf"))
+                    assert _same_file(host_path, _saved(dev, str(tmp_path / "dev.ivf"))), where
+                    for nprobe in (1, 3):
+                        a, b = host.search_delta(flat, q, 5, nprobe), dev.search_delta(flat, q, 5, nprobe)
+                        assert np.array_equal(a[1], b[1]) and np.array_equal(a[0], b[0]), (where, nprobe)
+                    back = IvfIndex.load(eng, host_path)
+                    try:
+                        assert _same_file(_saved(back, str(tmp_path / "back.ivf")), host_path), where
+                    finally:
+                        back.close()
+                finally:
+                    host.close()
+                    dev.close()
+    finally:
+        eng.close()
+
+
 # ------------------------------------------------------------------------------------------------ 3. / 4. absorb == fresh build
 def test_absorb_equals_a_fresh_build_from_the_same_assignment(gpu, tmp_path):
     from rassengine_amd.engine import Engine, FlatIndex
