@@ -207,16 +207,23 @@ __device__ __forceinline__ void issue_half_loads(HalfRegs<CH>& r, const TileDesc
 
 // multiply_and_refill for one block: the same k-ordered v_mfma_f32_16x16x4_f32 chain per (row, query) from zero — so the same
 // partial, bit for bit — with the NT accumulators advanced round-robin (NT - 1 >= 2 independent MFMAs between a producer and
-// its consumer), each consumed register re-loaded from the same block of the `next` tile, and between(j) after chunk j.
-template <int CH, int NT, typename Between>
+// its consumer), each consumed register re-loaded from the same block of the `next` tile, before(j) ahead of chunk j's MFMAs
+// and between(j) after them.  before(j) is where the ranking ISSUES its LDS reads (pinned there by a sched_barrier: hipcc sinks
+// them to their first use otherwise); between(j) consumes them, 16 MFMAs (>= 512 pipe cycles) later, so they have landed when
+// the ranking asks for them.  That sched_barrier holds back LDS instructions and MFMAs only (mask 0x16: VALU, SALU and VMEM may
+// cross): a full one also pins the caller's loop-top work — next tile's descriptor, tag load — ahead of chunk 0's first MFMA,
+// where hipcc otherwise threads it between the MFMAs, and that cost the stripped pass 7-10 us of 1 050.
+template <int CH, int NT, typename Before, typename Between>
 __device__ __forceinline__ void multiply_and_refill_half(HalfRegs<CH>& r, const f32x4 (&qf)[NT][CH], f32x4 (&acc)[NT],
                                                          const TileDesc& next, int voff_lane, int soff0,
-                                                         Between&& between) {
+                                                         Before&& before, Between&& between) {
     static_assert(NT >= 3, "a dependent MFMA issues 40 cycles after its producer: keep two others between them");
 #pragma unroll
     for (int nt = 0; nt < NT; ++nt) acc[nt] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int j = 0; j < CH; ++j) {
+        before(j);
+        __builtin_amdgcn_sched_barrier(0x16);
         const f32x4 a0 = r.a[j];
 #define RASS_KSTEP(comp)                                                                                              \
     _Pragma("unroll") for (int nt = 0; nt < NT; ++nt)                                                                 \

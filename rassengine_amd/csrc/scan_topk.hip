@@ -440,7 +440,11 @@ __global__ __launch_bounds__(kThreads, 2) void scan_topk_f32_kernel(ScanArgs p) 
 // 16..31, so the dump and the ranking address it exactly as above (same pitch, same bank pattern), and a half-wave
 // still ranks the 32 rows of a tile for one query in ascending row order.  One tile and one barrier per iteration
 // (256 MFMAs per wave, as above), two images; the previous tile's ranking is cut into 4 parts (one per N-tile: a wave
-// owns queries pq * 16 + {0, 8} + wid, 8 of them) placed between the MFMA chunks.
+// owns queries pq * 16 + {0, 8} + wid, 8 of them), each wrapped AROUND one MFMA chunk: its LDS reads are issued ahead of the
+// chunk's 16 MFMAs and consumed behind them (rank_load / rank_use below).  The 8 waves run in lockstep behind the per-tile
+// barrier, so whatever the ranking waits for behind a chunk, the matrix pipe waits for too: no LDS round trip is left there.
+// 1 087 -> 1 069 us per pass at CH = 8, 27 % of what the ranking cost (DESIGN.md s3,
+// profiles/scan_pair_rank_prefetch_experiment.txt).
 // Queries 0..31 are group g's (q_padded, q_filter, sample_best, part_*), 32..63 group g + 1's: q_padded +
 // q_group_stride, q_filter + 32, sample_best + 32 * kMaxSampleGroups, part_* + part_group_stride — where the two
 // launches it replaces read and write.  Flat scans without EXT only.
@@ -547,31 +551,54 @@ __global__ __launch_bounds__(kThreads, 2) void scan_topk_f32_pair_kernel(ScanArg
         for (int nt = 0; nt < NT; ++nt)
             *reinterpret_cast<f32x4*>(P + (wid * NQ + nt * 16 + m) * kPitch + blk * 16 + 4 * g) = acc[nt];
     };
-    // Rank one (tile, N-tile pq) of a dumped tile: sum the 8 K-partials in fixed order, filter, insert.
-    auto rank_part = [&](const WorkItem& w, int buf, int pq) {
+    // Rank one (tile, N-tile pq) of a dumped tile, in two steps.  rank_load issues EVERY LDS read of the part, unconditionally
+    // — the 8 K-partials, the row's tag, the query's filter and floor: 11 registers per part — and rank_use, one MFMA chunk
+    // later, sums the partials in the fixed order ((p0 + p1) + ...) + p7, filters and inserts.  Written as one function with a
+    // short-circuit predicate this compiled to three DEPENDENT LDS round trips behind two exec-mask branches (tag, then
+    // filter, then partials and floor) after a chunk's last MFMA, in all 8 waves at once; the predicate is bitwise now, so
+    // nothing but insert_candidates' loop branches.  Every part has its own registers: at small CH two parts share a slot.
+    struct RankIn {
+        float pz[kWaves];
+        int tag, qfilt;
+        float floor;
+    };
+    [[maybe_unused]] RankIn RI[NT];
+    auto rank_load = [&](int buf, int pq) {
 #ifndef RASS_SCAN_PAIR_NORANK  // the timing-only build of the go / no-go experiment (profiles/r05_scan_pair_experiment.txt)
         const float* P = lds + buf * (kWaves * NQ * kPitch);
         const int r = lane & 31;
-        const int row = w.tile * kTileRows + r;
-        const int tag_r = sh_tags[buf][r];
         const int q = pq * 16 + (lane >> 5) * 8 + wid;
-        const int qf1 = sh_qfilt[q];
         const float* src = P + q * kPitch + r;
-        float s = src[0];
 #pragma unroll
-        for (int wv = 1; wv < kWaves; ++wv) s += src[wv * NQ * kPitch];
+        for (int wv = 0; wv < kWaves; ++wv) RI[pq].pz[wv] = src[wv * NQ * kPitch];
+        RI[pq].tag = sh_tags[buf][r];
+        RI[pq].qfilt = sh_qfilt[q];
+        RI[pq].floor = sh_floor[q];
+#endif
+    };
+    auto rank_use = [&](const WorkItem& w, int pq) {
+#ifndef RASS_SCAN_PAIR_NORANK
+        const int r = lane & 31;
+        const int row = w.tile * kTileRows + r;
+        const RankIn& in = RI[pq];
+        float s = in.pz[0];
+#pragma unroll
+        for (int wv = 1; wv < kWaves; ++wv) s += in.pz[wv];
         // the sample floor: k rows of the corpus already score >= floor_q (ties are kept: the id order decides them in the merge)
-        const bool ok = (r < w.rows) && (tag_r != -1) && (qf1 < 0 || qf1 == tag_r) && (s >= sh_floor[q]);
+        const bool ok = (r < w.rows) & (in.tag != -1) & ((in.qfilt < 0) | (in.qfilt == in.tag)) & (s >= in.floor);
         s = ok ? s : -INFINITY;
         insert_candidates(L[pq], tau[pq], s, row, p.k);
 #endif
     };
 
-    // Main loop.  Iteration i multiplies tile i's two blocks and, between the MFMA chunks, ranks tile i-1 out of the
-    // image iteration i-1 dumped (4 parts over the 2 x CH chunk slots).  One barrier per iteration: it orders this
-    // iteration's dumps before the next iteration's reads, and the next iteration's dumps (into the image read now)
-    // behind this iteration's reads.
-    auto slot_of = [](int part) { return ((part + 1) * 2 * CH + NT - 1) / NT - 1; };
+    // Main loop.  Iteration i multiplies tile i's two blocks and ranks tile i-1 out of the image iteration i-1 dumped: 4 parts
+    // over the 2 x CH chunk slots, a part's reads ahead of its slot's MFMAs and its sum / filter / insertion behind them.  The
+    // image was completed at the previous iteration's barrier, so any slot from 0 on may read it: the parts sit EARLY (slots
+    // 1, 5, 9, 13 at CH = 8), which leaves no ranking between the last chunk and the barrier, where an insertion would hold up
+    // all 8 waves, and — where there are slots to choose from — none in chunk 0, whose MFMAs carry the loop-top work.  One
+    // barrier per iteration: it orders this iteration's dumps before the next iteration's reads, and the next iteration's
+    // dumps (into the image read now) behind this iteration's reads.
+    auto slot_of = [](int part) { return (part * 2 * CH) / NT + (2 * CH > NT ? 1 : 0); };
     WorkItem Pw{0, 0, 0u};  // the previous tile (rows = 0: nothing ranks in the first iteration)
     int cur = 0;            // which LDS image this iteration dumps into
     while (t < n_tiles) {
@@ -582,14 +609,21 @@ __global__ __launch_bounds__(kThreads, 2) void scan_topk_f32_pair_kernel(ScanArg
         const WorkItem Wn = get_work<kFlat>(p, t, n_tiles);
         const TileDesc dn = make_tile_desc(p.corpus, p.row_stride, p.row_tag, Wn);
         tag = load_tag(dn);
+        auto load_prev = [&](int slot) {
+#pragma unroll
+            for (int part = 0; part < NT; ++part)
+                if (slot_of(part) == slot) rank_load(cur ^ 1, part);
+        };
         auto rank_prev = [&](int slot) {
 #pragma unroll
             for (int part = 0; part < NT; ++part)
-                if (slot_of(part) == slot) rank_part(Pw, cur ^ 1, part);
+                if (slot_of(part) == slot) rank_use(Pw, part);
         };
-        multiply_and_refill_half<CH, NT>(R0, qf, acc, dn, voff_lane, 0, [&](int j) { rank_prev(j); });
+        multiply_and_refill_half<CH, NT>(R0, qf, acc, dn, voff_lane, 0, [&](int j) { load_prev(j); },
+                                         [&](int j) { rank_prev(j); });
         dump_half(acc, cur, 0);
-        multiply_and_refill_half<CH, NT>(R1, qf, acc, dn, voff_lane, mt_step, [&](int j) { rank_prev(CH + j); });
+        multiply_and_refill_half<CH, NT>(R1, qf, acc, dn, voff_lane, mt_step, [&](int j) { load_prev(CH + j); },
+                                         [&](int j) { rank_prev(CH + j); });
         dump_half(acc, cur, 1);
         W0 = Wn;
         Pw = Wc;
@@ -598,7 +632,10 @@ __global__ __launch_bounds__(kThreads, 2) void scan_topk_f32_pair_kernel(ScanArg
     }
     // the last tile
 #pragma unroll
-    for (int pq = 0; pq < NT; ++pq) rank_part(Pw, cur ^ 1, pq);
+    for (int pq = 0; pq < NT; ++pq) {
+        rank_load(cur ^ 1, pq);
+        rank_use(Pw, pq);
+    }
 #ifdef RASS_SCAN_PAIR_NORANK
     L[0].s = lds[threadIdx.x];  // keeps the dumps alive
 #endif
