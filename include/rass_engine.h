@@ -69,6 +69,16 @@ typedef enum rass_dtype {
 #define RASS_TAG_DOCTYPE_SHIFT 24
 #define RASS_TAG_DOCTYPE_MASK 0x7f000000
 #define RASS_ROW_TAG_DELETED (-1)
+/* Attribute columns of a flat index (rass_index_set_attr) and the predicates over them (rass_index_allow_from_attr_clauses). */
+#define RASS_MAX_ATTRS 8              /* int32 columns per index */
+#define RASS_ATTR_MISSING INT32_MIN   /* "this row has no value": every other int32 is a value */
+#define RASS_MAX_ATTR_CLAUSES 64      /* clauses per query per rass_index_allow_from_attr_clauses call */
+#define RASS_ATTR_ALL 0               /* mode: a row is allowed when ALL of the query's clauses hold */
+#define RASS_ATTR_ANY 1               /*       ... when at least one does */
+#define RASS_ATTR_REPLACE 0           /* combine: the result overwrites the bitmap */
+#define RASS_ATTR_AND 1               /*          ... is ANDed into what the bitmap holds */
+#define RASS_ATTR_OR 2                /*          ... is ORed into it */
+#define RASS_ATTR_ANDNOT 3            /* rass_index_allow_combine only: dst & ~src */
 #define RASS_QFILTER_NONE (-1)
 
 typedef struct rass_engine rass_engine_t;
@@ -334,8 +344,8 @@ int rass_index_search_grouped_device(rass_index_t* idx, const float* d_queries, 
                                      int32_t* d_out_groups, int64_t* d_group_total, int32_t* d_status);
 
 /* ALLOW-LIST search: the exact top-k among the rows a per-query BITMAP allows — the general restriction next to the tag
- * compare: a set of patients or doc types (OpenSearch `terms`), the hit set of a text query (`ids`), a date range or an ACL
- * resolved elsewhere.  A bitmap is uint32 words, bit (r & 31) of word r >> 5 allows row ordinal r; `allow` is
+ * compare: a set of patients or doc types (OpenSearch `terms`), the hit set of a text query (`ids`), an ACL resolved
+ * elsewhere, or a predicate over the index's attribute columns (rass_index_allow_from_attr_clauses: `term`, `range`).  A bitmap is uint32 words, bit (r & 31) of word r >> 5 allows row ordinal r; `allow` is
  * uint32[n_bitmaps][words_per_bitmap], row-major, words_per_bitmap >= ceil(rows / 32) for the index's row count at the call.
  * n_bitmaps = nq: bitmap q belongs to query q; n_bitmaps = 1: ONE bitmap shared by every query (it is read in place, never
  * expanded).  Bits of tombstoned rows, bits at or past the row count and surplus words allow nothing.
@@ -381,6 +391,51 @@ int rass_index_allow_from_tag_values(rass_index_t* idx, const int32_t* values, i
  * the tile that exist) / out_mask (bit q set iff query q has a bit set in the tile).  Synchronises. */
 int rass_index_allow_plan(rass_index_t* idx, const uint32_t* d_allow, int n_bitmaps, int64_t words_per_bitmap, int nq,
                           int32_t* out_tile, int32_t* out_rows, uint32_t* out_mask, int64_t capacity, int64_t* out_n);
+
+/* ATTRIBUTE COLUMNS: up to RASS_MAX_ATTRS typed per-row fields next to the tag — a keyword's dictionary code, an integer, a
+ * date as days since 1970-01-01 — for the stored-field filters OpenSearch takes next to a k-NN clause (`term`, `terms`,
+ * `range`, `exists`).  Column c is int32[capacity] in HBM, allocated by the first rass_index_set_attr on it and filled with
+ * RASS_ATTR_MISSING; an index on which no column was ever set allocates nothing, reads nothing and saves today's bytes.
+ * Valid values are every int32 above RASS_ATTR_MISSING; storing RASS_ATTR_MISSING un-sets a value.  fp32, bf16 and wide-row
+ * indices all take columns (only the allow-list search refuses the latter two, as before).
+ * ORDERING: a row appended by any rass_index_add* (or rass_index_fill_synthetic) reads RASS_ATTR_MISSING in every allocated
+ * column until rass_index_set_attr names it: until then no non-negated clause matches it.  Add, then set, then tombstone what
+ * the rows replace.  The columns follow their rows through growth, rass_index_compact (new ordinals), save and load (a
+ * second flag bit in the file header and a section after the ids; files without columns are unchanged and old files load);
+ * rass_index_delete leaves the values alone: the tombstone in the tag is what counts.
+ * _set_attr: `values` is a HOST array of n int32 for rows [first_row, first_row + n), which must lie within the rows at the
+ *   call; stream-ordered on the engine's stream, the array may be reused on return.  col outside 0 .. RASS_MAX_ATTRS - 1, a
+ *   range outside the rows, or NULL with n > 0: RASS_ERR_INVALID.
+ * _get_attr: the values of rows [first_row, first_row + n) to the HOST array `out`; synchronises.  A column that was never
+ *   set reads as all RASS_ATTR_MISSING.
+ * _attr_mask: bit c set iff column c is allocated.  _device_attr: the device pointer of column c (as rass_index_device_tags;
+ *   invalidated by growth and compaction), NULL for a column that was never set. */
+int rass_index_set_attr(rass_index_t* idx, int col, int64_t first_row, int64_t n, const int32_t* values);
+int rass_index_get_attr(rass_index_t* idx, int col, int64_t first_row, int64_t n, int32_t* out);
+int rass_index_attr_mask(const rass_index_t* idx);
+void* rass_index_device_attr(rass_index_t* idx, int col);
+/* PREDICATES -> BITMAPS: the builder that turns clauses over the columns into the bitmaps rass_index_search_allowed(_device)
+ * consumes.  `clauses` is a HOST array int32[n_clauses][5] = {query, col, lo, hi, negate}.  A clause HOLDS for a row whose
+ * value in `col` is v when v != RASS_ATTR_MISSING && lo <= v && v <= hi; with negate != 0 the result is inverted, so a
+ * missing value passes a negated clause (OpenSearch's must_not over an absent field).  lo > hi holds for nothing; `exists`
+ * is [INT32_MIN + 1, INT32_MAX]; equality is lo == hi; a column that was never set is all-missing.
+ * mode RASS_ATTR_ALL: query q allows a LIVE row iff all of q's clauses hold (no clause: every live row); RASS_ATTR_ANY: iff
+ * at least one holds (no clause: no row).  combine says how the result meets what d_allow already holds — RASS_ATTR_REPLACE,
+ * _AND, _OR — so a formula composes by successive calls, and with rass_index_allow_from_rows / _from_tag_values, which
+ * overwrite: run those first, then refine with _AND.  d_allow is DEVICE memory uint32[n_bitmaps][words_per_bitmap],
+ * words_per_bitmap >= ceil(rows / 32); n_bitmaps = nq, or 1 for one shared bitmap, whose clauses must all name query 0.
+ * Tombstoned rows never get a bit.  Bits at or past the row count and surplus words come out 0 under _REPLACE and _AND and
+ * are left as they were under _OR.  1 <= nq <= RASS_MAX_DEVICE_BATCH (launch groups of RASS_MAX_QBATCH queries: one pass
+ * over the named columns and the tags per group), at most RASS_MAX_ATTR_CLAUSES clauses per query per call; anything outside
+ * those bounds: RASS_ERR_INVALID with the reason in rass_last_error().  Stream-ordered on the engine's stream; the host
+ * array may be reused when the call returns.  A bitmap names rows of ONE layout epoch, as every bitmap does. */
+int rass_index_allow_from_attr_clauses(rass_index_t* idx, const int32_t* clauses, int64_t n_clauses, int nq, int n_bitmaps,
+                                       int mode, int combine, uint32_t* d_allow, int64_t words_per_bitmap);
+/* Word-wise merge of two DEVICE bitmaps of `words` uint32 each, for the formulas one builder call cannot fold (two nested
+ * sub-formulas under one and / or, a negated tag-value set): d_dst = d_dst & d_src (RASS_ATTR_AND), | d_src (RASS_ATTR_OR)
+ * or & ~d_src (RASS_ATTR_ANDNOT; "not x" is the all-live bitmap — an RASS_ATTR_ALL call without clauses — and-not x).  `words`
+ * may span several bitmaps laid out alike.  d_dst and d_src must not overlap.  Stream-ordered on the engine's stream. */
+int rass_index_allow_combine(rass_index_t* idx, uint32_t* d_dst, const uint32_t* d_src, int64_t words, int op);
 
 /* Semantic TERMS AGGREGATION: per-group hit counts above a min_score — OpenSearch's `"aggs": {"x": {"terms": {"field": ...}}}`
  * under a k-NN clause with a min_score, with a `cardinality` and the hit total thrown in.  The group of a row is a bit field

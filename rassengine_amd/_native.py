@@ -31,6 +31,11 @@ RASS_MAX_MMR_FETCH = 128
 RASS_F32 = 0
 RASS_BF16 = 1
 RASS_QFILTER_NONE = -1
+RASS_MAX_ATTRS = 8
+RASS_ATTR_MISSING = -(1 << 31)
+RASS_MAX_ATTR_CLAUSES = 64
+RASS_ATTR_ALL, RASS_ATTR_ANY = 0, 1
+RASS_ATTR_REPLACE, RASS_ATTR_AND, RASS_ATTR_OR, RASS_ATTR_ANDNOT = 0, 1, 2, 3
 
 c_float_p = ctypes.POINTER(ctypes.c_float)
 c_i32_p = ctypes.POINTER(ctypes.c_int32)
@@ -112,6 +117,13 @@ SIGNATURES = {
                                                         ctypes.c_void_p, ctypes.c_int64]),
     "rass_index_allow_plan": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int,
                                              ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, c_i64_p]),
+    "rass_index_set_attr": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p]),
+    "rass_index_get_attr": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p]),
+    "rass_index_attr_mask": (ctypes.c_int, [ctypes.c_void_p]),
+    "rass_index_device_attr": (ctypes.c_void_p, [ctypes.c_void_p, ctypes.c_int]),
+    "rass_index_allow_from_attr_clauses": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int,
+                                                          ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int64]),
+    "rass_index_allow_combine": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int]),
     "rass_index_aggregate": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int,
                                             ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                             ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),

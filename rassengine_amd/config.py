@@ -69,6 +69,11 @@ try:
 except ValueError:
     RASS_COMPACT_FRACTION = 0.0
 RASS_COMPACT_MIN_ROWS = _int("RASS_COMPACT_MIN_ROWS", 65536)
+# Attribute columns (docstore.AttrSchema): up to 8 `field:kind` pairs, kind = keyword | int | date, e.g.
+# "resourceType:keyword,file_type:keyword,chunkDate:date".  add_documents stores these fields of every doc as int32 columns
+# next to the vectors and HipIndexer.semantic_search_filtered filters on them.  Empty (the default): no schema, no columns,
+# the files of an index are what they were.
+RASS_ATTR_FIELDS = os.getenv("RASS_ATTR_FIELDS", "").strip()
 
 
 def get_index_name(user_id: str) -> str:

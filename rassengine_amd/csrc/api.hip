@@ -73,10 +73,19 @@ int index_reserve(rass_index* idx, int64_t need_rows) {
     int64_t* ngid = nullptr;
     e = hipMalloc(reinterpret_cast<void**>(&ntags), (size_t)cap * sizeof(int32_t));
     if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&ngid), (size_t)cap * sizeof(int64_t));
+    int32_t* nattr[RASS_MAX_ATTRS] = {};   // the attribute columns that exist grow with the rows
+    auto free_nattr = [&] {
+        for (int32_t* p : nattr)
+            if (p) (void)hipFree(p);
+    };
+    for (int c = 0; e == hipSuccess && c < RASS_MAX_ATTRS; ++c)
+        if (idx->d_attr[c]) e = hipMalloc(reinterpret_cast<void**>(&nattr[c]), (size_t)cap * sizeof(int32_t));
     if (e != hipSuccess) {
         (void)hipFree(nmain);
         if (ntags) (void)hipFree(ntags);
-        return fail(RASS_ERR_OOM, "index grow: hipMalloc of tag / id arrays failed");
+        if (ngid) (void)hipFree(ngid);
+        free_nattr();
+        return fail(RASS_ERR_OOM, "index grow: hipMalloc of tag / id / attribute arrays failed");
     }
     // rows of a block past the last appended one must read as finite zeros (they are masked,
     // never ranked): zero the part of the slab the copy below does not overwrite
@@ -96,6 +105,12 @@ int index_reserve(rass_index* idx, int64_t need_rows) {
             c = hipMemcpyAsync(ntags, idx->d_tags, (size_t)idx->rows * sizeof(int32_t), hipMemcpyDeviceToDevice, st);
         if (c == hipSuccess && idx->rows > 0)
             c = hipMemcpyAsync(ngid, idx->d_gid, (size_t)idx->rows * sizeof(int64_t), hipMemcpyDeviceToDevice, st);
+        for (int a = 0; c == hipSuccess && a < RASS_MAX_ATTRS; ++a) {   // the old rows' values, MISSING in the new capacity
+            if (!nattr[a]) continue;
+            c = rass::launch_fill_i32(nattr[a] + idx->rows, cap - idx->rows, RASS_ATTR_MISSING, st);
+            if (c == hipSuccess && idx->rows > 0)
+                c = hipMemcpyAsync(nattr[a], idx->d_attr[a], (size_t)idx->rows * sizeof(int32_t), hipMemcpyDeviceToDevice, st);
+        }
         if (c == hipSuccess && want_b16) {
             if (want_f32) c = hipMalloc(reinterpret_cast<void**>(&nb16), (size_t)cap * idx->stride * 2);
             if (c == hipSuccess) c = hipMemsetAsync(nb16, 0, (size_t)cap * idx->stride * 2, st);
@@ -122,6 +137,7 @@ int index_reserve(rass_index* idx, int64_t need_rows) {
         (void)hipFree(nmain);
         (void)hipFree(ntags);
         (void)hipFree(ngid);
+        free_nattr();
         if (nb16 && want_f32) (void)hipFree(nb16);
         if (ni8) (void)hipFree(ni8);
         if (nscale) (void)hipFree(nscale);
@@ -139,6 +155,10 @@ int index_reserve(rass_index* idx, int64_t need_rows) {
     idx->d_rows = nrows;
     idx->d_tags = ntags;
     idx->d_gid = ngid;
+    for (int a = 0; a < RASS_MAX_ATTRS; ++a) {
+        if (idx->d_attr[a]) (void)hipFree(idx->d_attr[a]);
+        idx->d_attr[a] = nattr[a];
+    }
     idx->d_rows_bf16 = nb16;
     idx->capacity = cap;
     return RASS_OK;
@@ -150,6 +170,29 @@ void index_free_slabs(rass_index* idx) {
         if (p) (void)hipFree(p);
     idx->d_rows = nullptr, idx->d_tags = nullptr, idx->d_gid = nullptr, idx->d_rows_bf16 = nullptr;
     idx->d_rows_i8 = nullptr, idx->d_row_scale = nullptr, idx->d_cert_stats = nullptr, idx->d_cert_counts = nullptr;
+    for (int32_t*& p : idx->d_attr) {
+        if (p) (void)hipFree(p);
+        p = nullptr;
+    }
+}
+
+// Attribute column `col` exists afterwards: allocated over the whole capacity and filled with RASS_ATTR_MISSING on first use.
+// The caller holds idx->mu and eng->mu (a bitmap builder reads the pointer under eng->mu).
+int index_attr_ensure(rass_index* idx, int col) {
+    if (idx->d_attr[col]) return RASS_OK;
+    if (idx->capacity == 0) {
+        if (int rc = index_reserve(idx, 1)) return rc;
+    }
+    int32_t* p = nullptr;
+    if (hipMalloc(reinterpret_cast<void**>(&p), (size_t)idx->capacity * sizeof(int32_t)) != hipSuccess)
+        return fail(RASS_ERR_OOM, "attribute column: hipMalloc failed");
+    const hipError_t e = rass::launch_fill_i32(p, idx->capacity, RASS_ATTR_MISSING, idx->eng->stream);
+    if (e != hipSuccess) {
+        (void)hipFree(p);
+        return hip_fail(e, "launch_fill_i32", __FILE__, __LINE__);
+    }
+    idx->d_attr[col] = p;
+    return RASS_OK;
 }
 
 // The candidate copies of rows [first, first + n) that the index's prefilter mode keeps next to the fp32 slab.
@@ -571,7 +614,9 @@ int rass_index_get_rows(rass_index_t* idx, int64_t first_row, int64_t n, float* 
     return RASS_OK;
 }
 
-// ---- persistence: header + unpadded fp32 rows + tags
+// ---- persistence: header + unpadded fp32 rows + tags [+ ids] [+ attribute columns]
+// SaveHeader.reserved: bit 0 = rows x int64 caller-assigned ids follow the tags; bit 1 = the attribute section follows
+// them: int32 n_cols, then per allocated column int32 col and rows x int32 values.  No column: today's bytes.
 struct SaveHeader {
     char magic[8];
     int32_t version;
@@ -598,7 +643,9 @@ int rass_index_save(rass_index_t* idx, const char* path) {
     h.rows = idx->rows;
     h.deleted = idx->deleted;
     const bool save_gid = idx->has_gid.load();
-    h.reserved = save_gid ? 1 : 0;  // 1: rows x int64 caller-assigned ids follow the tags
+    int attr_cols = 0;
+    for (const int32_t* col : idx->d_attr) attr_cols += col ? 1 : 0;
+    h.reserved = (save_gid ? 1 : 0) | (attr_cols ? 2 : 0);
     bool ok = fwrite(&h, sizeof(h), 1, f) == 1;
     hipStream_t st = idx->eng->stream;
     std::vector<float> buf((size_t)kStageRows * idx->dim);
@@ -635,6 +682,22 @@ int rass_index_save(rass_index_t* idx, const char* path) {
         }
         ok = fwrite(gids.data(), 8, (size_t)idx->rows, f) == (size_t)idx->rows;
     }
+    if (ok && attr_cols) {
+        const int32_t n_cols = attr_cols;
+        ok = fwrite(&n_cols, 4, 1, f) == 1;
+        std::vector<int32_t> vals((size_t)idx->rows);
+        for (int32_t c = 0; ok && c < RASS_MAX_ATTRS; ++c) {
+            if (!idx->d_attr[c]) continue;
+            hipError_t e = hipSuccess;
+            if (idx->rows > 0) e = hipMemcpyAsync(vals.data(), idx->d_attr[c], (size_t)idx->rows * 4, hipMemcpyDeviceToHost, st);
+            if (e == hipSuccess) e = hipStreamSynchronize(st);
+            if (e != hipSuccess) {
+                fclose(f);
+                return fail(RASS_ERR_HIP, std::string("save: attribute read failed: ") + hipGetErrorString(e));
+            }
+            ok = fwrite(&c, 4, 1, f) == 1 && fwrite(vals.data(), 4, (size_t)idx->rows, f) == (size_t)idx->rows;
+        }
+    }
     // durable before the caller renames it into place (docstore.py's manifest scheme)
     ok = ok && fflush(f) == 0 && fsync(fileno(f)) == 0;
     ok = (fclose(f) == 0) && ok;
@@ -651,7 +714,7 @@ int rass_index_load(rass_engine_t* eng, const char* name, const char* path, rass
         fclose(f);
         return fail(RASS_ERR_IO, "not a rass index file");
     }
-    if (h.dim != eng->dim || (h.dtype != RASS_F32 && h.dtype != RASS_BF16) || h.rows < 0) {
+    if (h.dim != eng->dim || (h.dtype != RASS_F32 && h.dtype != RASS_BF16) || h.rows < 0 || (h.reserved & ~3) != 0) {
         fclose(f);
         return fail(RASS_ERR_INVALID, "index file does not match the engine (dim / dtype)");
     }
@@ -659,8 +722,16 @@ int rass_index_load(rass_engine_t* eng, const char* name, const char* path, rass
         const long body = ftell(f);
         int64_t file_len = -1;
         if (body >= 0 && fseek(f, 0, SEEK_END) == 0) file_len = (int64_t)ftell(f);
-        const int64_t need = (int64_t)sizeof(SaveHeader) + h.rows * ((int64_t)h.dim * 4 + 4 + (h.reserved == 1 ? 8 : 0));
-        if (body < 0 || h.rows > ((int64_t)1 << 40) || file_len < need || fseek(f, body, SEEK_SET) != 0) {
+        int64_t need = (int64_t)sizeof(SaveHeader) + h.rows * ((int64_t)h.dim * 4 + 4 + ((h.reserved & 1) ? 8 : 0));
+        bool bad = body < 0 || h.rows > ((int64_t)1 << 40) || file_len < need;
+        if (!bad && (h.reserved & 2)) {   // the attribute section's own count sizes the rest of it
+            int32_t n_cols = 0;
+            bad = file_len < need + 4 || fseek(f, (long)need, SEEK_SET) != 0 || fread(&n_cols, 4, 1, f) != 1 || n_cols < 1 ||
+                  n_cols > RASS_MAX_ATTRS;
+            need += 4 + (int64_t)n_cols * (4 + h.rows * 4);
+            bad = bad || file_len < need;
+        }
+        if (bad || fseek(f, body, SEEK_SET) != 0) {
             fclose(f);
             return fail(RASS_ERR_IO, "truncated index file (shorter than its header says)");
         }
@@ -722,7 +793,7 @@ int rass_index_load(rass_engine_t* eng, const char* name, const char* path, rass
             }
         }
     }
-    if (h.rows > 0 && h.reserved == 1) {
+    if (h.rows > 0 && (h.reserved & 1)) {
         std::vector<int64_t> gids((size_t)h.rows);
         hipError_t e = hipSuccess;
         if (fread(gids.data(), 8, (size_t)h.rows, f) != (size_t)h.rows) {
@@ -740,6 +811,32 @@ int rass_index_load(rass_engine_t* eng, const char* name, const char* path, rass
             fclose(f);
             (void)rass_index_drop(eng, name);
             return fail(RASS_ERR_HIP, std::string("load: id upload failed: ") + hipGetErrorString(e));
+        }
+    }
+    if (h.reserved & 2) {
+        int32_t n_cols = 0;
+        bool ok = fread(&n_cols, 4, 1, f) == 1 && n_cols >= 1 && n_cols <= RASS_MAX_ATTRS;
+        std::vector<int32_t> vals((size_t)h.rows);
+        int rc2 = RASS_OK;
+        for (int32_t i = 0; ok && rc2 == RASS_OK && i < n_cols; ++i) {
+            int32_t c = -1;
+            ok = fread(&c, 4, 1, f) == 1 && c >= 0 && c < RASS_MAX_ATTRS &&
+                 fread(vals.data(), 4, (size_t)h.rows, f) == (size_t)h.rows;
+            if (!ok) break;
+            std::lock_guard<std::mutex> lk(idx->mu);
+            std::lock_guard<std::mutex> elk(eng->mu);
+            rc2 = index_attr_ensure(idx, c);
+            if (rc2 == RASS_OK && h.rows > 0) {
+                hipError_t e = hipMemcpyAsync(idx->d_attr[c], vals.data(), (size_t)h.rows * 4, hipMemcpyHostToDevice, eng->stream);
+                if (e == hipSuccess) e = hipStreamSynchronize(eng->stream);
+                if (e != hipSuccess) rc2 = fail(RASS_ERR_HIP, std::string("load: attribute upload failed: ") + hipGetErrorString(e));
+            }
+        }
+        if (!ok || rc2 != RASS_OK) {
+            const std::string why = rass_last_error();
+            fclose(f);
+            (void)rass_index_drop(eng, name);
+            return ok ? fail(rc2, why) : fail(RASS_ERR_IO, "truncated index file (attribute columns)");
         }
     }
     fclose(f);
@@ -778,6 +875,8 @@ int rass_index_fill_synthetic(rass_index_t* idx, int64_t n, uint64_t seed, int64
     } else
     HIP_TRY(rass::launch_fill_synthetic_f32(idx->d_rows, idx->stride, idx->rows, n, idx->dim, seed, row_id_base, st));
     HIP_TRY(rass::launch_fill_i32(idx->d_tags + idx->rows, n, 0, st));
+    for (int32_t* col : idx->d_attr)
+        if (col) HIP_TRY(rass::launch_fill_i32(col + idx->rows, n, RASS_ATTR_MISSING, st));
     HIP_TRY(rass::launch_iota_i64(idx->d_gid + idx->rows, n, idx->rows.load(), st));
     rc = index_refresh_copies(idx, idx->rows, n, st);
     if (rc != RASS_OK) return rc;

@@ -21,9 +21,12 @@ struct CompactBlocks {
     unsigned short* b16 = nullptr; // the candidate copies of an fp32 index
     signed char* i8 = nullptr;
     float* scale = nullptr;
+    int32_t* attr[RASS_MAX_ATTRS] = {};   // the attribute columns the index has allocated
     int64_t *new_row = nullptr, *src_row = nullptr, *n_live = nullptr;
     void* ws = nullptr;
     ~CompactBlocks() {
+        for (int32_t* p : attr)
+            if (p) (void)hipFree(p);
         for (void* p : {main, (void*)tags, (void*)gid, (void*)b16, (void*)i8, (void*)scale, (void*)new_row, (void*)src_row,
                         (void*)n_live, ws})
             if (p) (void)hipFree(p);
@@ -76,6 +79,8 @@ int rass_index_compact(rass_index_t* idx, int64_t* new_row_of, int64_t map_capac
     if (e == hipSuccess && want_b16) e = dev_alloc(&nb.b16, (size_t)cap * idx->stride * 2);
     if (e == hipSuccess && want_i8) e = dev_alloc(&nb.i8, (size_t)cap * idx->stride_i8);
     if (e == hipSuccess && want_i8) e = dev_alloc(&nb.scale, (size_t)cap * sizeof(float));
+    for (int c = 0; e == hipSuccess && c < RASS_MAX_ATTRS; ++c)
+        if (idx->d_attr[c]) e = dev_alloc(&nb.attr[c], (size_t)cap * sizeof(int32_t));
     if (e == hipSuccess) e = dev_alloc(&nb.new_row, (size_t)rows * sizeof(int64_t));
     if (e == hipSuccess) e = dev_alloc(&nb.src_row, (size_t)rows * sizeof(int64_t));   // rows, not live: in bounds whatever the tags say
     if (e == hipSuccess) e = dev_alloc(&nb.n_live, sizeof(int64_t));
@@ -104,6 +109,12 @@ int rass_index_compact(rass_index_t* idx, int64_t* new_row_of, int64_t map_capac
     else
         HIP_TRY(rass::launch_compact_rows_tile16b(idx->d_rows_bf16, nb.main, idx->stride, nb.src_row, live, rows, st));
     HIP_TRY(rass::launch_gather_i32(idx->d_tags, nb.tags, nb.src_row, live, rows, st));
+    // the attribute columns travel with their rows; the capacity past them reads MISSING, as after a growth
+    for (int c = 0; c < RASS_MAX_ATTRS; ++c) {
+        if (!nb.attr[c]) continue;
+        HIP_TRY(rass::launch_gather_i32(idx->d_attr[c], nb.attr[c], nb.src_row, live, rows, st));
+        HIP_TRY(rass::launch_fill_i32(nb.attr[c] + live, cap - live, RASS_ATTR_MISSING, st));
+    }
     // the id a search reports: caller-assigned ids travel with their rows, plain ordinals are the new ordinals
     if (idx->has_gid.load()) HIP_TRY(rass::launch_gather_i64(idx->d_gid, nb.gid, nb.src_row, live, rows, st));
     else HIP_TRY(rass::launch_iota_i64(nb.gid, live, 0, st));
@@ -119,6 +130,7 @@ int rass_index_compact(rass_index_t* idx, int64_t* new_row_of, int64_t map_capac
     // construction).  Mode 3's certificate maxima are monotone upper bounds over every row ever quantised: still valid.
     auto swap_slabs = [&] {
         std::swap(idx->d_tags, nb.tags);
+        for (int c = 0; c < RASS_MAX_ATTRS; ++c) std::swap(idx->d_attr[c], nb.attr[c]);
         std::swap(idx->d_gid, nb.gid);
         std::swap(idx->d_rows_i8, nb.i8);
         std::swap(idx->d_row_scale, nb.scale);

@@ -12,6 +12,7 @@
 //   api_ivf.hip      IVF: the host-planned and the device-planned build on one build tail, persistence over one section
 //                    list, the probe and the batch on one fine scan, the delta, the host API (host_groups)
 //   api_allow.hip    the allow-list search (top-k within a per-query row bitmap), its bitmap builders and its plan
+//   api_attr.hip     the attribute columns of a flat index and the predicate builder that turns clauses over them into bitmaps
 //   api_mmr.hip      the diversified (MMR) search and the Gram matrices of row lists
 //   api_compact.hip  compaction of a flat index, its layout epoch, the stateless wrappers of compact.hip
 //
@@ -367,6 +368,9 @@ struct rass_index {
     // the counters [queries, certified, fallbacks]; allocated when the mode is first set
     unsigned* d_cert_stats = nullptr;
     unsigned long long* d_cert_counts = nullptr;
+    // attribute columns (api_attr.hip): column c is int32 [capacity], nullptr until its first rass_index_set_attr, which
+    // fills it with RASS_ATTR_MISSING; every path that moves a row (grow, compact, save / load) carries the allocated ones
+    int32_t* d_attr[RASS_MAX_ATTRS] = {};
     std::vector<uint8_t> host_deleted;  // tombstone bitmap mirror (host)
     // compactions that moved rows (rass_index_compact): a row ordinal is only meaningful together with this value.
     // Written under mu + eng->mu; the host search entry points read it around their launch groups
@@ -419,6 +423,7 @@ namespace host {
 int set_device(const rass_engine* eng);
 int index_reserve(rass_index* idx, int64_t need_rows);   // api.hip; the caller holds idx->mu and eng->mu
 void index_free_slabs(rass_index* idx);                  // every device array of the index, freed and nulled
+int index_attr_ensure(rass_index* idx, int col);         // api.hip; attribute column `col` allocated (all MISSING) if it was not; same locks
 int index_refresh_copies(rass_index* idx, int64_t first, int64_t n, hipStream_t st);   // the prefilter mode's candidate copies of rows [first, first + n)
 
 // ---- the tuning switches (api_scan.hip: the only place of the host layer that reads the environment)

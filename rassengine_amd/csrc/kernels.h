@@ -181,6 +181,29 @@ hipError_t launch_allow_store(const float* scores, const int64_t* rows, int nq, 
                               const int64_t* id_map, float* out_scores, int64_t* out_ids, float* after_s, int64_t* after_i,
                               hipStream_t stream);
 
+// ---- attribute predicates (attr.hip): clauses over int32 columns -> the bitmaps of one launch group of nq <= 32 queries.
+// A clause {query, lo, hi, negate} of column c holds for row r when v = col[c][r] is not INT32_MIN and lo <= v <= hi, inverted
+// under negate; a NULL column reads as INT32_MIN everywhere.  clauses[col_off[c] .. col_off[c + 1]) are column c's
+// (col_off[0] = 0).  Bit q of a live row (tags[r] != -1, r < n_rows) = all (mode_any = 0) or any (1) of q's clauses hold; a
+// query without a clause gets every live row under all, none under any.  Words [0, ceil(span_rows / 32)) of bitmap q at allow +
+// q * q_stride are written: combine 0 = replace, 1 = and, 2 = or with what they hold; positions in [n_rows, span_rows)
+// contribute 0 bits, so span_rows = 32 * words clears a replace / and target whole and span_rows = n_rows leaves an or
+// target's surplus alone.  span_rows >= n_rows.
+constexpr int kAttrCols = 8;   // = RASS_MAX_ATTRS
+struct AttrArgs {
+    const int32_t* tags = nullptr;
+    const int32_t* col[kAttrCols] = {};
+    const int4* clauses = nullptr;
+    int col_off[kAttrCols + 1] = {};
+    int64_t n_rows = 0, span_rows = 0;
+    uint32_t* allow = nullptr;
+    int64_t q_stride = 0;
+    int nq = 0, mode_any = 0, combine = 0;
+};
+hipError_t launch_attr_clauses(const AttrArgs& a, hipStream_t stream);
+// dst[i] = dst[i] & src[i] (op 1), | src[i] (2) or & ~src[i] (3) for i < words: two bitmaps of equal length, dst != src.
+hipError_t launch_allow_combine(uint32_t* dst, const uint32_t* src, int64_t words, int op, hipStream_t stream);
+
 // ---- diversified (MMR) search (mmr.hip): the Gram matrices of short row lists and the greedy selection
 constexpr int kMmrMaxFetch = 128;   // = RASS_MAX_MMR_FETCH: rows per list, candidates per query (two per lane of one wave)
 // out[l][i][j] = the fp32 dot product of slab rows rows[l][i] and rows[l][j] (whole rows: `stride` columns, the padding is

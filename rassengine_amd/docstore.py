@@ -13,12 +13,17 @@ One ``IndexState`` per index name; a process-global registry makes
 """
 from __future__ import annotations
 
+import datetime as _dt
 import json
+import logging
 import os
+import re
 import threading
-from typing import Any, Dict, List, Optional, Tuple
+from typing import Any, Callable, Dict, List, Optional, Tuple
 
 import numpy as np
+
+logger = logging.getLogger("rassengine_amd")
 
 PATIENT_NONE = 0  # tag of rows without a patientId
 TAG_PATIENT_MASK = 0x00FFFFFF
@@ -61,6 +66,169 @@ class PatientDictionary:
         return len(self._name) - 1
 
 
+ATTR_MISSING = -(1 << 31)     # RASS_ATTR_MISSING: the row has no value in the column
+ATTR_MIN, ATTR_MAX = ATTR_MISSING + 1, (1 << 31) - 1
+MAX_ATTRS = 8                 # RASS_MAX_ATTRS
+_EPOCH = _dt.datetime(1970, 1, 1, tzinfo=_dt.timezone.utc)
+_DATE_ONLY = re.compile(r"^\d{4}-\d{2}-\d{2}$")
+_DATE_MATH = re.compile(r"^now(?:([+-])(\d+)([dwMy]))?$")
+
+
+def utc_now() -> _dt.datetime:
+    """The clock behind ``now`` in a date range (``AttrSchema.clock`` defaults to it; tests inject their own)."""
+    return _dt.datetime.now(_dt.timezone.utc)
+
+
+def date_days(value: Any) -> Optional[int]:
+    """A date as days since 1970-01-01 UTC: ``YYYY-MM-DD``, an ISO-8601 date-time with or without an offset (none = UTC;
+    floored to its UTC day) or integer epoch milliseconds.  None when the value is none of these."""
+    if isinstance(value, bool) or value is None:
+        return None
+    if isinstance(value, (int, np.integer)):
+        days = int(value) // 86_400_000
+        return days if ATTR_MIN <= days <= ATTR_MAX else None
+    if not isinstance(value, str):
+        return None
+    text = value.strip()
+    try:
+        if _DATE_ONLY.match(text):
+            return _dt.date.fromisoformat(text).toordinal() - _EPOCH.toordinal()
+        if text[-1:] in ("Z", "z"):
+            text = text[:-1] + "+00:00"
+        when = _dt.datetime.fromisoformat(text)
+    except ValueError:
+        return None
+    if when.tzinfo is None:
+        when = when.replace(tzinfo=_dt.timezone.utc)
+    return (when - _EPOCH) // _dt.timedelta(days=1)
+
+
+def date_bound_days(value: Any, now: _dt.datetime) -> Optional[int]:
+    """A bound of a ``range`` on a date field: what ``date_days`` takes, plus ``now`` and ``now±N(d|w|M|y)`` against the
+    given clock (months and years on the calendar, the day clamped to the month's length)."""
+    if isinstance(value, str):
+        m = _DATE_MATH.match(value.strip())
+        if m:
+            when = now.astimezone(_dt.timezone.utc)
+            if m.group(1):
+                n = int(m.group(2)) * (1 if m.group(1) == "+" else -1)
+                unit = m.group(3)
+                if unit in "dw":
+                    when = when + _dt.timedelta(days=n * (7 if unit == "w" else 1))
+                else:
+                    months = when.year * 12 + (when.month - 1) + n * (12 if unit == "y" else 1)
+                    year, month = divmod(months, 12)
+                    nxt = _dt.date(year + (month == 11), (month + 1) % 12 + 1, 1)
+                    last = (nxt - _dt.timedelta(days=1)).day
+                    when = when.replace(year=year, month=month + 1, day=min(when.day, last))
+            return (when - _EPOCH) // _dt.timedelta(days=1)
+    return date_days(value)
+
+
+class AttrSchema:
+    """The typed per-row fields an index keeps as int32 attribute columns: an ordered list of up to 8 ``(field, kind)``
+    pairs, column c = pair c.  ``keyword``: the value's dictionary code (>= 1; the dictionary grows as values arrive, like
+    ``PatientDictionary``); ``int``: the value itself, which must fit int32; ``date``: days since 1970-01-01 UTC
+    (``date_days``).  An absent, None or (keyword) empty value, and a date that cannot be parsed (logged once per field), is
+    missing.  An empty schema is falsy: no column is ever set."""
+
+    KINDS = ("keyword", "int", "date")
+
+    def __init__(self, fields=()):
+        self.fields: List[Tuple[str, str]] = [(str(f), str(k)) for f, k in fields]
+        if len(self.fields) > MAX_ATTRS:
+            raise ValueError(f"at most {MAX_ATTRS} attribute fields, got {len(self.fields)}")
+        names = [f for f, _ in self.fields]
+        if len(set(names)) != len(names) or any(not f for f in names):
+            raise ValueError(f"attribute field names must be distinct and non-empty: {names}")
+        for f, k in self.fields:
+            if k not in self.KINDS:
+                raise ValueError(f"attribute field {f!r}: kind must be one of {self.KINDS}, not {k!r}")
+            if f in ("patientId", "doc_type"):
+                raise ValueError(f"{f!r} lives in the row tag, not in an attribute column")
+        self.dicts: Dict[str, PatientDictionary] = {f: PatientDictionary(max_code=ATTR_MAX) for f, k in self.fields if k == "keyword"}
+        self.clock: Callable[[], _dt.datetime] = utc_now
+        self._warned: set = set()
+
+    @classmethod
+    def parse(cls, spec: Optional[str]) -> "AttrSchema":
+        """``"resourceType:keyword,file_type:keyword,chunkDate:date"`` (``config.RASS_ATTR_FIELDS``); empty = no schema."""
+        pairs = []
+        for item in (spec or "").split(","):
+            if item.strip():
+                field, sep, kind = item.strip().partition(":")
+                if not sep:
+                    raise ValueError(f"attribute field {item!r}: expected field:kind")
+                pairs.append((field.strip(), kind.strip().lower()))
+        return cls(pairs)
+
+    def __bool__(self) -> bool:
+        return bool(self.fields)
+
+    def __len__(self) -> int:
+        return len(self.fields)
+
+    def __eq__(self, other) -> bool:
+        return isinstance(other, AttrSchema) and self.fields == other.fields
+
+    def column(self, field: str) -> Optional[Tuple[int, str]]:
+        """(column, kind) of a schema field, None for a field the schema does not hold."""
+        for c, (f, k) in enumerate(self.fields):
+            if f == field:
+                return c, k
+        return None
+
+    def encode_value(self, col: int, value: Any) -> int:
+        """The int32 stored for ``value`` in column ``col`` (a new keyword value gets a code)."""
+        field, kind = self.fields[col]
+        if value is None:
+            return ATTR_MISSING
+        if kind == "keyword":
+            code = self.dicts[field].encode(value)
+            return code if code != PATIENT_NONE else ATTR_MISSING
+        if kind == "int":
+            if isinstance(value, bool) or not isinstance(value, (int, np.integer)):
+                raise ValueError(f"attribute field {field!r} is an int column, got {value!r}")
+            if not ATTR_MIN <= int(value) <= ATTR_MAX:
+                raise OverflowError(f"attribute field {field!r}: {value} does not fit an int32 column")
+            return int(value)
+        days = date_days(value)
+        if days is None or not ATTR_MIN <= days <= ATTR_MAX:
+            if field not in self._warned:
+                self._warned.add(field)
+                logger.warning(f"attribute field {field!r}: {value!r} is not a date (YYYY-MM-DD, ISO-8601 or epoch "
+                               "milliseconds); stored as missing (logged once per field)")
+            return ATTR_MISSING
+        return days
+
+    def encode_docs(self, docs: List[dict]) -> np.ndarray:
+        """int32 [len(fields), len(docs)]: row c is column c of the docs."""
+        out = np.full((len(self.fields), len(docs)), ATTR_MISSING, dtype=np.int32)
+        for c, (field, _) in enumerate(self.fields):
+            for i, d in enumerate(docs):
+                if d is not None:
+                    out[c, i] = self.encode_value(c, d.get(field))
+        return out
+
+    def to_meta(self) -> dict:
+        return {"fields": [[f, k] for f, k in self.fields], "keywords": {f: d.names() for f, d in self.dicts.items()}}
+
+    @classmethod
+    def from_meta(cls, meta: Optional[dict]) -> "AttrSchema":
+        if not meta:
+            return cls()
+        schema = cls([(f, k) for f, k in meta.get("fields", [])])
+        schema.absorb(meta)
+        return schema
+
+    def absorb(self, meta: Optional[dict]) -> None:
+        """The keyword dictionaries of a manifest or a delta segment, in their stored order (codes are positions)."""
+        for field, names in ((meta or {}).get("keywords") or {}).items():
+            if field in self.dicts:
+                for name in names:
+                    self.dicts[field].encode(name)
+
+
 def compose_tag(patient_code: int, doctype_code: int) -> int:
     return (int(patient_code) & TAG_PATIENT_MASK) | (int(doctype_code) << TAG_DOCTYPE_SHIFT)
 
@@ -77,6 +245,8 @@ class IndexState:
         self.structured: Dict[str, dict] = {}    # structured docs carry no embedding (app/main.py:1222-1240)
         self.patients = PatientDictionary()
         self.doc_types = PatientDictionary(max_code=0x7F)
+        from . import config
+        self.attrs = AttrSchema.parse(config.RASS_ATTR_FIELDS)   # empty (falsy) = no attribute columns
         self.batcher = None                      # QueryBatcher, created on first async search
         self.generation = 0                      # bumped by every save()
         # incremental persistence (save_delta): what changed since the last save() / save_delta()
@@ -162,6 +332,8 @@ class IndexState:
                     "rows": int(self.index.rows), "live": int(self.index.count),
                     "row_doc": self.row_doc, "structured": self.structured,
                     "patients": self.patients.names(), "doc_types": self.doc_types.names()}
+            if self.attrs:          # the schema and its keyword dictionaries; the values are columns of the vector file
+                meta["attrs"] = self.attrs.to_meta()
             tmp_meta = prefix + ".meta.json.tmp"
             with open(tmp_meta, "w", encoding="utf-8") as f:
                 json.dump(meta, f)
@@ -208,6 +380,9 @@ class IndexState:
                     "structured": {k: self.structured[k] for k in sorted(self._structured_dirty) if k in self.structured},
                     "patients": self.patients.names(), "doc_types": self.doc_types.names(),
                     "rows_after": rows_now, "live_after": int(self.index.count)}
+            if self.attrs and hasattr(self.index, "get_attr"):   # the appended rows' column values, read back like the rows
+                head["attrs"] = dict(self.attrs.to_meta(), values=[
+                    self.index.get_attr(c, self._ckpt_rows, n_new).tolist() for c in range(len(self.attrs))])
             d, base = os.path.dirname(prefix) or ".", os.path.basename(prefix)
             seg = f"{base}.g{self.generation:06d}.d{self._delta_seq + 1:06d}.delta"
             tmp = os.path.join(d, seg + ".tmp")
@@ -283,6 +458,14 @@ class IndexState:
                 first = self.index.add(vecs, tags=tags, normalize=False)     # the stored bits, not re-normalised
                 if int(first) != int(head["first_row"]):
                     raise ValueError(f"{seg}: rows landed at {first}, expected {head['first_row']}")
+            seg_attrs = head.get("attrs")
+            if seg_attrs and self.attrs:
+                if [list(p) for p in self.attrs.fields] != [list(p) for p in seg_attrs.get("fields", [])]:
+                    raise ValueError(f"{seg}: the segment's attribute schema is not the snapshot's")
+                self.attrs.absorb(seg_attrs)
+                for c, vals in enumerate(seg_attrs.get("values", [])):
+                    if n:
+                        self.index.set_attr(c, int(head["first_row"]), np.asarray(vals, dtype=np.int32))
             for r in head["dead"]:
                 self.index.delete(int(r))
                 doc = self.row_doc[int(r)]
@@ -362,6 +545,11 @@ class IndexState:
         for t in meta.get("doc_types", []):
             st.doc_types.encode(t)
         st.doc_row = {d["doc_id"]: r for r, d in enumerate(st.row_doc) if d is not None}
+        loaded = AttrSchema.from_meta(meta.get("attrs"))     # a manifest without the key: no schema
+        if loaded != st.attrs:
+            logger.warning(f"{prefix}: the saved attribute schema {loaded.fields} differs from the configured one "
+                           f"{st.attrs.fields}; keeping the saved one (it describes the columns of the file)")
+        st.attrs = loaded
         st._ckpt_rows = rows
         st._replay_deltas(prefix)
         return st

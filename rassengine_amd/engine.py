@@ -562,16 +562,18 @@ class FlatIndex:
 
     ALLOW_SLACK_WORDS = 64       # words a new bitmap gets beyond ceil(rows / 32): rows appended meanwhile (2 048 of them) still fit
 
-    def _build_bitmap(self, fn: str, call):
+    def _build_bitmap(self, fn: str, call, n_bitmaps: Optional[int] = None, words: Optional[int] = None):
         """A device bitmap sized for the index as it is NOW plus slack, filled by ``call(tensor)`` (a native builder).  The
         index may grow between reading ``rows`` here and the builder's own check: the slack absorbs that, and a builder that
         still finds the bitmap too short is given a fresh, longer one.  Surplus words allow nothing."""
         import torch
         for _ in range(4):
-            words = self.allow_words + self.ALLOW_SLACK_WORDS
-            out = torch.empty((words,), dtype=torch.int32, device=f"cuda:{self.engine.device}")
+            fixed, words = words, (self.allow_words + self.ALLOW_SLACK_WORDS if words is None else int(words))
+            out = torch.empty((words,) if n_bitmaps is None else (n_bitmaps, words), dtype=torch.int32,
+                              device=f"cuda:{self.engine.device}")
             rc = call(out)
-            if rc < 0 and self.allow_words > words:
+            if rc < 0 and self.allow_words > words and fixed is None:
+                words = None
                 continue            # the index outgrew the slack meanwhile
             N.check(fn, rc)
             return out
@@ -585,7 +587,7 @@ class FlatIndex:
         return self._build_bitmap("rass_index_allow_from_rows", lambda out: self._L.rass_index_allow_from_rows(
             self._h, _np_ptr(r), r.shape[0], ctypes.c_void_p(out.data_ptr()), out.shape[0]))
 
-    def allow_from_tag_values(self, values, mask: int):
+    def allow_from_tag_values(self, values, mask: int, words: Optional[int] = None):
         """A device bitmap allowing every live row whose ``(tag & mask)`` is one of ``values`` (``rass_index_allow_from_tag_values``):
         OpenSearch's ``terms`` filter.  ``mask``: ``RASS_TAG_PATIENT_MASK`` (values = patient codes), ``RASS_TAG_DOCTYPE_MASK``
         (values = codes << 24) or both.  Rows appended after the call are not allowed by it."""
@@ -594,7 +596,94 @@ class FlatIndex:
         if not 0 <= mask <= 0x7FFFFFFF:
             raise ValueError(f"mask must be within 0x7fffffff, got {mask:#x}")
         return self._build_bitmap("rass_index_allow_from_tag_values", lambda out: self._L.rass_index_allow_from_tag_values(
-            self._h, _np_ptr(v), v.shape[0], mask, ctypes.c_void_p(out.data_ptr()), out.shape[0]))
+            self._h, _np_ptr(v), v.shape[0], mask, ctypes.c_void_p(out.data_ptr()), out.shape[0]), words=words)
+
+    # ---- attribute columns and the predicates over them
+    ATTR_MISSING = N.RASS_ATTR_MISSING
+    ATTR_MODES = {"all": N.RASS_ATTR_ALL, "any": N.RASS_ATTR_ANY}
+    ATTR_COMBINES = {"replace": N.RASS_ATTR_REPLACE, "and": N.RASS_ATTR_AND, "or": N.RASS_ATTR_OR}
+
+    def set_attr(self, col: int, first_row: int, values) -> None:
+        """Store int32 ``values`` in attribute column ``col`` (0 .. 7) for rows [first_row, first_row + len(values)), which
+        must exist (``rass_index_set_attr``).  The column is allocated, all ``ATTR_MISSING``, on its first use; storing
+        ``ATTR_MISSING`` un-sets a value.  Rows appended by ``add`` read missing until they are set here."""
+        v = np.asarray(values)
+        if v.dtype.kind not in "iu" or v.ndim != 1:
+            raise ValueError(f"values must be a 1-d integer array, got {v.dtype} {v.shape}")
+        if v.size and (int(v.min()) < -(1 << 31) or int(v.max()) > (1 << 31) - 1):
+            raise OverflowError("attribute values must fit int32")
+        v = np.ascontiguousarray(v, dtype=np.int32)
+        N.check("rass_index_set_attr", self._L.rass_index_set_attr(self._h, int(col), int(first_row), v.shape[0], _np_ptr(v)))
+
+    def get_attr(self, col: int, first_row: int, n: int) -> np.ndarray:
+        """Column ``col`` of rows [first_row, first_row + n) as int32 [n]; a column never set reads all ``ATTR_MISSING``."""
+        out = np.empty(int(n), dtype=np.int32)
+        N.check("rass_index_get_attr", self._L.rass_index_get_attr(self._h, int(col), int(first_row), int(n), _np_ptr(out)))
+        return out
+
+    @property
+    def attr_mask(self) -> int:
+        """Bit c set iff attribute column c is allocated (``rass_index_attr_mask``)."""
+        return int(N.check("rass_index_attr_mask", self._L.rass_index_attr_mask(self._h)))
+
+    def device_attr_ptr(self, col: int) -> int:
+        return int(self._L.rass_index_device_attr(self._h, int(col)) or 0)
+
+    def allow_from_attr_clauses(self, clauses, nq: int = 1, shared: bool = False, mode: str = "all", combine: str = "replace",
+                                allow=None):
+        """Device bitmaps from predicates over the attribute columns (``rass_index_allow_from_attr_clauses``).  ``clauses``:
+        int32 [n, 5] rows ``(query, col, lo, hi, negate)``; a clause holds where the row's value v in ``col`` is not missing
+        and lo <= v <= hi, inverted under ``negate`` (a missing value then passes).  ``mode`` "all": query q allows a live
+        row iff all of its clauses hold (none: every live row); "any": iff one does (none: no row).  At most 64 clauses per
+        query per call.  ``shared``: ONE bitmap for every query (the clauses name query 0).  With ``allow=None`` a new
+        tensor is returned — int32 CUDA [words] when shared, else [nq, words], words = ``allow_words`` plus slack — and
+        ``combine`` must be "replace"; otherwise ``allow`` (such a tensor, e.g. from ``allow_from_tag_values``) is refined in
+        place with ``combine`` "replace" / "and" / "or" and returned.  The result is what ``search_allowed`` /
+        ``search_allowed_device`` take; it names rows of one ``layout_epoch``."""
+        import torch
+        c = np.ascontiguousarray(np.asarray(clauses, dtype=np.int64).reshape(-1, 5))
+        if c.size and (int(c.min()) < -(1 << 31) or int(c.max()) > (1 << 31) - 1):
+            raise OverflowError("clause fields must fit int32")
+        c = np.ascontiguousarray(c, dtype=np.int32)
+        nq, n_bitmaps = int(nq), 1 if shared else int(nq)
+        try:
+            mode_c, comb_c = self.ATTR_MODES[mode], self.ATTR_COMBINES[combine]
+        except KeyError:
+            raise ValueError(f"mode must be all / any and combine replace / and / or, not {mode!r} / {combine!r}") from None
+        fn = "rass_index_allow_from_attr_clauses"
+
+        def call(out) -> int:
+            words = int(out.shape[-1])
+            torch.cuda.current_stream(out.device).synchronize()     # the engine works on its own stream
+            return self._L.rass_index_allow_from_attr_clauses(self._h, _np_ptr(c), c.shape[0], nq, n_bitmaps, mode_c, comb_c,
+                                                              ctypes.c_void_p(out.data_ptr()), words)
+        if allow is None:
+            if comb_c != N.RASS_ATTR_REPLACE:
+                raise ValueError("combine 'and' / 'or' needs the bitmap to refine (allow=...)")
+            return self._build_bitmap(fn, call, None if shared else n_bitmaps)
+        if not allow.is_cuda or allow.dtype != torch.int32 or not allow.is_contiguous():
+            raise ValueError("a device bitmap must be a contiguous int32 CUDA tensor")
+        if tuple(allow.shape[:-1]) not in (((), (1,)) if shared else ((n_bitmaps,),) + (((),) if n_bitmaps == 1 else ())):
+            raise ValueError(f"allow has shape {tuple(allow.shape)} for {n_bitmaps} bitmap(s)")
+        N.check(fn, call(allow))
+        return allow
+
+    def allow_combine(self, dst, src, op: str):
+        """``dst`` = ``dst`` and / or / andnot ``src`` word for word, in place (``rass_index_allow_combine``): two device
+        bitmaps of one shape, as the builders return them.  Returns ``dst``."""
+        import torch
+        ops = {"and": N.RASS_ATTR_AND, "or": N.RASS_ATTR_OR, "andnot": N.RASS_ATTR_ANDNOT}
+        if op not in ops:
+            raise ValueError(f"op must be and / or / andnot, not {op!r}")
+        for t in (dst, src):
+            if not t.is_cuda or t.dtype != torch.int32 or not t.is_contiguous():
+                raise ValueError("a device bitmap must be a contiguous int32 CUDA tensor")
+        if tuple(dst.shape) != tuple(src.shape) or dst.data_ptr() == src.data_ptr():
+            raise ValueError(f"dst {tuple(dst.shape)} and src {tuple(src.shape)} must be two bitmaps of one shape")
+        torch.cuda.current_stream(dst.device).synchronize()     # the engine works on its own stream
+        N.check("rass_index_allow_combine", self._L.rass_index_allow_combine(
+            self._h, ctypes.c_void_p(dst.data_ptr()), ctypes.c_void_p(src.data_ptr()), int(dst.numel()), ops[op]))
+        return dst
 
     def allow_plan(self, allow, nq: int) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
         """The work list an allowed search of one launch group of ``nq`` <= 32 queries walks (``rass_index_allow_plan``), for

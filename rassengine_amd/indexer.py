@@ -375,6 +375,53 @@ class HipIndexer:
                 return hits
         raise RuntimeError(f"{self.index_name}: the index was compacted during every one of {LAYOUT_ATTEMPTS} searches")
 
+    def semantic_search_filtered(self, query_emb: np.ndarray, k: int = TOP_K, where: Optional[Any] = None,
+                                 filter_clause: Optional[Dict] = None, patient_id: Optional[str] = None
+                                 ) -> List[Tuple[Dict, float]]:
+        """The k-NN clause under an OpenSearch ``filter``: ``where`` is a clause (or a list of them, ANDed) of ``term``,
+        ``terms``, ``range`` (``gte`` / ``gt`` / ``lte`` / ``lt``), ``exists`` and ``bool`` (``must`` / ``filter`` = and,
+        ``should`` = at least one, ``must_not``), nested freely, over ``patientId``, ``doc_type`` and the attribute fields of
+        the index (``config.RASS_ATTR_FIELDS``: keyword, int and date columns stored by ``add_documents``).  On a date field
+        the bounds are ``YYYY-MM-DD``, ISO-8601 date-times, epoch milliseconds, ``now`` or ``now-N(d|w|M|y)``, compared as
+        UTC days (``gt`` / ``lt``: the next / previous day).  A keyword value that was never indexed matches nothing; a
+        ``must_not`` passes the chunks that lack the field.  An unknown field or an unsupported clause (``match``, ...)
+        raises ``ValueError`` naming it.  The filter is compiled into a few bitmap-builder calls (``attrfilter``), evaluated
+        on the GPU over the columns, and the scan reads only the 32-row tiles with an allowed chunk
+        (``FlatIndex.search_allowed``): every allowed chunk gets its exact cosine.  ``filter_clause`` / ``patient_id`` as in
+        ``semantic_search``, intersected with ``where``.  ``where=None`` is ``semantic_search`` that raises.  Returns
+        ``[(doc_dict, float(score))]`` best first in ``semantic_search``'s score units.  Errors raise (no counterpart in the
+        reference)."""
+        if _empty(query_emb):
+            return []
+        if where is None:
+            return self._knn(query_emb, k, filter_clause, patient_id, boost=1.0)
+        st: Optional[IndexState] = REGISTRY.get(self.index_name, create=False)
+        if st is None:
+            return []
+        prep = self._prepare(st, query_emb, k, filter_clause, patient_id, None)
+        if prep is None:
+            return []
+        q, k_eff, (fval, fmask) = prep
+        flt = dict(q_filter=np.array([fval], dtype=np.int32), q_filter_mask=np.array([fmask], dtype=np.int32)) if fmask else {}
+        if not hasattr(st.index, "search_allowed") or not hasattr(st.index, "allow_from_attr_clauses"):
+            raise NotImplementedError(f"{self.index_name}: {type(st.index).__name__} has no filtered search "
+                                      "(IVF-backed and sharded indices cannot restrict by a bitmap; use a flat fp32 index)")
+        from .attrfilter import compile_filter, run_plan
+        for _ in range(LAYOUT_ATTEMPTS):    # the bitmap and the ids belong to ONE layout of the index, as in semantic_search_within
+            layout = _layout_epoch(st.index)
+            # under the state's lock: the dictionaries are read as one, and no row sits between its append and its column
+            # values (add_documents holds the lock across both), where a negated clause would pass it as "missing"
+            with st.lock:
+                if _layout_epoch(st.index) != layout:
+                    continue
+                plan = compile_filter(where, st.attrs, st.patients, st.doc_types)
+                allow = run_plan(st.index, plan)
+            scores, ids = st.index.search_allowed(q, k_eff, allow, **flt)
+            hits = self._hits(st, scores[0], ids[0], 1.0, None, layout)
+            if hits is not None:
+                return hits
+        raise RuntimeError(f"{self.index_name}: the index was compacted during every one of {LAYOUT_ATTEMPTS} searches")
+
     def knn_scores(self, query_emb: np.ndarray, k: int = TOP_K, boost: float = 1.0,
                    filter_clause: Optional[Dict] = None, patient_id: Optional[str] = None,
                    doc_type: Optional[str] = None) -> List[Tuple[Dict, float]]:
@@ -611,6 +658,8 @@ def add_documents(index_name: str, docs: List[Dict], embeddings: Optional[np.nda
             raise ValueError(f"embeddings {emb.shape} do not match {len(docs)} docs")
     with st.lock:
         tags = np.array([st.tag_of(d) for d in docs], dtype=np.int32)
+        # the attribute columns of the new rows; encoded before the append, so a value that does not fit changes nothing
+        cols = st.attrs.encode_docs(docs) if st.attrs and hasattr(st.index, "set_attr") else None
         # duplicates inside one batch: the last one wins, as with sequential bulk index ops
         last = {}
         for i, d in enumerate(docs):
@@ -620,6 +669,9 @@ def add_documents(index_name: str, docs: List[Dict], embeddings: Optional[np.nda
         else:
             first = st.index.add(emb, tags=tags, normalize=True)      # raises -> nothing was changed
         rows = list(range(first, first + len(docs)))
+        if cols is not None and len(docs):      # right after the append, before the rows they supersede are tombstoned
+            for c in range(cols.shape[0]):
+                st.index.set_attr(c, first, cols[c])
         for d in docs:
             old = st.doc_row.pop(d.get("doc_id"), None)
             if old is not None:
