@@ -79,6 +79,8 @@ typedef enum rass_dtype {
 #define RASS_ATTR_AND 1               /*          ... is ANDed into what the bitmap holds */
 #define RASS_ATTR_OR 2                /*          ... is ORed into it */
 #define RASS_ATTR_ANDNOT 3            /* rass_index_allow_combine only: dst & ~src */
+#define RASS_KEY_NONE (-1)            /* key column: this row is in no group (every negative key reads so) */
+#define RASS_MAX_KEY_EDGES 4097       /* rass_index_keys_from_attr_edges: RASS_MAX_K_MULTIPASS buckets */
 #define RASS_QFILTER_NONE (-1)
 
 typedef struct rass_engine rass_engine_t;
@@ -361,8 +363,9 @@ int rass_index_search_grouped_device(rass_index_t* idx, const float* d_queries, 
  * list); 0 <= nq <= RASS_MAX_DEVICE_BATCH.  Outside those, n_bitmaps neither 1 nor nq, or words_per_bitmap too small:
  * RASS_ERR_INVALID.  fp32 indices with dim <= 1024; a bf16 index or a wide-row index answers RASS_ERR_UNSUPPORTED.  The
  * prefilter mode of the index is ignored: an allowed search always runs the exact fp32 scan.  IVF, cross-index batches
- * (rass_index_search_multi), the sharded multi-GPU front, the 64-query pair kernel, and the range and grouped searches have
- * no allow-list form.
+ * (rass_index_search_multi), the sharded multi-GPU front, the 64-query pair kernel and the range search have no allow-list
+ * form; the grouped search and the aggregation take a bitmap in their key-column forms (rass_index_search_grouped_keys,
+ * rass_index_aggregate_keys), which stream every tile.
  * A bitmap names row ordinals of ONE layout of the index: build it and search under one layout epoch
  * (rass_index_layout_epoch).  Thread-safety and layout epochs as rass_index_search_ex. */
 int rass_index_search_allowed(rass_index_t* idx, const float* queries, int nq, int k,
@@ -457,8 +460,8 @@ int rass_index_allow_combine(rass_index_t* idx, uint32_t* d_dst, const uint32_t*
  * the answer: RASS_ERR_INVALID, named in rass_last_error(), and the outputs are unspecified; a row below the threshold never
  * causes that.  Any nq (scanned in groups of RASS_MAX_QBATCH).  fp32 indices of every dim the engine takes, wide rows
  * included; a bf16 index answers RASS_ERR_UNSUPPORTED.  The prefilter mode of the index is ignored: a candidate scan cannot
- * bound a count.  IVF, cross-index batches, the sharded multi-GPU front, the 64-query pair kernel and the allow list have no
- * aggregate form.  Thread-safety and layout epochs as rass_index_search_grouped. */
+ * bound a count.  IVF, cross-index batches, the sharded multi-GPU front and the 64-query pair kernel have no aggregate form;
+ * a bitmap restricts rass_index_aggregate_keys.  Thread-safety and layout epochs as rass_index_search_grouped. */
 int rass_index_aggregate(rass_index_t* idx, const float* queries, int nq, const float* min_score, int size,
                          int32_t group_mask, int32_t n_groups,
                          const int32_t* q_filter, const int32_t* q_filter_mask,
@@ -473,6 +476,68 @@ int rass_index_aggregate_device(rass_index_t* idx, const float* d_queries, int n
                                 const int32_t* d_q_filter, const int32_t* d_q_filter_mask,
                                 int64_t id_base, int32_t* d_out_groups, int64_t* d_out_counts, float* d_out_scores,
                                 int64_t* d_out_ids, int64_t* d_n_buckets, int64_t* d_total_hits, int32_t* d_status);
+
+/* KEY COLUMNS: the group of a row from any attribute column, or from the caller.  A key column is int32[n_keys] in DEVICE
+ * memory, owned by the caller as a bitmap is: key g with 0 <= g < n_groups places row r in group g; RASS_KEY_NONE, or any
+ * negative key, means the row belongs to NO group — it is neither a match nor a hit and is left out of every figure; a key
+ * >= n_groups on a matching row raises the status word exactly as an out-of-range tag key does.  A key column names rows of
+ * ONE layout epoch, as a bitmap does.
+ * The builders write d_keys[0 .. n_keys), n_keys >= the index's rows at the call (else RASS_ERR_INVALID and d_keys is left
+ * untouched); entries [rows, n_keys) are RASS_KEY_NONE.  They are stream-ordered on the engine's stream and do not read the
+ * tags: the scan skips tombstones itself.  col outside 0 .. RASS_MAX_ATTRS - 1: RASS_ERR_INVALID; every dtype that takes
+ * columns takes the builders.  missing_key >= -1 is the key of a row whose value is RASS_ATTR_MISSING (every row of a column
+ * that was never set).
+ * _keys_from_attr: key = v - base, computed without overflow; a result outside [0, INT32_MAX] becomes RASS_KEY_NONE.  For a
+ *   keyword column base = 0, missing_key = 0 reproduces the tag convention (codes from 1, 0 = none).
+ * _keys_from_attr_edges: `edges` is a HOST array (reusable on return: the call synchronises), strictly ascending,
+ *   2 <= n_edges <= RASS_MAX_KEY_EDGES, else RASS_ERR_INVALID; key j means edges[j] <= v < edges[j + 1]; a value below the
+ *   first edge or at or above the last becomes RASS_KEY_NONE.  A histogram's buckets, a calendar's months.
+ * _keys_from_tag: key = (tag & mask) >> ctz(mask) of a live row, RASS_KEY_NONE for a tombstone: the group of the tag-keyed
+ *   calls as a key column, so that they can run within a bitmap.  mask: non-zero, within 0x7fffffff.
+ * _attr_minmax: min, max and count of the present values of column col over the LIVE rows, by one small reduction; it
+ *   synchronises.  *out_n_present == 0 (a column never set, an empty index) leaves *out_min / *out_max unspecified. */
+int rass_index_keys_from_attr(rass_index_t* idx, int col, int32_t base, int32_t missing_key, int32_t* d_keys, int64_t n_keys);
+int rass_index_keys_from_attr_edges(rass_index_t* idx, int col, const int32_t* edges, int n_edges, int32_t missing_key,
+                                    int32_t* d_keys, int64_t n_keys);
+int rass_index_keys_from_tag(rass_index_t* idx, int32_t mask, int32_t* d_keys, int64_t n_keys);
+int rass_index_attr_minmax(rass_index_t* idx, int col, int32_t* out_min, int32_t* out_max, int64_t* out_n_present);
+/* rass_index_search_grouped and rass_index_aggregate with the group of a row taken from a key column, optionally within a
+ * row bitmap: "the best chunk per source document", "hits per condition code", "hits per month under a date range".  The tag
+ * is still read for tombstones and for q_filter / q_filter_mask.  d_keys and d_allow are DEVICE memory in the host variants
+ * too: a key column is 4 bytes per row and is built where it is used; the caller orders its own writes to them before the
+ * call.  n_keys >= the index's rows at the call, else RASS_ERR_INVALID.  d_allow may be NULL (no restriction); otherwise it is
+ * uint32[n_bitmaps][words_per_bitmap] as rass_index_search_allowed takes it, n_bitmaps 1 (shared) or nq, words_per_bitmap >=
+ * ceil(rows / 32), else RASS_ERR_INVALID; a row then also needs its bit.  A bitmap on a wide-row index (dim > 1024) answers
+ * RASS_ERR_UNSUPPORTED; keys alone run on every dim.  With a bitmap the scan still streams EVERY tile of the slab — only the
+ * emission is restricted; a plan-driven walk over the tiles with a bit set, as the allow-list search has, is not built.
+ * Everything else — the bounds on k / size and n_groups, padding values, result order, the status word and RASS_ERR_INVALID
+ * for a key >= n_groups, the engine-owned table block, fp32 indices only, one layout per answer — is exactly that of the
+ * tag-keyed calls, and scores are the flat scan's, bit for bit.  out_group_total and out_total_hits / out_n_buckets count
+ * only rows that have a group. */
+int rass_index_search_grouped_keys(rass_index_t* idx, const float* queries, int nq, int k,
+                                   const int32_t* d_keys, int64_t n_keys, int32_t n_groups,
+                                   const uint32_t* d_allow, int n_bitmaps, int64_t words_per_bitmap,
+                                   const int32_t* q_filter, const int32_t* q_filter_mask,
+                                   float* out_scores, int64_t* out_ids, int32_t* out_groups,
+                                   int64_t* out_group_total);
+int rass_index_search_grouped_keys_device(rass_index_t* idx, const float* d_queries, int nq, int k,
+                                          const int32_t* d_keys, int64_t n_keys, int32_t n_groups,
+                                          const uint32_t* d_allow, int n_bitmaps, int64_t words_per_bitmap,
+                                          const int32_t* d_q_filter, const int32_t* d_q_filter_mask,
+                                          int64_t id_base, float* d_out_scores, int64_t* d_out_ids,
+                                          int32_t* d_out_groups, int64_t* d_group_total, int32_t* d_status);
+int rass_index_aggregate_keys(rass_index_t* idx, const float* queries, int nq, const float* min_score, int size,
+                              const int32_t* d_keys, int64_t n_keys, int32_t n_groups,
+                              const uint32_t* d_allow, int n_bitmaps, int64_t words_per_bitmap,
+                              const int32_t* q_filter, const int32_t* q_filter_mask,
+                              int32_t* out_groups, int64_t* out_counts, float* out_scores, int64_t* out_ids,
+                              int64_t* out_n_buckets, int64_t* out_total_hits);
+int rass_index_aggregate_keys_device(rass_index_t* idx, const float* d_queries, int nq, const float* d_min_score, int size,
+                                     const int32_t* d_keys, int64_t n_keys, int32_t n_groups,
+                                     const uint32_t* d_allow, int n_bitmaps, int64_t words_per_bitmap,
+                                     const int32_t* d_q_filter, const int32_t* d_q_filter_mask,
+                                     int64_t id_base, int32_t* d_out_groups, int64_t* d_out_counts, float* d_out_scores,
+                                     int64_t* d_out_ids, int64_t* d_n_buckets, int64_t* d_total_hits, int32_t* d_status);
 
 /* GRAM matrices of short row lists: out[l][i][j] = the fp32 dot product of stored rows rows[l][i] and rows[l][j], as they lie
  * in the slab (normalised at add time: their cosine).  The similarity structure of a result set, duplicate detection over an

@@ -1,8 +1,9 @@
 // api_emit.hip — the C ABI of include/rass_engine.h: the searches that ride the exact fp32 scan and emit on the way, with
 // no ranking: the score-threshold search rass_index_search_range(_device), the grouped (collapsed) search
-// rass_index_search_grouped(_device) and the terms aggregation rass_index_aggregate(_device).  One device-group driver
-// (emit_begin / emit_scan) serves the three; the host variants go through host_groups.  Host-side C++ only: the kernels are scan_topk.hip
-// (ScanMode kRange / kGroupMax / kGroupCount), merge_topk.hip and group_topk.hip.  The objects and the threading rules:
+// rass_index_search_grouped(_device) and the terms aggregation rass_index_aggregate(_device), and the last two over a caller's
+// key column and bitmap: rass_index_search_grouped_keys(_device), rass_index_aggregate_keys(_device).  One device-group driver
+// (emit_begin / emit_scan) serves them all; the host variants go through host_groups.  Host-side C++ only: the kernels are scan_topk.hip
+// (ScanMode kRange / kGroupMax / kGroupCount / kGroupMaxKeys / kGroupCountKeys), merge_topk.hip and group_topk.hip.  The objects and the threading rules:
 // api_internal.h.
 
 #include "api_internal.h"
@@ -18,7 +19,52 @@ struct EmitRequest {
     const int32_t* q_filter = nullptr;
     const int32_t* q_filter_mask = nullptr;
     int64_t id_base = 0;
+    // the key-column forms of the grouped search and the aggregation: the rows' groups (nullptr: a bit field of the tag) and
+    // the bitmap(s) of THIS launch group's queries (nullptr: no restriction; allow_q_stride 0: one shared by all of them)
+    const int32_t* keys = nullptr;
+    int64_t n_keys = 0;
+    const uint32_t* allow = nullptr;
+    int64_t allow_q_stride = 0, allow_words = 0;
 };
+
+// What the caller of a key-column entry point passed, whole: key_request cuts out a launch group's part.
+struct KeyArgs {
+    const int32_t* keys;
+    int64_t n_keys;
+    const uint32_t* allow;
+    int n_bitmaps;
+    int64_t words;
+};
+constexpr int32_t kWholeKey = 0x7fffffff;   // group_mask of a key-column request: the whole (non-negative) key is the group
+
+void key_request(EmitRequest& r, const KeyArgs* kv, int done) {
+    if (!kv) return;
+    r.keys = kv->keys, r.n_keys = kv->n_keys;
+    if (kv->allow) {
+        r.allow_q_stride = kv->n_bitmaps == 1 ? 0 : kv->words;
+        r.allow = kv->allow + (int64_t)done * r.allow_q_stride;
+        r.allow_words = kv->words;
+    }
+}
+
+// The checks of a key-column request against the rows this launch group scans (read once: IndexView).
+int check_key_rows(const EmitRequest& r, const IndexView& iv) {
+    if (!r.keys) return RASS_OK;
+    if (r.n_keys < iv.rows)
+        return fail(RASS_ERR_INVALID, "n_keys (" + std::to_string(r.n_keys) + ") is smaller than the index's rows (" + std::to_string(iv.rows) + ")");
+    if (r.allow && r.allow_words < (iv.rows + 31) / 32)
+        return fail(RASS_ERR_INVALID, "words_per_bitmap (" + std::to_string(r.allow_words) + ") is smaller than ceil(rows / 32) = " +
+                                          std::to_string((iv.rows + 31) / 32));
+    return RASS_OK;
+}
+
+// ... and its fields of the launch that starts at query q0 of the group.
+void key_scan_args(rass::ScanArgs& a, const EmitRequest& r, const IndexView& iv, int q0) {
+    if (!r.keys) return;
+    a.group_keys = r.keys;
+    a.group_key_rows = (int)iv.rows;
+    if (r.allow) a.allow = r.allow + (int64_t)q0 * r.allow_q_stride, a.allow_q_stride = r.allow_q_stride;
+}
 
 // Where every scan keeps its queries: the head of the engine scratch.
 float* emit_queries(const rass_engine* eng) { return range_layout(eng->d_scratch).q_padded; }
@@ -222,6 +268,7 @@ int group_device_group(rass_index* idx, const GroupRequest& r) {
     rass_engine* eng = idx->eng;
     hipStream_t st = eng->stream;
     const IndexView iv = index_view(idx, /*filtered=*/true, r.id_base);   // the group key is in the tag: always read them
+    if (int rc = check_key_rows(r, iv)) return rc;
     if (int rc = emit_begin(idx, r, iv)) return rc;
     if (int rc = grow_group_table(eng, group_layout(nullptr, r.nq, r.n_groups).total, st, "grouped search")) return rc;
     const GroupView G = group_layout(eng->d_group, r.nq, r.n_groups);
@@ -233,6 +280,7 @@ int group_device_group(rass_index* idx, const GroupRequest& r) {
         a.group_mask = r.group_mask;
         a.group_shift = __builtin_ctz((unsigned)r.group_mask);
         a.group_n = r.n_groups;
+        key_scan_args(a, r, iv, q0);
     });
     if (rc != RASS_OK) return rc;
     HIP_TRY(rass::launch_group_select(G.table, r.nq, r.n_groups, r.k, iv.id_base, iv.id_map, r.out_scores, r.out_ids, r.out_groups,
@@ -250,15 +298,16 @@ int check_grouped(const rass_index* idx, int k, int32_t group_mask, int32_t n_gr
 // One attempt of the host grouped search.  A group whose scan met a group key >= n_groups ends the call.
 int search_grouped_once(rass_index* idx, const float* queries, int nq, int k, int32_t group_mask, int32_t n_groups,
                         const int32_t* q_filter, const int32_t* q_filter_mask, float* out_scores, int64_t* out_ids, int32_t* out_groups,
-                        int64_t* out_total) {
+                        int64_t* out_total, const KeyArgs* kv = nullptr) {
     rass_engine* eng = idx->eng;
     return host_groups(
         idx, queries, nq, q_filter, q_filter_mask, group_io_layout(nullptr).bytes, no_fill,
-        [&](HostSlot* sl, int, int b) -> int {
+        [&](HostSlot* sl, int done, int b) -> int {
             hipStream_t st = eng->stream;
             const GroupIoView H = group_io_layout(static_cast<unsigned char*>(sl->h_io)), D = group_io_layout(eng->d_io);
             const size_t cells = (size_t)b * k;
             GroupRequest r;
+            key_request(r, kv, done);
             r.queries = eng->d_qraw, r.nq = b, r.k = k, r.group_mask = group_mask, r.n_groups = n_groups;
             r.q_filter = q_filter ? eng->d_qfilter : nullptr, r.q_filter_mask = q_filter_mask ? eng->d_qmask : nullptr;
             r.out_scores = D.out_scores, r.out_ids = D.out_ids, r.out_groups = D.out_groups, r.total = D.total, r.status = D.status;
@@ -303,6 +352,7 @@ int agg_device_group(rass_index* idx, const AggRequest& r) {
     rass_engine* eng = idx->eng;
     hipStream_t st = eng->stream;
     const IndexView iv = index_view(idx, /*filtered=*/true, r.id_base);   // the group key is in the tag: always read them
+    if (int rc = check_key_rows(r, iv)) return rc;
     if (int rc = emit_begin(idx, r, iv)) return rc;
     if (int rc = grow_group_table(eng, agg_layout(nullptr, r.nq, r.n_groups).total, st, "aggregation")) return rc;
     const AggView G = agg_layout(eng->d_group, r.nq, r.n_groups);
@@ -316,6 +366,7 @@ int agg_device_group(rass_index* idx, const AggRequest& r) {
         a.group_mask = r.group_mask;
         a.group_shift = __builtin_ctz((unsigned)r.group_mask);
         a.group_n = r.n_groups;
+        key_scan_args(a, r, iv, q0);
     });
     if (rc != RASS_OK) return rc;
     HIP_TRY(rass::launch_group_count_select(G.count, G.best, r.nq, r.n_groups, r.size, iv.id_base, iv.id_map, r.out_groups, r.out_counts,
@@ -333,19 +384,20 @@ int check_aggregate(const rass_index* idx, int size, int32_t group_mask, int32_t
 // One attempt of the host aggregation.  A group whose scan met a hit with a group key >= n_groups ends the call.
 int aggregate_once(rass_index* idx, const float* queries, int nq, const float* min_score, int size, int32_t group_mask,
                    int32_t n_groups, const int32_t* q_filter, const int32_t* q_filter_mask, int32_t* out_groups, int64_t* out_counts,
-                   float* out_scores, int64_t* out_ids, int64_t* out_n_buckets, int64_t* out_total_hits) {
+                   float* out_scores, int64_t* out_ids, int64_t* out_n_buckets, int64_t* out_total_hits, const KeyArgs* kv = nullptr) {
     rass_engine* eng = idx->eng;
     return host_groups(
         idx, queries, nq, q_filter, q_filter_mask, agg_io_layout(nullptr).bytes,
         [&](HostSlot* sl, int done, int b) {
             memcpy(agg_io_layout(static_cast<unsigned char*>(sl->h_io)).thr, min_score + done, (size_t)b * sizeof(float));
         },
-        [&](HostSlot* sl, int, int b) -> int {
+        [&](HostSlot* sl, int done, int b) -> int {
             hipStream_t st = eng->stream;
             const AggIoView H = agg_io_layout(static_cast<unsigned char*>(sl->h_io)), D = agg_io_layout(eng->d_io);
             const size_t cells = (size_t)b * size;
             HIP_TRY(hipMemcpyAsync(D.thr, H.thr, (size_t)b * sizeof(float), hipMemcpyHostToDevice, st));
             AggRequest r;
+            key_request(r, kv, done);
             r.queries = eng->d_qraw, r.nq = b, r.min_score = D.thr, r.size = size, r.group_mask = group_mask, r.n_groups = n_groups;
             r.q_filter = q_filter ? eng->d_qfilter : nullptr, r.q_filter_mask = q_filter_mask ? eng->d_qmask : nullptr;
             r.out_groups = D.out_groups, r.out_counts = D.out_counts, r.out_scores = D.out_scores, r.out_ids = D.out_ids;
@@ -373,6 +425,17 @@ int aggregate_once(rass_index* idx, const float* queries, int nq, const float* m
             memcpy(out_ids + (int64_t)done * size, H.out_ids, cells * sizeof(int64_t));
             return RASS_OK;
         });
+}
+
+// The arguments every key-column entry point adds.
+int check_keys(const rass_index* idx, const KeyArgs& kv, int nq) {
+    if (!kv.keys) return fail(RASS_ERR_INVALID, "d_keys is NULL");
+    if (kv.n_keys < 0) return fail(RASS_ERR_INVALID, "n_keys is negative");
+    if (!kv.allow) return RASS_OK;
+    if (kv.n_bitmaps != 1 && kv.n_bitmaps != nq) return fail(RASS_ERR_INVALID, "n_bitmaps must be 1 (shared) or nq (one per query)");
+    if (kv.words < 0) return fail(RASS_ERR_INVALID, "words_per_bitmap is negative");
+    if (idx->stride > kNarrowStride) return fail(RASS_ERR_UNSUPPORTED, "a bitmap with a key column needs dim <= 1024");
+    return RASS_OK;
 }
 
 }  // namespace
@@ -468,6 +531,82 @@ int rass_index_aggregate(rass_index_t* idx, const float* queries, int nq, const 
     return one_layout([&] { return idx->layout_epoch.load(std::memory_order_acquire); }, [&] {
         return aggregate_once(idx, queries, nq, min_score, size, group_mask, n_groups, q_filter, q_filter_mask, out_groups, out_counts,
                               out_scores, out_ids, out_n_buckets, out_total_hits);
+    });
+}
+
+int rass_index_search_grouped_keys_device(rass_index_t* idx, const float* d_queries, int nq, int k, const int32_t* d_keys,
+                                          int64_t n_keys, int32_t n_groups, const uint32_t* d_allow, int n_bitmaps,
+                                          int64_t words_per_bitmap, const int32_t* d_q_filter, const int32_t* d_q_filter_mask,
+                                          int64_t id_base, float* d_out_scores, int64_t* d_out_ids, int32_t* d_out_groups,
+                                          int64_t* d_group_total, int32_t* d_status) {
+    if (!idx || !d_queries || !d_out_scores || !d_out_ids || !d_out_groups || !d_group_total || !d_status)
+        return fail(RASS_ERR_INVALID, "NULL argument");
+    if (int rc = check_nq(nq)) return rc;
+    if (int rc = check_grouped(idx, k, kWholeKey, n_groups, d_q_filter, d_q_filter_mask)) return rc;
+    const KeyArgs kv{d_keys, n_keys, d_allow, n_bitmaps, words_per_bitmap};
+    if (int rc = check_keys(idx, kv, nq)) return rc;
+    GroupRequest r;
+    r.queries = d_queries, r.nq = nq, r.k = k, r.group_mask = kWholeKey, r.n_groups = n_groups;
+    r.q_filter = d_q_filter, r.q_filter_mask = d_q_filter_mask, r.id_base = id_base;
+    r.out_scores = d_out_scores, r.out_ids = d_out_ids, r.out_groups = d_out_groups, r.total = d_group_total, r.status = d_status;
+    key_request(r, &kv, 0);
+    return device_locked(idx, [&] { return group_device_group(idx, r); });
+}
+
+int rass_index_search_grouped_keys(rass_index_t* idx, const float* queries, int nq, int k, const int32_t* d_keys, int64_t n_keys,
+                                   int32_t n_groups, const uint32_t* d_allow, int n_bitmaps, int64_t words_per_bitmap,
+                                   const int32_t* q_filter, const int32_t* q_filter_mask, float* out_scores, int64_t* out_ids,
+                                   int32_t* out_groups, int64_t* out_group_total) {
+    if (!idx || !out_scores || !out_ids || !out_groups || !out_group_total) return fail(RASS_ERR_INVALID, "NULL argument");
+    if (nq < 0 || (nq > 0 && !queries)) return fail(RASS_ERR_INVALID, "bad queries / nq");
+    if (int rc = check_grouped(idx, k, kWholeKey, n_groups, q_filter, q_filter_mask)) return rc;
+    const KeyArgs kv{d_keys, n_keys, d_allow, n_bitmaps, words_per_bitmap};
+    if (int rc = check_keys(idx, kv, nq)) return rc;
+    if (nq == 0) return RASS_OK;
+    return one_layout([&] { return idx->layout_epoch.load(std::memory_order_acquire); }, [&] {
+        return search_grouped_once(idx, queries, nq, k, kWholeKey, n_groups, q_filter, q_filter_mask, out_scores, out_ids, out_groups,
+                                   out_group_total, &kv);
+    });
+}
+
+int rass_index_aggregate_keys_device(rass_index_t* idx, const float* d_queries, int nq, const float* d_min_score, int size,
+                                     const int32_t* d_keys, int64_t n_keys, int32_t n_groups, const uint32_t* d_allow, int n_bitmaps,
+                                     int64_t words_per_bitmap, const int32_t* d_q_filter, const int32_t* d_q_filter_mask,
+                                     int64_t id_base, int32_t* d_out_groups, int64_t* d_out_counts, float* d_out_scores,
+                                     int64_t* d_out_ids, int64_t* d_n_buckets, int64_t* d_total_hits, int32_t* d_status) {
+    if (!idx || !d_queries || !d_min_score || !d_out_groups || !d_out_counts || !d_out_scores || !d_out_ids || !d_n_buckets ||
+        !d_total_hits || !d_status)
+        return fail(RASS_ERR_INVALID, "NULL argument");
+    if (int rc = check_nq(nq)) return rc;
+    if (int rc = check_aggregate(idx, size, kWholeKey, n_groups, d_q_filter, d_q_filter_mask)) return rc;
+    const KeyArgs kv{d_keys, n_keys, d_allow, n_bitmaps, words_per_bitmap};
+    if (int rc = check_keys(idx, kv, nq)) return rc;
+    AggRequest r;
+    r.queries = d_queries, r.nq = nq, r.min_score = d_min_score, r.size = size, r.group_mask = kWholeKey, r.n_groups = n_groups;
+    r.q_filter = d_q_filter, r.q_filter_mask = d_q_filter_mask, r.id_base = id_base;
+    r.out_groups = d_out_groups, r.out_counts = d_out_counts, r.out_scores = d_out_scores, r.out_ids = d_out_ids;
+    r.n_buckets = d_n_buckets, r.total_hits = d_total_hits, r.status = d_status;
+    key_request(r, &kv, 0);
+    return device_locked(idx, [&] { return agg_device_group(idx, r); });
+}
+
+int rass_index_aggregate_keys(rass_index_t* idx, const float* queries, int nq, const float* min_score, int size,
+                              const int32_t* d_keys, int64_t n_keys, int32_t n_groups, const uint32_t* d_allow, int n_bitmaps,
+                              int64_t words_per_bitmap, const int32_t* q_filter, const int32_t* q_filter_mask, int32_t* out_groups,
+                              int64_t* out_counts, float* out_scores, int64_t* out_ids, int64_t* out_n_buckets,
+                              int64_t* out_total_hits) {
+    if (!idx || !out_groups || !out_counts || !out_scores || !out_ids || !out_n_buckets || !out_total_hits)
+        return fail(RASS_ERR_INVALID, "NULL argument");
+    if (nq < 0 || (nq > 0 && (!queries || !min_score))) return fail(RASS_ERR_INVALID, "bad queries / min_score / nq");
+    if (int rc = check_aggregate(idx, size, kWholeKey, n_groups, q_filter, q_filter_mask)) return rc;
+    const KeyArgs kv{d_keys, n_keys, d_allow, n_bitmaps, words_per_bitmap};
+    if (int rc = check_keys(idx, kv, nq)) return rc;
+    for (int q = 0; q < nq; ++q)
+        if (min_score[q] != min_score[q]) return fail(RASS_ERR_INVALID, "min_score is NaN");
+    if (nq == 0) return RASS_OK;
+    return one_layout([&] { return idx->layout_epoch.load(std::memory_order_acquire); }, [&] {
+        return aggregate_once(idx, queries, nq, min_score, size, kWholeKey, n_groups, q_filter, q_filter_mask, out_groups, out_counts,
+                              out_scores, out_ids, out_n_buckets, out_total_hits, &kv);
     });
 }
 

@@ -12,6 +12,7 @@
 //   api_ivf.hip      IVF: the host-planned and the device-planned build on one build tail, persistence over one section
 //                    list, the probe and the batch on one fine scan, the delta, the host API (host_groups)
 //   api_allow.hip    the allow-list search (top-k within a per-query row bitmap), its bitmap builders and its plan
+//   api_keys.hip     the key columns built from the attribute columns (what the grouped search and the aggregation group by)
 //   api_attr.hip     the attribute columns of a flat index and the predicate builder that turns clauses over them into bitmaps
 //   api_mmr.hip      the diversified (MMR) search and the Gram matrices of row lists
 //   api_compact.hip  compaction of a flat index, its layout epoch, the stateless wrappers of compact.hip

@@ -3,6 +3,7 @@
 #pragma once
 
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 
 namespace rass {
@@ -75,7 +76,10 @@ struct ScanArgs {
     // row of this slab).  launch_range_finish turns that into the answer.
     const float* range_thr = nullptr;
     unsigned* range_count = nullptr;
-    uint2* range_hits = nullptr;
+    union {
+        uint2* range_hits = nullptr;
+        const int32_t* group_keys;   // kGroupMaxKeys / kGroupCountKeys (below): never together with a range scan
+    };
     int range_cap = 0;
     // Group-max scan (kGroupMax; group_table != nullptr selects it: flat scans only, no sample floor, no continuation bound,
     // `k` and part_* unused).  The group key of a row is (tag & group_mask) >> group_shift.  A row that is live and passes
@@ -86,6 +90,7 @@ struct ScanArgs {
     unsigned long long* group_table = nullptr;
     unsigned* group_status = nullptr;
     int group_mask = 0, group_shift = 0, group_n = 0;
+    int group_key_rows = 0;   // kGroupMaxKeys / kGroupCountKeys (below)
     // Allow-list scan (kAllow; allow != nullptr selects it: narrow rows, <= 32 zero-padded queries, a work list as for an IVF
     // probe — launch_allow_plan's —, plain or masked filters and the continuation bound; no sample floor).  Query q's word of
     // tile t is allow[q * allow_q_stride + t] (allow_q_stride = 0: one bitmap shared by every query); bit r of it allows row
@@ -100,7 +105,24 @@ struct ScanArgs {
     // zeroed by the caller).  A hit with key >= group_n is left out and sets *group_status to 1.  launch_group_count_select
     // turns the two tables into the answer.
     unsigned* count_table = nullptr;
+    // Key-column grouping (kGroupMaxKeys / kGroupCountKeys; group_keys != nullptr selects them, with the fields of the group-max
+    // or group-count scan set as above except group_mask / group_shift, which are not read).  The group of row r is
+    // group_keys[r]: >= 0 the key, negative (RASS_KEY_NONE) = in no group.  A row without a group, or at or past
+    // group_key_rows, is neither a match nor a hit and never touches *group_status; a key >= group_n on a matching row / a hit
+    // sets it, as above.  row_tag may be null (no tombstones, no filters).  `allow` (optional, narrow rows only) restricts
+    // query q to the rows whose bit is set in allow[q * allow_q_stride + tile], kAllow's test (the words are read through the
+    // constant address space: these kernels write global memory, and a plain load would not come out scalar); the scan stays flat — every
+    // tile is streamed whatever the bitmap holds (a plan-driven walk that skips tiles is not built).
+    // The two fields live in the struct where it had room (group_keys shares range_hits' slot, group_key_rows fills the
+    // padding behind group_n): the kernel argument block keeps its size and every older field its offset, so the kernels that
+    // do not read them compile to the device code they had.
 };
+// The layout the comment above promises: the argument block of every scan kernel is these 312 bytes.
+static_assert(sizeof(ScanArgs) == 312 && offsetof(ScanArgs, range_hits) == 240 && offsetof(ScanArgs, group_keys) == 240 &&
+                  offsetof(ScanArgs, range_cap) == 248 && offsetof(ScanArgs, group_n) == 280 &&
+                  offsetof(ScanArgs, group_key_rows) == 284 && offsetof(ScanArgs, allow) == 288 &&
+                  offsetof(ScanArgs, count_table) == 304,
+              "ScanArgs grew or moved a field: every scan kernel's device code changes with it");
 constexpr int kRangeCountStride = 32;   // one 128-byte line per query's counter: every workgroup adds to all of them
 constexpr int kRangeMaxHits = 4096;     // = RASS_MAX_K_MULTIPASS: 4 096 64-bit sort keys are range_finish's 32 KiB of LDS
 
@@ -203,6 +225,23 @@ struct AttrArgs {
 hipError_t launch_attr_clauses(const AttrArgs& a, hipStream_t stream);
 // dst[i] = dst[i] & src[i] (op 1), | src[i] (2) or & ~src[i] (3) for i < words: two bitmaps of equal length, dst != src.
 hipError_t launch_allow_combine(uint32_t* dst, const uint32_t* src, int64_t words, int op, hipStream_t stream);
+
+// ---- key columns (group_keys.hip): the group of every row as int32 keys[n_keys], >= 0 the group, -1 (RASS_KEY_NONE) none; what
+// ScanArgs::group_keys takes.  col: an attribute column of n_rows <= n_keys values (nullptr: all missing); keys[n_rows .. n_keys)
+// = -1; missing_key >= -1 is the key of a missing value (INT32_MIN).  The tags are not read.  Plain vector loads and stores.
+// key = col[r] - base where that lies in [0, INT32_MAX] (computed in 64 bits), else -1.
+hipError_t launch_keys_from_attr(const int32_t* col, int64_t n_rows, int64_t n_keys, int32_t base, int32_t missing_key, int32_t* keys,
+                                 hipStream_t stream);
+// key = j where edges[j] <= col[r] < edges[j + 1], -1 outside [edges[0], edges[n_edges - 1]): `edges` is a DEVICE array of
+// 2 <= n_edges <= kKeyMaxEdges strictly ascending values (the caller checks the order), held in LDS and binary searched.
+constexpr int kKeyMaxEdges = 4097;   // = RASS_MAX_KEY_EDGES: RASS_MAX_K_MULTIPASS buckets
+hipError_t launch_keys_from_attr_edges(const int32_t* col, int64_t n_rows, int64_t n_keys, const int32_t* edges, int n_edges,
+                                       int32_t missing_key, int32_t* keys, hipStream_t stream);
+// key = (tags[r] & mask) >> ctz(mask) for a live row, -1 for a tombstone: the group of the tag-keyed searches.  mask > 0.
+hipError_t launch_keys_from_tag(const int32_t* tags, int64_t n_rows, int64_t n_keys, int32_t mask, int32_t* keys, hipStream_t stream);
+// out[0] / out[1] = min / max and out[2..3] (one 64-bit count) over the values of col that are not missing in rows whose tag is
+// not -1; the caller has set out to {INT32_MAX, INT32_MIN, 0, 0}.  col == nullptr: out is left as it is.
+hipError_t launch_attr_minmax(const int32_t* col, const int32_t* tags, int64_t n_rows, int32_t* out, hipStream_t stream);
 
 // ---- diversified (MMR) search (mmr.hip): the Gram matrices of short row lists and the greedy selection
 constexpr int kMmrMaxFetch = 128;   // = RASS_MAX_MMR_FETCH: rows per list, candidates per query (two per lane of one wave)

@@ -65,11 +65,17 @@ struct WorkItem {
 // kGroupCount: kRange's hits, emitted as kGroupMax emits: every row scoring >= the query's threshold adds 1 to the counter of
 // its (query, group) slot and is folded into the slot's running maximum (emit_group_count below; ScanArgs::count_table with
 // group_* and range_thr), for the terms aggregation.  No sample pass, no floor, no TopList.
+// kGroupMaxKeys / kGroupCountKeys: kGroupMax / kGroupCount with the row's group taken from a KEY COLUMN (ScanArgs::group_keys,
+// one int32 per row: >= 0 the group, < 0 no group) instead of a bit field of its tag, and, where ScanArgs::allow is set, within
+// a row bitmap as kAllow tests it.  The tag still decides tombstones and the per-query filters.  The key travels as the tag
+// does: one 32-lane buffer load per tile through a descriptor of its own (load_tile_keys below), parked in LDS for the ranking
+// step.  Still a flat scan: every tile is streamed whatever the bitmap holds.
 enum ScanMode { kFlat = 0, kIvf = 1, kMulti = 2, kFlatSample = 3, kFlatGroups = 4, kIvfGroups = 5, kFlatSampleGroups = 6, kRange = 7,
-                kGroupMax = 8, kAllow = 9, kGroupCount = 10 };
+                kGroupMax = 8, kAllow = 9, kGroupCount = 10, kGroupMaxKeys = 11, kGroupCountKeys = 12 };
+constexpr bool mode_has_keys(int mode) { return mode == kGroupMaxKeys || mode == kGroupCountKeys; }
 constexpr bool mode_is_flat(int mode) {
     return mode == kFlat || mode == kFlatSample || mode == kFlatGroups || mode == kFlatSampleGroups || mode == kRange ||
-           mode == kGroupMax || mode == kGroupCount;
+           mode == kGroupMax || mode == kGroupCount || mode_has_keys(mode);
 }
 constexpr bool mode_is_sample(int mode) { return mode == kFlatSample || mode == kFlatSampleGroups; }
 
@@ -119,6 +125,16 @@ __device__ __forceinline__ f32x4 load_chunk(const TileDesc& d, int voff, int sof
 
 __device__ __forceinline__ int load_tag(const TileDesc& d) {
     return (int)__builtin_amdgcn_raw_buffer_load_b32(d.tags, (lane_id() & 31) * 4, 0, 0);
+}
+
+// The group keys of a tile's 32 rows (kGroupMaxKeys / kGroupCountKeys), one per lane & 31 as load_tag: a descriptor of its
+// own over the tile's rows that have a key (none for a run-ahead tile past the end: zero records, no traffic).  A lane past
+// the records reads 0; the ranking step drops such a row by its number, not by what it read.
+__device__ __forceinline__ int load_tile_keys(const int32_t* __restrict__ keys, int key_rows, const WorkItem& w) {
+    const int left = key_rows - w.tile * kTileRows;
+    const int n = left < w.rows ? (left < 0 ? 0 : left) : w.rows;
+    const __amdgpu_buffer_rsrc_t d = make_rsrc(reinterpret_cast<uint64_t>(keys + (int64_t)w.tile * kTileRows), (unsigned)(n * 4));
+    return (int)__builtin_amdgcn_raw_buffer_load_b32(d, (lane_id() & 31) * 4, 0, 0);
 }
 
 // Prologue: all of a tile's loads, in the order multiply_and_refill consumes them.  `soff0`: byte offset of the K

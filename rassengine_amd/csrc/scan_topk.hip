@@ -180,12 +180,14 @@ __global__ __launch_bounds__(kThreads, 2) void scan_topk_f32_kernel(ScanArgs p) 
     __shared__ float sh_after_s[32];
     __shared__ int64_t sh_after_i[32];
     __shared__ float sh_thr[32];    // kRange, kGroupCount: the per-query score thresholds (NaN past nq: nothing matches)
+    __shared__ int sh_keys[4][32];  // kGroupMaxKeys, kGroupCountKeys: the dumped tiles' group keys, next to their tags
+    constexpr bool KEYS = mode_has_keys(MODE);
     if (threadIdx.x < 32) {
         const int q = threadIdx.x;
         const bool live = q < p.nq;
         sh_qfilt[q] = (p.q_filter != nullptr && live) ? p.q_filter[q] : -1;
         sh_floor[q] = -INFINITY;
-        if (MODE == kRange || MODE == kGroupCount) sh_thr[q] = live ? p.range_thr[q] : __builtin_nanf("");
+        if (MODE == kRange || MODE == kGroupCount || MODE == kGroupCountKeys) sh_thr[q] = live ? p.range_thr[q] : __builtin_nanf("");
         if (EXT) {
             sh_qmask[q] = (p.q_filter_mask != nullptr && live) ? p.q_filter_mask[q] : -1;
             sh_after_s[q] = (p.q_after_score != nullptr && live) ? p.q_after_score[q] : INFINITY;
@@ -216,6 +218,13 @@ __global__ __launch_bounds__(kThreads, 2) void scan_topk_f32_kernel(ScanArgs p) 
     int t = seq.next();  // the item R0 holds; R1 holds the one after it
     const int t1 = seq.next();
     WorkItem W0 = get_work<MODE>(p, t, n_tiles), W1 = get_work<MODE>(p, t1, n_tiles);
+    // KEYS: the two tiles' group keys, one register each, requested AHEAD of the tiles' own loads here and in the main loop: the
+    // wait that parks a tile's tags in LDS has then seen the older key load come back too (vmcnt counts in order)
+    int K0 = 0, K1 = 0;
+    if (KEYS) {
+        K0 = load_tile_keys(p.group_keys, p.group_key_rows, W0);
+        K1 = load_tile_keys(p.group_keys, p.group_key_rows, W1);
+    }
     issue_tile_loads<CH>(R0, make_tile_desc(slab_of<MODE>(p, t, n_tiles), p.row_stride, tags_of<MODE>(p, t, n_tiles), W0),
                          voff_lane, mt_step);
     issue_tile_loads<CH>(R1, make_tile_desc(slab_of<MODE>(p, t1, n_tiles), p.row_stride, tags_of<MODE>(p, t1, n_tiles), W1),
@@ -312,6 +321,30 @@ __global__ __launch_bounds__(kThreads, 2) void scan_topk_f32_kernel(ScanArgs p) 
                              p.group_status);
             return;
         }
+        if (KEYS) {   // the two emissions above with the row's group from its key column, within the bitmap where there is one
+            const int key = sh_keys[buf][r];
+            ok = ok && key >= 0 && row < p.group_key_rows;   // no group: neither a match nor a hit, whatever the key's size
+            if (p.allow != nullptr) {   // kAllow's test (a kernel argument: a scalar branch, not an exec mask)
+                // The wave's two words of the tile.  This kernel also writes global memory (the emitters' atomics), so hipcc
+                // no longer proves a plain load of the bitmap unclobbered and would fetch it with a vector load and a
+                // vmcnt(0) wait right here, between the MFMA chunks, draining the corpus loads in flight.  Read through
+                // the constant address space the two wave-uniform addresses are scalar loads whatever else the kernel does.
+                typedef const __attribute__((address_space(4))) unsigned* const_words;
+                const const_words allow = (const_words)reinterpret_cast<uintptr_t>(p.allow);
+                const int qa = min(pq * 16 + wid, p.nq - 1), qb = min(pq * 16 + 8 + wid, p.nq - 1);
+                const unsigned wa = allow[(int64_t)qa * p.allow_q_stride + w.tile];
+                const unsigned wb = allow[(int64_t)qb * p.allow_q_stride + w.tile];
+                ok = ok && ((((lane & 32) ? wb : wa) >> r) & 1u);
+            }
+            // the whole key is the group: mask 0x7fffffff, shift 0
+            if (MODE == kGroupMaxKeys)
+                emit_group_max(ok && q < p.nq, s, row, key, 0x7fffffff, 0, p.group_n, p.group_table + (int64_t)q * p.group_n,
+                               p.group_status);
+            else
+                emit_group_count(ok && s >= sh_thr[q], s, row, key, q, 0x7fffffff, 0, p.group_n, p.group_table, p.count_table,
+                                 p.group_status);
+            return;
+        }
         // the sample floor: k rows of the corpus already score >= floor_q, so a row below it cannot be in the
         // query's top-k (ties are kept: the id order decides them in the merge)
         const float floor_q = MODE == kFlat ? sh_floor[q] : -INFINITY;
@@ -349,10 +382,15 @@ __global__ __launch_bounds__(kThreads, 2) void scan_topk_f32_kernel(ScanArgs p) 
         if (wid == 0 && lane < 32) {
             sh_tags[pair][lane] = R0.tag;
             sh_tags[pair + 1][lane] = R1.tag;
+            if (KEYS) {
+                sh_keys[pair][lane] = K0;
+                sh_keys[pair + 1][lane] = K1;
+            }
         }
         const WorkItem Wa = W0;
         t = seq.next();
         WorkItem Wn = get_work<MODE>(p, t, n_tiles);
+        if (KEYS) K0 = load_tile_keys(p.group_keys, p.group_key_rows, Wn);
         auto rank_prev = [&](int slot) {
 #pragma unroll
             for (int part = 0; part < kParts; ++part)
@@ -371,6 +409,7 @@ __global__ __launch_bounds__(kThreads, 2) void scan_topk_f32_kernel(ScanArgs p) 
         const WorkItem Wb = W1;
         const int tn = seq.next();
         Wn = get_work<MODE>(p, tn, n_tiles);
+        if (KEYS) K1 = load_tile_keys(p.group_keys, p.group_key_rows, Wn);
         multiply_and_refill<CH, NT>(R1, qf, acc,
                                     make_tile_desc(slab_of<MODE>(p, tn, n_tiles), p.row_stride, tags_of<MODE>(p, tn, n_tiles), Wn),
                                     voff_lane, mt_step, [&](int j) { rank_prev(CH + j); });
@@ -399,7 +438,7 @@ __global__ __launch_bounds__(kThreads, 2) void scan_topk_f32_kernel(ScanArgs p) 
     if (threadIdx.x == 0) g_scan_clocks[2 * blockIdx.x + 1] = wall_clock64();
     if (threadIdx.x == 0 && blockIdx.x == 0) g_scan_core[1] = clock64();
 #endif
-    if (MODE == kRange || MODE == kGroupMax || MODE == kGroupCount) return;   // everything was emitted on the way
+    if (MODE == kRange || MODE == kGroupMax || MODE == kGroupCount || KEYS) return;   // everything was emitted on the way
     if (mode_is_sample(MODE)) {
         // The sample pass: this workgroup's best score per query -> part_scores[32][kMaxSampleGroups] (-inf: no row of the
         // sample passed the query's filters); the big scan's waves take the k-th largest over the workgroups.
@@ -681,9 +720,16 @@ __device__ __forceinline__ void wide_panels(TileRegs<CHP>& R0, TileRegs<CHP>& R1
     }
 }
 
-template <int CHP, int P, bool EXT, bool RANGE, bool GROUP, bool COUNT>
+// PK: the number of panels P, plus kWideKeys where GROUP / COUNT take the row's group from its key column (the emission of
+// kGroupMaxKeys / kGroupCountKeys; no bitmap on wide rows).  The flag rides in the panel slot because a template parameter
+// of its own would rename every instantiation this kernel already has.
+constexpr int kWideKeys = 8;
+template <int CHP, int PK, bool EXT, bool RANGE, bool GROUP, bool COUNT>
 __global__ __launch_bounds__(kThreads, 2) void scan_topk_f32_wide_kernel(ScanArgs p) {
+    constexpr int P = PK & (kWideKeys - 1);
+    constexpr bool KEYS = (PK & kWideKeys) != 0;
     static_assert((int)RANGE + (int)GROUP + (int)COUNT <= 1, "one emission per kernel");
+    static_assert(!KEYS || GROUP || COUNT, "a key column feeds the grouped emissions only");
     static_assert(P == 2 || P == 4, "R0 holds the even panels, R1 the odd ones");
     constexpr int NQ = 16, CHT = P * CHP;
     extern __shared__ __attribute__((aligned(16))) float lds[];  // [4][kWaves][NQ][kPitch]
@@ -714,6 +760,7 @@ __global__ __launch_bounds__(kThreads, 2) void scan_topk_f32_wide_kernel(ScanArg
     __shared__ float sh_after_s[16];
     __shared__ int64_t sh_after_i[16];
     __shared__ float sh_thr[16];    // RANGE, COUNT: the per-query score thresholds (NaN past nq: nothing matches)
+    __shared__ int sh_keys[4][32];  // KEYS: the dumped tiles' group keys, next to their tags
     if (threadIdx.x < 16) {
         const int q = threadIdx.x;
         const bool live = q < p.nq;
@@ -733,6 +780,9 @@ __global__ __launch_bounds__(kThreads, 2) void scan_topk_f32_wide_kernel(ScanArg
     int t = seq.next();
     WorkItem W0 = get_work<kFlat>(p, t, n_tiles);
     TileDesc D0 = make_tile_desc(p.corpus, p.row_stride, p.row_tag, W0);
+    // KEYS: the group keys of the tile whose first panels are on their way, requested ahead of them (see scan_topk_f32_kernel)
+    int K0 = 0;
+    if (KEYS) K0 = load_tile_keys(p.group_keys, p.group_key_rows, W0);
     issue_tile_loads<CHP, true>(R0, D0, voff_lane, mt_step, 0);
     issue_tile_loads<CHP, false>(R1, D0, voff_lane, mt_step, CHP * 1024);
     __builtin_amdgcn_sched_barrier(0);
@@ -768,6 +818,17 @@ __global__ __launch_bounds__(kThreads, 2) void scan_topk_f32_wide_kernel(ScanArg
                        p.range_cap);
             return;
         }
+        if (KEYS) {   // the emission of scan_topk_f32_kernel's kGroupMaxKeys / kGroupCountKeys modes
+            const int key = sh_keys[buf][r];
+            ok = ok && key >= 0 && row < p.group_key_rows;
+            if (GROUP)
+                emit_group_max(ok && q < p.nq, s, row, key, 0x7fffffff, 0, p.group_n, p.group_table + (int64_t)q * p.group_n,
+                               p.group_status);
+            else
+                emit_group_count(ok && s >= sh_thr[q], s, row, key, q, 0x7fffffff, 0, p.group_n, p.group_table, p.count_table,
+                                 p.group_status);
+            return;
+        }
         if (GROUP) {   // the emission of scan_topk_f32_kernel's kGroupMax mode
             emit_group_max(ok && q < p.nq, s, row, tag, p.group_mask, p.group_shift, p.group_n,
                            p.group_table + (int64_t)q * p.group_n, p.group_status);
@@ -788,16 +849,20 @@ __global__ __launch_bounds__(kThreads, 2) void scan_topk_f32_wide_kernel(ScanArg
         f32x4 acc[2][1];
         // ---- tile A = W0 (its first two panels resident); the registers run on into tile B
         if (wid == 0 && lane < 32) sh_tags[pair][lane] = R0.tag;
+        if (KEYS && wid == 0 && lane < 32) sh_keys[pair][lane] = K0;
         const WorkItem Wa = W0;
         const int tb = seq.next();
         const WorkItem Wb = get_work<kFlat>(p, tb, n_tiles);
+        if (KEYS) K0 = load_tile_keys(p.group_keys, p.group_key_rows, Wb);
         const TileDesc Db = make_tile_desc(p.corpus, p.row_stride, p.row_tag, Wb);
         wide_panels<0, P, CHP>(R0, R1, qf, acc, D0, Db, voff_lane, mt_step, [&]() { rank_tile(Pa, pair ^ 2); });
         dump_tile(acc, pair);
         // ---- tile B; the registers run on into tile C
         if (wid == 0 && lane < 32) sh_tags[pair + 1][lane] = R0.tag;
+        if (KEYS && wid == 0 && lane < 32) sh_keys[pair + 1][lane] = K0;
         t = seq.next();
         const WorkItem Wc = get_work<kFlat>(p, t, n_tiles);
+        if (KEYS) K0 = load_tile_keys(p.group_keys, p.group_key_rows, Wc);
         D0 = make_tile_desc(p.corpus, p.row_stride, p.row_tag, Wc);
         wide_panels<0, P, CHP>(R0, R1, qf, acc, Db, D0, voff_lane, mt_step, [&]() { rank_tile(Pb, (pair ^ 2) + 1); });
         dump_tile(acc, pair + 1);
@@ -821,7 +886,7 @@ __global__ __launch_bounds__(kThreads, 2) void scan_topk_f32_wide_kernel(ScanArg
     }
 }
 
-template <int CHP, int P, bool EXT, bool RANGE, bool GROUP, bool COUNT>
+template <int CHP, int P, bool EXT, bool RANGE, bool GROUP, bool COUNT>   // P: panels (+ kWideKeys)
 static hipError_t launch_wide_variant(const ScanArgs& a, int grid, hipStream_t stream) {
     constexpr size_t lds_bytes = (size_t)4 * kWaves * 16 * kPitch * sizeof(float);  // 72 KiB
     static bool attr_set = false;
@@ -835,13 +900,13 @@ static hipError_t launch_wide_variant(const ScanArgs& a, int grid, hipStream_t s
     return hipGetLastError();
 }
 
-template <bool EXT, bool RANGE = false, bool GROUP = false, bool COUNT = false>
+template <bool EXT, bool RANGE = false, bool GROUP = false, bool COUNT = false, int KEYS = 0>   // KEYS: 0 or kWideKeys
 static hipError_t launch_wide(int ch_total, const ScanArgs& a, int grid, hipStream_t stream) {
     switch (ch_total) {
-        case 10: return launch_wide_variant<5, 2, EXT, RANGE, GROUP, COUNT>(a, grid, stream);
-        case 12: return launch_wide_variant<6, 2, EXT, RANGE, GROUP, COUNT>(a, grid, stream);
-        case 14: return launch_wide_variant<7, 2, EXT, RANGE, GROUP, COUNT>(a, grid, stream);
-        case 16: return launch_wide_variant<4, 4, EXT, RANGE, GROUP, COUNT>(a, grid, stream);   // 2 x 8 chunks spill (256 VGPRs at 2 waves per SIMD)
+        case 10: return launch_wide_variant<5, 2 + KEYS, EXT, RANGE, GROUP, COUNT>(a, grid, stream);
+        case 12: return launch_wide_variant<6, 2 + KEYS, EXT, RANGE, GROUP, COUNT>(a, grid, stream);
+        case 14: return launch_wide_variant<7, 2 + KEYS, EXT, RANGE, GROUP, COUNT>(a, grid, stream);
+        case 16: return launch_wide_variant<4, 4 + KEYS, EXT, RANGE, GROUP, COUNT>(a, grid, stream);   // 2 x 8 chunks spill (256 VGPRs at 2 waves per SIMD)
         default: return hipErrorInvalidValue;
     }
 }
@@ -936,10 +1001,33 @@ static hipError_t launch_emit(int ch, bool ext, const ScanArgs& a, int grid, hip
     return ext ? launch_ch<2, MODE, true>(ch, a, grid, stream) : launch_ch<2, MODE>(ch, a, grid, stream);
 }
 
+// The group-max / group-count scans over a key column (kGroupMaxKeys / kGroupCountKeys), optionally within a bitmap: one
+// variant per stride and query count, always the masked-filter one (absent masks take their neutral value in LDS).
+static hipError_t launch_emit_keys(int ch, const ScanArgs& a, int grid, hipStream_t stream) {
+    const bool count = a.count_table != nullptr;
+    if (a.nq < 1 || a.nq > 32 || !a.group_status || a.group_n < 1 || a.group_n > kGroupMaxGroups || a.group_key_rows < 0)
+        return hipErrorInvalidValue;
+    if (count && !a.range_thr) return hipErrorInvalidValue;
+    if (a.q_after_score || a.q_after_id || a.work_tile || a.work_base || a.sample_pass || a.sample_best || a.wgs_per_group || a.live_nq)
+        return hipErrorInvalidValue;
+    if ((a.q_filter_mask != nullptr && a.q_filter == nullptr) || (a.q_filter != nullptr && a.row_tag == nullptr)) return hipErrorInvalidValue;
+    if (a.allow != nullptr && (ch > 8 || a.allow_q_stride < 0)) return hipErrorInvalidValue;   // the bitmap: narrow rows only
+    if (ch > 8) {
+        if (a.nq > 16) return hipErrorInvalidValue;   // the caller splits larger groups, as for the top-k scan
+        return count ? launch_wide<true, false, false, true, kWideKeys>(ch, a, grid, stream)
+                     : launch_wide<true, false, true, false, kWideKeys>(ch, a, grid, stream);
+    }
+    if (a.nq <= 16)
+        return count ? launch_ch<1, kGroupCountKeys, true>(ch, a, grid, stream) : launch_ch<1, kGroupMaxKeys, true>(ch, a, grid, stream);
+    return count ? launch_ch<2, kGroupCountKeys, true>(ch, a, grid, stream) : launch_ch<2, kGroupMaxKeys, true>(ch, a, grid, stream);
+}
+
 hipError_t launch_scan_topk_f32(const ScanArgs& a, int grid, hipStream_t stream) {
     if (!scan_supported_stride(a.row_stride)) return hipErrorInvalidValue;
     const int ch = (int)(a.row_stride / 128);
     const bool ext = a.q_filter_mask || a.q_after_score || a.q_after_id;
+    // a key column (it shares range_hits' slot: a range scan, range_count set, has none)
+    if (a.range_count == nullptr && a.group_table != nullptr && a.group_keys != nullptr) return launch_emit_keys(ch, a, grid, stream);
     if (a.allow != nullptr) {  // the allow-list scan: narrow rows, a work list, filters and continuation bound, nothing else
         if (!a.work_tile || !a.work_rows || !a.work_mask || !a.n_work || a.work_base || ch > 8 || a.nq < 1 || a.nq > 32 || a.allow_q_stride < 0)
             return hipErrorInvalidValue;

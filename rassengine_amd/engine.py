@@ -554,6 +554,240 @@ class FlatIndex:
                                                     ctypes.c_void_p(d_n_buckets_ptr), ctypes.c_void_p(d_total_hits_ptr),
                                                     ctypes.c_void_p(d_status_ptr)))
 
+    # ---- key columns: group and aggregate by any attribute column, optionally within a bitmap
+    KEY_NONE = N.RASS_KEY_NONE             # a row in no group
+    ERR_INVALID = -1                       # RASS_ERR_INVALID: what a native call answers to a column that is too short
+    MAX_KEY_EDGES = N.RASS_MAX_KEY_EDGES   # group_keys_from_attr(edges=...): 4 096 buckets
+    KEY_SLACK_ROWS = 2048                  # keys a new column gets beyond ``rows``: rows appended meanwhile still fit
+
+    @staticmethod
+    def _check_key_builder(col, base, missing, edges):
+        col, base, missing = int(col), int(base), int(missing)
+        if not 0 <= col < N.RASS_MAX_ATTRS:
+            raise ValueError(f"col must be in [0, {N.RASS_MAX_ATTRS}), got {col}")
+        if not -(1 << 31) <= base <= (1 << 31) - 1:
+            raise ValueError(f"base must fit int32, got {base}")
+        if not -1 <= missing <= (1 << 31) - 1:
+            raise ValueError(f"missing must be -1 (no group) or a key >= 0 that fits int32, got {missing}")
+        if edges is not None:
+            e = np.asarray(edges)
+            if e.ndim != 1 or e.dtype.kind not in "iu" or not 2 <= e.shape[0] <= FlatIndex.MAX_KEY_EDGES:
+                raise ValueError(f"edges must be 2 .. {FlatIndex.MAX_KEY_EDGES} integers in a 1-d array")
+            if int(e.min()) < -(1 << 31) or int(e.max()) > (1 << 31) - 1:
+                raise ValueError("edges must fit int32")
+            if base != 0:
+                raise ValueError("base has no meaning with edges")
+            edges = np.ascontiguousarray(e, dtype=np.int32)
+            if np.any(edges[1:] <= edges[:-1]):
+                raise ValueError("edges must be strictly ascending")
+        return col, base, missing, edges
+
+    def group_keys_from_attr(self, col: int, base: int = 0, missing: int = -1, edges=None):
+        """A key column from attribute column ``col``: an int32 CUDA tensor of ``rows`` entries plus slack (the surplus reads
+        ``KEY_NONE``) that ``search_grouped_by_keys`` / ``search_counts_by_keys`` take.  Without ``edges`` the key of a row
+        is ``value - base`` (``rass_index_keys_from_attr``; a result outside [0, 2^31) is ``KEY_NONE``): keyword codes with
+        ``base=0``, ints and days with ``base=min``.  With ``edges`` (2 .. 4097 strictly ascending int32) key j means
+        ``edges[j] <= value < edges[j + 1]``, a value outside them ``KEY_NONE`` (``rass_index_keys_from_attr_edges``).  A row
+        without a value gets ``missing`` (-1: no group).  The column names rows of one ``layout_epoch``; rows appended after
+        the call have no group in it."""
+        import torch
+        col, base, missing, edges = self._check_key_builder(col, base, missing, edges)
+        for _ in range(4):
+            n = self.rows + self.KEY_SLACK_ROWS
+            out = torch.empty((n,), dtype=torch.int32, device=f"cuda:{self.engine.device}")
+            torch.cuda.current_stream(out.device).synchronize()     # the engine works on its own stream
+            if edges is None:
+                fn = "rass_index_keys_from_attr"
+                rc = self._L.rass_index_keys_from_attr(self._h, col, base, missing, ctypes.c_void_p(out.data_ptr()), n)
+            else:
+                fn = "rass_index_keys_from_attr_edges"
+                rc = self._L.rass_index_keys_from_attr_edges(self._h, col, _np_ptr(edges), edges.shape[0], missing,
+                                                             ctypes.c_void_p(out.data_ptr()), n)
+            if rc < 0 and self.rows > n:
+                continue            # the index outgrew the slack meanwhile
+            N.check(fn, rc)
+            self.engine.synchronize()     # the builder ran on the engine's stream: the tensor is complete for torch's too
+            return out
+        raise RuntimeError(f"{self.name}: the index kept outgrowing the key column under construction")
+
+    def group_keys_from_tag(self, mask: int):
+        """The tag-keyed searches' group as a key column (``rass_index_keys_from_tag``): ``(tag & mask) >> ctz(mask)`` per live
+        row, ``KEY_NONE`` for a tombstone and in the slack; what ``search_grouped`` / ``search_counts`` group by under that
+        mask, for the ``*_by_keys`` calls that also take a bitmap."""
+        import torch
+        mask = int(mask)
+        if not 1 <= mask <= 0x7FFFFFFF:
+            raise ValueError(f"mask must be non-zero and within 0x7fffffff, got {mask:#x}")
+        for _ in range(4):
+            n = self.rows + self.KEY_SLACK_ROWS
+            out = torch.empty((n,), dtype=torch.int32, device=f"cuda:{self.engine.device}")
+            torch.cuda.current_stream(out.device).synchronize()     # the engine works on its own stream
+            rc = self._L.rass_index_keys_from_tag(self._h, mask, ctypes.c_void_p(out.data_ptr()), n)
+            if rc == self.ERR_INVALID and self.rows > n:
+                continue            # the index outgrew the slack meanwhile
+            N.check("rass_index_keys_from_tag", rc)
+            self.engine.synchronize()
+            return out
+        raise RuntimeError(f"{self.name}: the index kept outgrowing the key column under construction")
+
+    def attr_minmax(self, col: int) -> Tuple[Optional[int], Optional[int], int]:
+        """(min, max, n_present) of attribute column ``col`` over the live rows that have a value (``rass_index_attr_minmax``:
+        one small reduction on the device); (None, None, 0) when no live row has one."""
+        col = int(col)
+        if not 0 <= col < N.RASS_MAX_ATTRS:
+            raise ValueError(f"col must be in [0, {N.RASS_MAX_ATTRS}), got {col}")
+        lo, hi, n = ctypes.c_int32(0), ctypes.c_int32(0), ctypes.c_int64(0)
+        N.check("rass_index_attr_minmax", self._L.rass_index_attr_minmax(self._h, col, ctypes.byref(lo), ctypes.byref(hi), ctypes.byref(n)))
+        return (int(lo.value), int(hi.value), int(n.value)) if n.value else (None, None, 0)
+
+    @staticmethod
+    def _check_keys(keys, allow, nq: int):
+        """The key column and the bitmap of a ``*_by_keys`` call, checked without touching the device."""
+        dev_k = not isinstance(keys, np.ndarray) and hasattr(keys, "data_ptr")
+        if dev_k:
+            if not keys.is_cuda or str(keys.dtype) != "torch.int32" or keys.dim() != 1 or not keys.is_contiguous():
+                raise ValueError("a device key column must be a contiguous 1-d int32 CUDA tensor")
+        else:
+            k = np.asarray(keys)
+            if k.ndim != 1 or k.dtype.kind not in "iu":
+                raise ValueError(f"keys must be a 1-d integer array or a device key column, got {k.dtype} {k.shape}")
+            if k.size and (int(k.min()) < -(1 << 31) or int(k.max()) > (1 << 31) - 1):
+                raise ValueError("keys must fit int32")
+        if allow is None:
+            return
+        dev_a = not isinstance(allow, np.ndarray) and hasattr(allow, "data_ptr")
+        if dev_a:
+            if not allow.is_cuda or str(allow.dtype) != "torch.int32" or not allow.is_contiguous():
+                raise ValueError("a device bitmap must be a contiguous int32 CUDA tensor")
+        shape = tuple(allow.shape) if dev_a else np.asarray(allow).shape
+        if len(shape) not in (1, 2) or (len(shape) == 2 and shape[0] not in (1, nq)):
+            raise ValueError(f"allow must be [words] (shared) or [nq, words], got {shape} for {nq} queries")
+
+    def _fit_keys(self, keys, allow):
+        """``keys`` / ``allow`` on the device and long enough for the index as it is now: a key column shorter than the
+        index is padded with ``KEY_NONE`` (rows appended since it was built have no group), a bitmap with zero words."""
+        import torch
+        dev = torch.device(f"cuda:{self.engine.device}")
+        if isinstance(keys, np.ndarray) or not hasattr(keys, "data_ptr"):
+            keys = torch.from_numpy(np.ascontiguousarray(keys, dtype=np.int32)).to(dev)
+        rows = self.rows
+        if keys.shape[0] < rows:
+            pad = torch.full((rows + self.KEY_SLACK_ROWS - keys.shape[0],), self.KEY_NONE, dtype=torch.int32, device=dev)
+            keys = torch.cat([keys, pad]).contiguous()
+        if allow is not None:
+            if isinstance(allow, np.ndarray) or not hasattr(allow, "data_ptr"):
+                allow = torch.from_numpy(np.ascontiguousarray(allow, dtype=np.uint32).view(np.int32)).to(dev)
+            need = (rows + 31) // 32
+            if allow.shape[-1] < need:
+                pad = need + self.ALLOW_SLACK_WORDS - allow.shape[-1]
+                allow = torch.cat([allow, torch.zeros(tuple(allow.shape[:-1]) + (pad,), dtype=torch.int32, device=dev)], dim=-1).contiguous()
+        torch.cuda.current_stream(dev).synchronize()     # the engine works on its own stream
+        return keys, allow
+
+    @staticmethod
+    def _key_call_args(keys, allow):
+        n_bitmaps = 0 if allow is None else (1 if allow.dim() == 1 else int(allow.shape[0]))
+        return (ctypes.c_void_p(keys.data_ptr()), int(keys.shape[0]),
+                ctypes.c_void_p(allow.data_ptr()) if allow is not None else None, n_bitmaps,
+                int(allow.shape[-1]) if allow is not None else 0)
+
+    def _by_keys(self, fn: str, keys, allow, call):
+        """``call(d_keys, n_keys, d_allow, n_bitmaps, words)`` -> rc with the columns fitted to the index; run again where an
+        append outgrew them between the fit and the native call's own check."""
+        for _ in range(4):
+            k, a = self._fit_keys(keys, allow)
+            d_keys, n_keys, d_allow, n_bitmaps, words = self._key_call_args(k, a)
+            rc = call(d_keys, n_keys, d_allow, n_bitmaps, words)
+            if rc == self.ERR_INVALID and (self.rows > n_keys or (a is not None and self.allow_words > words)):
+                continue            # the native check refused columns an append has just outgrown: fit them again
+            N.check(fn, rc)
+            return
+        raise RuntimeError(f"{self.name}: the index kept outgrowing the key column during the search")
+
+    def search_grouped_by_keys(self, queries: np.ndarray, k: int, keys, n_groups: int, allow=None,
+                               q_filter: Optional[np.ndarray] = None, q_filter_mask: Optional[np.ndarray] = None
+                               ) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+        """``search_grouped`` with the group of a row taken from a key column (``rass_index_search_grouped_keys``): ``keys`` is
+        what ``group_keys_from_attr`` returns, or any int32 per row (numpy is uploaded) — >= 0 the group, negative = the row
+        is in no group and is never a match; a key >= ``n_groups`` on a matching row makes the call fail.  ``allow``
+        (optional): a bitmap as ``search_allowed`` takes it ([words] shared, [nq, words] one per query; dim <= 1024 only) —
+        a row then also needs its bit; the scan still streams the whole index.  Keys or bitmaps shorter than the index are
+        padded (no group / not allowed).  Returns what ``search_grouped`` returns; totals count only rows with a group."""
+        q = self._queries(queries)
+        nq = q.shape[0]
+        k, _, n_groups = self._check_grouped(k, 1, n_groups)
+        f, m = self._filters(q_filter, q_filter_mask, nq)
+        self._check_keys(keys, allow, nq)
+        out_s = np.empty((nq, k), dtype=np.float32)
+        out_i = np.empty((nq, k), dtype=np.int64)
+        out_g = np.empty((nq, k), dtype=np.int32)
+        total = np.empty((nq,), dtype=np.int64)
+        if nq == 0:
+            return out_s, out_i, out_g, total
+        fn = "rass_index_search_grouped_keys"
+        self._by_keys(fn, keys, allow, lambda d_keys, n_keys, d_allow, n_bitmaps, words: self._L.rass_index_search_grouped_keys(
+            self._h, _np_ptr(q), nq, k, d_keys, n_keys, n_groups, d_allow, n_bitmaps, words, _np_ptr(f), _np_ptr(m),
+            _np_ptr(out_s), _np_ptr(out_i), _np_ptr(out_g), _np_ptr(total)))
+        return out_s, out_i, out_g, total
+
+    def search_grouped_by_keys_device(self, d_queries_ptr: int, nq: int, k: int, d_keys_ptr: int, n_keys: int, n_groups: int,
+                                      d_out_scores_ptr: int, d_out_ids_ptr: int, d_out_groups_ptr: int, d_group_total_ptr: int,
+                                      d_status_ptr: int, d_allow_ptr: int = 0, n_bitmaps: int = 0, words_per_bitmap: int = 0,
+                                      id_base: int = 0, d_q_filter_ptr: int = 0, d_q_filter_mask_ptr: int = 0) -> None:
+        """Async, device-resident ``search_grouped_by_keys`` (``rass_index_search_grouped_keys_device``); nq <= 32.  Nothing is
+        padded: ``n_keys`` below the index's rows is refused.  ``*d_status`` as in ``search_grouped_device``."""
+        k, _, n_groups = self._check_grouped(k, 1, n_groups)
+        N.check("rass_index_search_grouped_keys_device",
+                self._L.rass_index_search_grouped_keys_device(
+                    self._h, ctypes.c_void_p(d_queries_ptr), int(nq), k, ctypes.c_void_p(d_keys_ptr), int(n_keys), n_groups,
+                    ctypes.c_void_p(d_allow_ptr or 0), int(n_bitmaps), int(words_per_bitmap),
+                    ctypes.c_void_p(d_q_filter_ptr or 0), ctypes.c_void_p(d_q_filter_mask_ptr or 0), int(id_base),
+                    ctypes.c_void_p(d_out_scores_ptr), ctypes.c_void_p(d_out_ids_ptr), ctypes.c_void_p(d_out_groups_ptr),
+                    ctypes.c_void_p(d_group_total_ptr), ctypes.c_void_p(d_status_ptr)))
+
+    def search_counts_by_keys(self, queries: np.ndarray, min_score, size: int, keys, n_groups: int, allow=None,
+                              q_filter: Optional[np.ndarray] = None, q_filter_mask: Optional[np.ndarray] = None
+                              ) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+        """``search_counts`` with the group of a row taken from a key column and, optionally, within a bitmap
+        (``rass_index_aggregate_keys``); ``keys`` / ``allow`` as in ``search_grouped_by_keys``.  A row without a group is
+        never a hit: it is in no bucket and in neither total.  Returns what ``search_counts`` returns."""
+        q = self._queries(queries)
+        nq = q.shape[0]
+        thr = self._thresholds(min_score, nq)
+        size, _, n_groups = self._check_counts(size, 1, n_groups)
+        f, m = self._filters(q_filter, q_filter_mask, nq)
+        self._check_keys(keys, allow, nq)
+        out_g = np.empty((nq, size), dtype=np.int32)
+        out_c = np.empty((nq, size), dtype=np.int64)
+        out_s = np.empty((nq, size), dtype=np.float32)
+        out_i = np.empty((nq, size), dtype=np.int64)
+        n_buckets = np.empty((nq,), dtype=np.int64)
+        total = np.empty((nq,), dtype=np.int64)
+        if nq == 0:
+            return out_g, out_c, out_s, out_i, n_buckets, total
+        fn = "rass_index_aggregate_keys"
+        self._by_keys(fn, keys, allow, lambda d_keys, n_keys, d_allow, n_bitmaps, words: self._L.rass_index_aggregate_keys(
+            self._h, _np_ptr(q), nq, _np_ptr(thr), size, d_keys, n_keys, n_groups, d_allow, n_bitmaps, words, _np_ptr(f),
+            _np_ptr(m), _np_ptr(out_g), _np_ptr(out_c), _np_ptr(out_s), _np_ptr(out_i), _np_ptr(n_buckets), _np_ptr(total)))
+        return out_g, out_c, out_s, out_i, n_buckets, total
+
+    def search_counts_by_keys_device(self, d_queries_ptr: int, nq: int, d_min_score_ptr: int, size: int, d_keys_ptr: int,
+                                     n_keys: int, n_groups: int, d_out_groups_ptr: int, d_out_counts_ptr: int,
+                                     d_out_scores_ptr: int, d_out_ids_ptr: int, d_n_buckets_ptr: int, d_total_hits_ptr: int,
+                                     d_status_ptr: int, d_allow_ptr: int = 0, n_bitmaps: int = 0, words_per_bitmap: int = 0,
+                                     id_base: int = 0, d_q_filter_ptr: int = 0, d_q_filter_mask_ptr: int = 0) -> None:
+        """Async, device-resident ``search_counts_by_keys`` (``rass_index_aggregate_keys_device``); nq <= 32.  Nothing is
+        padded.  ``*d_status`` as in ``search_counts_device``."""
+        size, _, n_groups = self._check_counts(size, 1, n_groups)
+        N.check("rass_index_aggregate_keys_device",
+                self._L.rass_index_aggregate_keys_device(
+                    self._h, ctypes.c_void_p(d_queries_ptr), int(nq), ctypes.c_void_p(d_min_score_ptr), size,
+                    ctypes.c_void_p(d_keys_ptr), int(n_keys), n_groups, ctypes.c_void_p(d_allow_ptr or 0), int(n_bitmaps),
+                    int(words_per_bitmap), ctypes.c_void_p(d_q_filter_ptr or 0), ctypes.c_void_p(d_q_filter_mask_ptr or 0),
+                    int(id_base), ctypes.c_void_p(d_out_groups_ptr), ctypes.c_void_p(d_out_counts_ptr),
+                    ctypes.c_void_p(d_out_scores_ptr), ctypes.c_void_p(d_out_ids_ptr), ctypes.c_void_p(d_n_buckets_ptr),
+                    ctypes.c_void_p(d_total_hits_ptr), ctypes.c_void_p(d_status_ptr)))
+
     # ---- allow-list search: exact top-k within a per-query row bitmap
     @property
     def allow_words(self) -> int:

@@ -99,6 +99,101 @@ def _empty(query_emb) -> bool:
     return query_emb is None or np.size(query_emb) == 0
 
 
+MAX_VALUE_SPAN = 1 << 20        # group by value on an int / date field: max - min + 1 may not exceed FlatIndex.MAX_GROUPS
+MAX_HISTOGRAM_BUCKETS = 4096    # = RASS_MAX_KEY_EDGES - 1
+CALENDAR_INTERVALS = ("day", "week", "month", "year")
+_EPOCH_ORDINAL = 719163         # datetime.date(1970, 1, 1).toordinal()
+
+
+def _day_date(day: int):
+    import datetime as _dt
+    return _dt.date.fromordinal(_EPOCH_ORDINAL + int(day))
+
+
+def histogram_edges(lo: int, hi: int, interval: Any, kind: str) -> List[int]:
+    """The ascending bucket edges of a ``histogram`` (``interval`` an int >= 1: buckets ``[m * interval, (m + 1) * interval)``,
+    as OpenSearch keys them) or a ``date_histogram`` (``"day" | "week" | "month" | "year"`` on a date field, days since
+    1970-01-01 UTC; weeks start on Monday) that cover the values ``lo .. hi``: the first edge is <= lo, the last > hi.  More
+    than 4 096 buckets, or edges outside int32, raise ``ValueError``."""
+    lo, hi = int(lo), int(hi)
+    if isinstance(interval, str):
+        if kind != "date" or interval not in CALENDAR_INTERVALS:
+            raise ValueError(f"interval must be an int >= 1, or one of {CALENDAR_INTERVALS} on a date field, not {interval!r}")
+        if interval == "day":
+            step, first = 1, lo
+        elif interval == "week":
+            step, first = 7, lo - (lo + 3) % 7      # 1970-01-01 was a Thursday: Monday = day -3
+        else:
+            a, b = _day_date(lo), _day_date(hi)
+            months = 1 if interval == "month" else 12
+            m0 = (a.year * 12 + a.month - 1) // months * months       # months since year 0 of the first bucket's first day
+            n = ((b.year * 12 + b.month - 1) - m0) // months + 1
+            if n > MAX_HISTOGRAM_BUCKETS:
+                raise ValueError(f"{n} {interval} buckets between the smallest and the largest value: at most {MAX_HISTOGRAM_BUCKETS}")
+            return [type(a)(divmod(m0 + j * months, 12)[0], divmod(m0 + j * months, 12)[1] + 1, 1).toordinal() - _EPOCH_ORDINAL
+                    for j in range(n + 1)]
+    else:
+        if isinstance(interval, bool) or not isinstance(interval, (int, np.integer)) or int(interval) < 1:
+            raise ValueError(f"interval must be an int >= 1, or one of {CALENDAR_INTERVALS} on a date field, not {interval!r}")
+        step = int(interval)
+        first = lo // step * step
+    n = (hi - first) // step + 1
+    if n > MAX_HISTOGRAM_BUCKETS:
+        raise ValueError(f"{n} buckets of {interval!r} between the smallest and the largest value: at most {MAX_HISTOGRAM_BUCKETS}")
+    if first < -(1 << 31) + 1 or first + n * step > (1 << 31) - 1:
+        raise ValueError(f"the buckets of {interval!r} over [{lo}, {hi}] reach beyond int32")
+    return [first + j * step for j in range(n + 1)]
+
+
+class _GroupBy:
+    """How one collapse / aggregation call groups its rows: by a bit field of the tag (``tag_mask``: the tag-keyed native
+    calls, as before attribute columns could group) or by a key column built per attempt (``keys(st)``)."""
+
+    def __init__(self, what: str, field: Any, st: Optional[IndexState], interval: Any = None):
+        self.field, self.interval = field, interval
+        self.tag_mask = {"patientId": TAG_PATIENT_MASK, "doc_type": TAG_DOCTYPE_MASK}.get(field) if isinstance(field, str) else None
+        self.col = self.kind = None
+        if self.tag_mask is None:
+            found = st.attrs.column(field) if st is not None and isinstance(field, str) and getattr(st, "attrs", None) else None
+            if found is None:
+                raise ValueError(f"{what} must be 'patientId', 'doc_type' or an attribute field of the index, not {field!r}")
+            self.col, self.kind = found
+        if interval is not None and self.kind not in ("int", "date"):
+            raise ValueError(f"interval needs an int or date attribute field, and {field!r} is not one")
+
+    def tag_names(self, st: IndexState) -> List[str]:
+        return (st.patients if self.field == "patientId" else st.doc_types).names()
+
+    def keys(self, st: IndexState):
+        """(device key column, n_groups, label) for the index as it is now, or None when no live row has a value; label(g) ->
+        the bucket's ``key``.  Called under ``st.lock``."""
+        index = st.index
+        if self.tag_mask is not None:          # the tag's own field: one pass over the tags on the device
+            names = self.tag_names(st)
+            return index.group_keys_from_tag(self.tag_mask), len(names) + 1, lambda g: names[g - 1] if g > 0 else None
+        if self.kind == "keyword":             # key = code, 0 = the rows without the field
+            names = st.attrs.dicts[self.field].names()
+            return index.group_keys_from_attr(self.col, base=0, missing=0), len(names) + 1, lambda g: names[g - 1] if g > 0 else None
+        lo, hi, present = index.attr_minmax(self.col)
+        if not present:                        # no live row has a value
+            if self.interval is not None:      # ... and a histogram counts only rows that have one
+                return None
+            return index.group_keys_from_attr(self.col, base=0, missing=0), 1, lambda g: None     # one group: None
+        as_key = (lambda v: v) if self.kind == "int" else (lambda v: _day_date(v).isoformat())
+        if self.interval is None:              # by value: key = value - min, the rows without the field in one more group
+            if hi - lo + 1 > MAX_VALUE_SPAN:
+                raise ValueError(f"{self.field!r} spans {hi - lo + 1} values ({lo} .. {hi}): at most {MAX_VALUE_SPAN} "
+                                 "can be grouped by value (use interval=)")
+            span = hi - lo + 1
+            if span == MAX_VALUE_SPAN:         # the table is full of values: no slot is left for the rows without the field
+                return index.group_keys_from_attr(self.col, base=lo, missing=-1), span, lambda g: as_key(lo + g)
+            return (index.group_keys_from_attr(self.col, base=lo, missing=span), span + 1,
+                    lambda g: as_key(lo + g) if g < span else None)
+        edges = histogram_edges(lo, hi, self.interval, self.kind)
+        return (index.group_keys_from_attr(self.col, missing=-1, edges=np.asarray(edges, dtype=np.int64)), len(edges) - 1,
+                lambda g: edges[g])
+
+
 class HipIndexer:
     """Exact cosine k-NN over the HBM-resident index named ``index_name``; everything that is not
     k-NN is delegated to the original ``OpenSearchIndexer`` (``_original_cls``, set by ``install``)."""
@@ -186,19 +281,23 @@ class HipIndexer:
         raise RuntimeError(f"{self.index_name}: the index was compacted during every one of {LAYOUT_ATTEMPTS} searches")
 
     def semantic_search_collapsed(self, query_emb: np.ndarray, k: int = TOP_K, collapse: str = "patientId",
-                                  filter_clause: Optional[Dict] = None, patient_id: Optional[str] = None
-                                  ) -> Tuple[List[Tuple[Dict, float]], int]:
-        """The k-NN clause under ``"collapse": {"field": collapse}``: the best chunk of every distinct ``patientId`` (or
-        ``doc_type``), the k best of those, in one pass over the index whatever k is (``FlatIndex.search_grouped``).
-        Returns ``(hits, total_groups)``: ``[(doc_dict, float(score))]`` best first in ``semantic_search``'s score units,
-        and the exact number of distinct values among the matching chunks (chunks without the field count as one value,
-        as OpenSearch collapses missing values together).  Filters as ``semantic_search``.  An empty embedding or an
-        unindexed patient gives ``([], 0)``; errors raise (this method has no counterpart in the reference to mirror)."""
-        if collapse not in ("patientId", "doc_type"):
-            raise ValueError(f"collapse must be 'patientId' or 'doc_type', not {collapse!r}")
+                                  filter_clause: Optional[Dict] = None, patient_id: Optional[str] = None,
+                                  where: Optional[Any] = None) -> Tuple[List[Tuple[Dict, float]], int]:
+        """The k-NN clause under ``"collapse": {"field": collapse}``: the best chunk of every distinct value of
+        ``collapse`` — ``patientId``, ``doc_type`` or any attribute field of the index (``config.RASS_ATTR_FIELDS``: a
+        keyword, int or date column) — the k best of those, in one pass over the index whatever k is
+        (``FlatIndex.search_grouped``; for an attribute field ``FlatIndex.search_grouped_by_keys`` over a key column built
+        from the field's column on the GPU).  Returns ``(hits, total_groups)``: ``[(doc_dict, float(score))]`` best first in
+        ``semantic_search``'s score units, and the exact number of distinct values among the matching chunks (chunks
+        without the field count as one value, as OpenSearch collapses missing values together).  An int or date field is
+        grouped by value and may span at most 1 048 576 values.  ``where``: an OpenSearch filter as
+        ``semantic_search_filtered`` takes it, compiled into a bitmap the scan honours (dim <= 1024; the whole index is
+        still streamed).  Filters as ``semantic_search``.  An empty embedding or an unindexed patient gives ``([], 0)``;
+        errors raise (this method has no counterpart in the reference to mirror)."""
+        st: Optional[IndexState] = REGISTRY.get(self.index_name, create=False)
+        by = _GroupBy("collapse", collapse, st)
         if _empty(query_emb):
             return [], 0
-        st: Optional[IndexState] = REGISTRY.get(self.index_name, create=False)
         if st is None:
             return [], 0
         prep = self._prepare(st, query_emb, k, filter_clause, patient_id, None)
@@ -208,17 +307,56 @@ class HipIndexer:
         if not hasattr(st.index, "search_grouped"):
             raise NotImplementedError(f"{self.index_name}: {type(st.index).__name__} has no grouped search "
                                       "(IVF-backed and sharded indices cannot collapse; use a flat fp32 index)")
-        group_mask = TAG_PATIENT_MASK if collapse == "patientId" else TAG_DOCTYPE_MASK
         flt = dict(q_filter=np.array([fval], dtype=np.int32), q_filter_mask=np.array([fmask], dtype=np.int32)) if fmask else {}
+        if by.tag_mask is None or where is not None:
+            self._need_keys(st, where, "grouped search")
         for _ in range(LAYOUT_ATTEMPTS):    # row ids belong to one layout of the index, as in _knn
             layout = _layout_epoch(st.index)
-            # codes run 1 .. len, 0 = none; read per attempt: a concurrent ingest may have added a value
-            n_groups = len(st.patients if collapse == "patientId" else st.doc_types) + 1
-            scores, ids, _groups, totals = st.index.search_grouped(q, k_eff, group_mask, n_groups, **flt)
+            if by.tag_mask is not None and where is None:       # the tag path, call for call
+                # codes run 1 .. len, 0 = none; read per attempt: a concurrent ingest may have added a value
+                n_groups = len(st.patients if collapse == "patientId" else st.doc_types) + 1
+                scores, ids, _groups, totals = st.index.search_grouped(q, k_eff, by.tag_mask, n_groups, **flt)
+            else:
+                built = self._keys_and_bitmap(st, by, where, layout)
+                if built is None:
+                    continue
+                keyed, allow = built
+                if keyed is None:
+                    return [], 0
+                scores, ids, _groups, totals = st.index.search_grouped_by_keys(q, k_eff, keyed[0], keyed[1], allow=allow, **flt)
             hits = self._hits(st, scores[0], ids[0], 1.0, None, layout)
             if hits is not None:
                 return hits, int(totals[0])
         raise RuntimeError(f"{self.index_name}: the index was compacted during every one of {LAYOUT_ATTEMPTS} searches")
+
+    def _need_keys(self, st: IndexState, where: Any, what: str) -> None:
+        """The refusals of a key-column call, before anything is built."""
+        index = st.index
+        if not all(hasattr(index, m) for m in ("search_grouped_by_keys", "search_counts_by_keys", "group_keys_from_attr", "group_keys_from_tag", "attr_minmax")):
+            raise NotImplementedError(f"{self.index_name}: {type(index).__name__} has no {what} over a key column "
+                                      "(IVF-backed and sharded indices cannot group by an attribute field; use a flat fp32 index)")
+        if where is not None:
+            if not hasattr(index, "allow_from_attr_clauses"):
+                raise NotImplementedError(f"{self.index_name}: {type(index).__name__} has no filtered search "
+                                          "(IVF-backed and sharded indices cannot restrict by a bitmap; use a flat fp32 index)")
+            if int(getattr(index, "dim", 0)) > 1024:
+                raise NotImplementedError(f"{self.index_name}: where= with a {what} needs dim <= 1024 (the bitmap forms of the "
+                                          "scan serve narrow rows only)")
+
+    @staticmethod
+    def _keys_and_bitmap(st: IndexState, by: "_GroupBy", where: Any, layout: int):
+        """The key column and the bitmap of one attempt, built under the state's lock and ONE layout epoch, exactly as
+        ``semantic_search_filtered`` builds its bitmap: ``((keys, n_groups, label) or None, allow or None)``; None when a
+        compaction landed first (try again)."""
+        from .attrfilter import compile_filter, run_plan
+        with st.lock:
+            if _layout_epoch(st.index) != layout:
+                return None
+            keyed = by.keys(st)
+            allow = None
+            if where is not None and keyed is not None:
+                allow = run_plan(st.index, compile_filter(where, st.attrs, st.patients, st.doc_types))
+        return keyed, allow
 
     def semantic_search_diverse(self, query_emb: np.ndarray, k: int = TOP_K, fetch_k: Optional[int] = None,
                                 lambda_mult: float = 0.5, filter_clause: Optional[Dict] = None,
@@ -253,8 +391,10 @@ class HipIndexer:
         raise RuntimeError(f"{self.index_name}: the index was compacted during every one of {LAYOUT_ATTEMPTS} searches")
 
     def semantic_aggregate(self, query_emb: np.ndarray, min_score: float, by: str = "patientId", size: int = 5,
-                           filter_clause: Optional[Dict] = None, patient_id: Optional[str] = None) -> Dict[str, Any]:
-        """A ``terms`` aggregation on ``by`` (``"patientId"`` or ``"doc_type"``) under the k-NN clause with a ``min_score``:
+                           filter_clause: Optional[Dict] = None, patient_id: Optional[str] = None,
+                           interval: Optional[Any] = None, where: Optional[Any] = None) -> Dict[str, Any]:
+        """A ``terms`` aggregation on ``by`` (``"patientId"``, ``"doc_type"`` or any attribute field of the index:
+        ``conditionCodeText``, ``resourceType``, a date) under the k-NN clause with a ``min_score``:
         how many chunks score at least ``min_score``, of how many distinct values, and the ``size`` values with the most such
         chunks, in one pass over the index (``FlatIndex.search_counts``).  ``min_score`` is in the units ``semantic_search``
         returns (``RASS_SCORE_MODE``) and is converted to a cosine once.  Returns the shape of an OpenSearch ``terms``
@@ -265,15 +405,26 @@ class HipIndexer:
              "sum_other_doc_count": total - the listed doc_counts,
              "cardinality": distinct values among the hits, "total": hits}
 
-        Filters as ``semantic_search``.  An empty embedding or an unindexed patient gives the empty aggregation with zeros;
-        errors raise (this method has no counterpart in the reference to mirror: ``aggregate_search`` ignores the query
-        text and stays with the text engine)."""
-        if by not in ("patientId", "doc_type"):
-            raise ValueError(f"by must be 'patientId' or 'doc_type', not {by!r}")
+        An attribute field goes through a key column built from its column on the GPU (``FlatIndex.search_counts_by_keys``);
+        an int or date field is grouped by value (at most 1 048 576 values between its smallest and largest).
+
+        ``interval`` (an int or date field only) makes it OpenSearch's ``histogram`` / ``date_histogram`` instead: an int
+        (units, or days on a date field), or ``"day" | "week" | "month" | "year"`` on a date field (UTC calendar, weeks from
+        Monday).  Every non-empty bucket (``min_doc_count = 1``) comes back in KEY order — ``size`` is not used —, each
+        ``{"key": lower edge (first day), "key_as_string": ISO date (date fields), "doc_count", "top_hit"}``; chunks
+        without the field are not counted; more than 4 096 buckets between the smallest and the largest value raise
+        ``ValueError``.
+
+        ``where``: an OpenSearch filter as ``semantic_search_filtered`` takes it (a date range, a ``term``), compiled into
+        a bitmap the scan honours (dim <= 1024; the whole index is still streamed).  Filters as ``semantic_search``.  An
+        empty embedding or an unindexed patient gives the empty aggregation with zeros; errors raise (this method has no
+        counterpart in the reference to mirror: ``aggregate_search`` ignores the query text and stays with the text
+        engine)."""
+        st: Optional[IndexState] = REGISTRY.get(self.index_name, create=False)
+        grp = _GroupBy("by", by, st, interval)
         empty = {"buckets": [], "sum_other_doc_count": 0, "cardinality": 0, "total": 0}
         if _empty(query_emb):
             return empty
-        st: Optional[IndexState] = REGISTRY.get(self.index_name, create=False)
         if st is None:
             return empty
         prep = self._prepare(st, query_emb, size, filter_clause, patient_id, None)
@@ -286,24 +437,42 @@ class HipIndexer:
         thr = np.array([_cos_of_score(min_score)], dtype=np.float32)
         if np.isnan(thr[0]):
             raise ValueError("min_score must not be NaN")
-        group_mask = TAG_PATIENT_MASK if by == "patientId" else TAG_DOCTYPE_MASK
         flt = dict(q_filter=np.array([fval], dtype=np.int32), q_filter_mask=np.array([fmask], dtype=np.int32)) if fmask else {}
+        if grp.tag_mask is None or where is not None:
+            self._need_keys(st, where, "aggregation")
         for _ in range(LAYOUT_ATTEMPTS):    # top_hit ids belong to one layout of the index, as in _knn
             layout = _layout_epoch(st.index)
-            # codes run 1 .. len, 0 = none; read per attempt: a concurrent ingest may have added a value
-            names = (st.patients if by == "patientId" else st.doc_types).names()
-            groups, counts, scores, ids, n_buckets, totals = st.index.search_counts(q, thr, size_eff, group_mask, len(names) + 1,
-                                                                                    **flt)
+            if grp.tag_mask is not None and where is None:      # the tag path, call for call
+                # codes run 1 .. len, 0 = none; read per attempt: a concurrent ingest may have added a value
+                names = grp.tag_names(st)
+                label = lambda g, names=names: names[g - 1] if g > 0 else None
+                groups, counts, scores, ids, n_buckets, totals = st.index.search_counts(q, thr, size_eff, grp.tag_mask,
+                                                                                        len(names) + 1, **flt)
+            else:
+                built = self._keys_and_bitmap(st, grp, where, layout)
+                if built is None:
+                    continue
+                keyed, allow = built
+                if keyed is None:
+                    return empty
+                keys, n_groups, label = keyed
+                # a histogram lists every bucket: the select is asked for all of them and the host puts them in key order
+                ask = n_groups if interval is not None else size_eff
+                groups, counts, scores, ids, n_buckets, totals = st.index.search_counts_by_keys(q, thr, ask, keys, n_groups,
+                                                                                                allow=allow, **flt)
+            listed = [(int(g), int(c), s, i) for g, c, s, i in zip(groups[0], counts[0], scores[0], ids[0]) if g >= 0]
+            if interval is not None:
+                listed.sort()
             buckets = []
-            for g, c, s, i in zip(groups[0], counts[0], scores[0], ids[0]):
-                if g < 0:
-                    break
+            for g, c, s, i in listed:
                 top = self._hits(st, [s], [i], 1.0, None, layout)
                 if top is None:
                     buckets = None
                     break
-                buckets.append({"key": names[int(g) - 1] if g > 0 else None, "doc_count": int(c),
-                                "top_hit": top[0] if top else None})
+                bucket = {"key": label(g), "doc_count": c, "top_hit": top[0] if top else None}
+                if interval is not None and grp.kind == "date":
+                    bucket["key_as_string"] = _day_date(bucket["key"]).isoformat()
+                buckets.append(bucket)
             if buckets is not None:
                 total = int(totals[0])
                 return {"buckets": buckets, "sum_other_doc_count": total - sum(b["doc_count"] for b in buckets),
