@@ -622,6 +622,15 @@ int rass_index_certify_stats(rass_index_t* idx, int64_t* queries, int64_t* certi
  * RASS_ERR_UNSUPPORTED unless the index is in mode 3. */
 int rass_index_candidates_exact_device(rass_index_t* idx, const float* d_queries, int nq, int k, const int32_t* d_q_filter,
                                        float* d_cand_scores, int64_t* d_cand_rows, float* d_tau, int32_t* d_certified);
+/* The sample floor's parity hook for a fused fp32 batch (nq > 32 device queries on an fp32 index without prefilter): the
+ * normalise launch and the sample stage exactly as rass_index_search_device_batch would run them for this nq and k, then, per
+ * query, the 32 representative rows ([nq][32] LOCAL rows, one per block of the slab's sample prefix; -1: the block has no row
+ * the query may rank) and their scores ([nq][32], the flat scan's score of that row bit for bit; -inf: no representative, or a
+ * score that is not finite).  The floor of a query is the k-th largest of its 32 scores.  Stream-ordered.
+ * RASS_ERR_UNSUPPORTED where the batch would not take that stage (small slab, ragged nq, RASS_SCAN_BATCH_SAMPLE=f32 / groups,
+ * RASS_SCAN_SAMPLE_FLOOR=0). */
+int rass_index_sample_floor_device(rass_index_t* idx, const float* d_queries, int nq, int k, const int32_t* d_q_filter,
+                                   int32_t* d_out_rows, float* d_out_scores);
 /* The candidate lists of the active prefilter mode for <= 32 device queries, BEFORE the exact re-rank: [nq][32] candidate
  * scores (bf16: fp32-accumulated dot of the bf16-rounded operands; int8: as above) and LOCAL rows, (score desc, row asc),
  * -inf / -1 past the end.  Parity hook of the integer path (tests compare it with the oracle bit for bit); stream-ordered.

@@ -161,6 +161,9 @@ struct BatchView {
     unsigned char* q_small;        // [groups][32] bf16 / int8 queries
     float* cand_scores;            // [groups][32][32]
     int64_t* cand_rows;
+    unsigned char* rep_qfrag;      // the fp32 batch's sample stage (sample_rep.hip): [groups][32][stride] bf16 query fragments,
+    unsigned char* rep_part;       // [groups][32][kMaxSampleGroups] (score, row) pairs
+    int* rep_row;                  // and the representatives [groups][32][32]
     size_t total;
     size_t part_per_group;         // elements of one group's [grid][32][k] lists
     float* group_sample(int g) const { return sample_best + (int64_t)g * 32 * rass::kMaxSampleGroups; }
@@ -431,7 +434,8 @@ int index_refresh_copies(rass_index* idx, int64_t first, int64_t n, hipStream_t 
 int scan_xcd_skew(int nq, int grid, int n_cus);   // ScanArgs::xcd_skew of a launch; RASS_SCAN_XCD_SKEW, read once
 int64_t scan_sample_floor_min_share();            // RASS_SCAN_SAMPLE_FLOOR, read per call
 bool i8_sample_floor(int64_t rows, int grid);     // RASS_I8_SAMPLE_FLOOR, read per call
-bool scan_batch_one_sample();                     // RASS_SCAN_BATCH_SAMPLE, read per call
+enum { kBatchSampleGroups = 0, kBatchSampleF32 = 1, kBatchSampleRep = 2 };
+int scan_batch_sample_mode();                   // RASS_SCAN_BATCH_SAMPLE, read per call: a kBatchSample* value
 bool scan_batch_pair();                           // RASS_SCAN_BATCH_PAIR, read once
 bool ivf_batch_one_launch();                      // RASS_IVF_BATCH_FINE, read per call
 

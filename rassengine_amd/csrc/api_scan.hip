@@ -60,10 +60,14 @@ bool i8_sample_floor(int64_t rows, int grid) {
     return grid <= rass::kMaxSampleGroups && rows >= (int64_t)(force ? 2 : 8) * 64 * grid;
 }
 
-// RASS_SCAN_BATCH_SAMPLE=groups: the fused fp32 batch samples group by group instead of in one launch (the A/B).  Read per call.
-bool scan_batch_one_sample() {
+// How the fused fp32 batch samples.  Default: representatives chosen by bf16 MFMAs and scored exactly (sample_rep.hip);
+// RASS_SCAN_BATCH_SAMPLE=f32: the one-launch fp32 sample pass (kFlatSampleGroups) it replaced; =groups: group by group (the
+// A/Bs; results do not depend on it).  Read per call.
+int scan_batch_sample_mode() {
     const char* e = getenv("RASS_SCAN_BATCH_SAMPLE");
-    return !(e && e[0] == 'g');
+    if (e && e[0] == 'g') return kBatchSampleGroups;
+    if (e && e[0] == 'f') return kBatchSampleF32;
+    return kBatchSampleRep;
 }
 
 // RASS_SCAN_BATCH_PAIR=0: the fused fp32 batch launches one scan per group instead of one per two full groups (the A/B).  Read once.
@@ -114,6 +118,9 @@ BatchView batch_layout(unsigned char* base, int groups, int grid, int k, int64_t
     L.q_small = candidates ? c.take<unsigned char>((size_t)groups * 32 * kMaxStride * 2) : nullptr;
     L.cand_scores = candidates ? c.take<float>((size_t)groups * 32 * k * sizeof(float)) : nullptr;
     L.cand_rows = candidates ? c.take<int64_t>((size_t)groups * 32 * k * sizeof(int64_t)) : nullptr;
+    L.rep_qfrag = candidates ? nullptr : c.take<unsigned char>((size_t)groups * 32 * stride * 2);
+    L.rep_part = candidates ? nullptr : c.take<unsigned char>((size_t)groups * 32 * rass::kMaxSampleGroups * 8);
+    L.rep_row = candidates ? nullptr : c.take<int>((size_t)groups * 32 * 32 * sizeof(int));
     L.total = c.off;
     return L;
 }

@@ -97,6 +97,27 @@ FlatRequest batch_group(const rass_index* idx, const FlatRequest& r, int g, int6
     return q;
 }
 
+// How a fused fp32 batch finds its sample floors: nothing (small slab, RASS_SCAN_SAMPLE_FLOOR=0), group by group, or for
+// all groups at once when the batch has several full groups — representatives chosen by bf16 MFMAs and scored exactly
+// (sample_rep.hip: `rep`) or, where that stage has no kernel (a grid that is no multiple of 32) and under
+// RASS_SCAN_BATCH_SAMPLE=f32, one fp32 sample launch (kFlatSampleGroups).  Either way the floor is the k-th largest of 32
+// scores of different rows of the slab's first 64 * grid; results do not depend on it (rows tying with it are kept).
+struct BatchSamplePlan {
+    int grid;
+    bool sample, one_sample, rep;
+};
+BatchSamplePlan batch_sample_plan(const rass_engine* eng, int64_t rows, int64_t stride, int nq, int k) {
+    BatchSamplePlan p;
+    p.grid = scan_grid((rows + 31) / 32, k, eng->n_cus);
+    const int groups = (nq + RASS_MAX_QBATCH - 1) / RASS_MAX_QBATCH;
+    const int64_t min_share = scan_sample_floor_min_share();
+    const int mode = scan_batch_sample_mode();
+    p.sample = min_share > 0 && p.grid <= rass::kMaxSampleGroups && rows >= min_share * 64 * p.grid;
+    p.one_sample = p.sample && groups >= 2 && nq % 32 == 0 && mode != kBatchSampleGroups && p.grid >= 32;
+    p.rep = p.one_sample && mode == kBatchSampleRep && rass::sample_rep_supported(stride, p.grid);
+    return p;
+}
+
 // The fused batch of rass_index_search_device_batch on an fp32 flat index: the per-group steps of scan_launch, but
 // ONE normalise launch and ONE merge launch for the whole batch, and the groups' sample passes back to back (their
 // 64 * grid rows stay in the Infinity Cache between them) ahead of the big scans.  Per 32 queries the serial tail
@@ -122,7 +143,8 @@ int scan_launch_batch(rass_index* idx, const FlatRequest& r, int64_t gs, int64_t
         }
         return RASS_OK;
     }
-    const int grid = scan_grid((rows + 31) / 32, k, eng->n_cus);
+    const BatchSamplePlan plan = batch_sample_plan(eng, rows, stride, nq, k);
+    const int grid = plan.grid;
     int rc = grow_block(&eng->d_batch, &eng->batch_bytes, batch_layout(nullptr, groups, grid, k, stride).total, st);
     if (rc != RASS_OK) return rc;
     const BatchView L = batch_layout(eng->d_batch, groups, grid, k, stride);
@@ -146,15 +168,15 @@ int scan_launch_batch(rass_index* idx, const FlatRequest& r, int64_t gs, int64_t
         return a;
     };
     const int64_t sample_rows = (int64_t)64 * grid;
-    const int64_t min_share = scan_sample_floor_min_share();
-    const bool sample = min_share > 0 && grid <= rass::kMaxSampleGroups && rows >= min_share * sample_rows;
-    // The sample passes: ONE launch for all groups (kFlatSampleGroups, 32 workgroups of 16 tiles per group: the same
-    // 64 * grid sample rows, the floor = the k-th largest of 32 block maxima instead of `grid` of them) when the batch has
-    // several full groups; group by group otherwise (RASS_SCAN_BATCH_SAMPLE=groups: the A/B).  Results do not depend on the
-    // floor (rows tying with it are kept).
-    const bool one_sample = sample && groups >= 2 && nq % 32 == 0 && scan_batch_one_sample() && grid >= 32;
+    const bool sample = plan.sample, one_sample = plan.one_sample;
+    // The sample stage (batch_sample_plan): for all groups at once — the representatives' stage, or ONE fp32 launch
+    // (kFlatSampleGroups, 32 workgroups of 16 tiles per group: the floor = the k-th largest of 32 block maxima instead of
+    // `grid` of them) — when the batch has several full groups; group by group otherwise.  Outside the timing brackets.
     const int sample_wgs = one_sample ? 32 : grid;
-    if (one_sample) {   // not sample_prelaunch: 32 workgroups per group share the 64 * grid sample rows
+    if (plan.rep) {
+        HIP_TRY(rass::launch_sample_rep(iv.corpus, iv.row_tag, stride, grid, L.q_padded, r.q_filter, nq, L.rep_qfrag, L.rep_part,
+                                        L.rep_row, L.sample_best, st));
+    } else if (one_sample) {   // not sample_prelaunch: 32 workgroups per group share the 64 * grid sample rows
         rass::ScanArgs s = group_args(0);
         s.n_rows = (int)sample_rows;
         s.xcd_skew = 0;
@@ -198,6 +220,32 @@ int scan_launch_batch(rass_index* idx, const FlatRequest& r, int64_t gs, int64_t
     }
     const rass::MergeGroups mg = dense_groups(nq, (int64_t)L.part_per_group, gs, gi);
     HIP_TRY(rass::launch_merge_topk(L.part_scores, L.part_ids, grid, nq, k, r.out_scores, r.out_ids, st, iv.id_map, 0, 0, &mg));
+    return RASS_OK;
+}
+
+// The parity hook of the batch's sample stage (rass_index_sample_floor_device): the normalise launch and the stage as
+// scan_launch_batch enqueues them for this index, batch and k, then the representatives and their scores copied out.
+int sample_floor_hook(rass_index* idx, const float* d_queries, int nq, int k, const int32_t* d_q_filter, int32_t* d_rows,
+                      float* d_scores) {
+    rass_engine* eng = idx->eng;
+    hipStream_t st = eng->stream;
+    const IndexView iv = index_view(idx, d_q_filter != nullptr, 0);
+    const int64_t stride = idx->stride;
+    if (idx->dtype != RASS_F32 || idx->prefilter || nq <= RASS_MAX_QBATCH || iv.rows <= 0 || iv.rows > kMaxScanRows ||
+        stride > kNarrowStride || !rass::scan_supported_stride(stride))
+        return fail(RASS_ERR_UNSUPPORTED, "not a fused fp32 batch");
+    const BatchSamplePlan plan = batch_sample_plan(eng, iv.rows, stride, nq, k);
+    if (!plan.rep) return fail(RASS_ERR_UNSUPPORTED, "this batch does not take the representatives' sample stage");
+    const int groups = nq / RASS_MAX_QBATCH;
+    int rc = grow_block(&eng->d_batch, &eng->batch_bytes, batch_layout(nullptr, groups, plan.grid, k, stride).total, st);
+    if (rc != RASS_OK) return rc;
+    const BatchView L = batch_layout(eng->d_batch, groups, plan.grid, k, stride);
+    HIP_TRY(rass::launch_normalize_rows_f32(d_queries, idx->dim, L.q_padded, stride, nq, idx->dim, st, nq));
+    HIP_TRY(rass::launch_sample_rep(iv.corpus, iv.row_tag, stride, plan.grid, L.q_padded, d_q_filter, nq, L.rep_qfrag, L.rep_part,
+                                    L.rep_row, L.sample_best, st));
+    HIP_TRY(hipMemcpyAsync(d_rows, L.rep_row, (size_t)nq * 32 * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
+    HIP_TRY(hipMemcpy2DAsync(d_scores, 32 * sizeof(float), L.sample_best, rass::kMaxSampleGroups * sizeof(float), 32 * sizeof(float),
+                             (size_t)nq, hipMemcpyDeviceToDevice, st));
     return RASS_OK;
 }
 
@@ -470,6 +518,18 @@ int rass_index_candidates_exact_device(rass_index_t* idx, const float* d_queries
     r.row_tag = index_view(idx, d_q_filter != nullptr).row_tag;
     r.cand_scores = d_cand_scores, r.cand_rows = d_cand_rows, r.tau = d_tau, r.certified = d_certified;
     return cert_launch(idx, r);
+}
+
+int rass_index_sample_floor_device(rass_index_t* idx, const float* d_queries, int nq, int k, const int32_t* d_q_filter,
+                                   int32_t* d_out_rows, float* d_out_scores) {
+    if (!idx || !d_queries || !d_out_rows || !d_out_scores) return fail(RASS_ERR_INVALID, "NULL argument");
+    if (nq < 1 || nq > RASS_MAX_DEVICE_BATCH) return fail(RASS_ERR_INVALID, "nq must be in [1, RASS_MAX_DEVICE_BATCH]");
+    if (int rc = check_k(k)) return rc;
+    rass_engine* eng = idx->eng;
+    std::lock_guard<std::mutex> lk(eng->mu);
+    int rc = set_device(eng);
+    if (rc != RASS_OK) return rc;
+    return sample_floor_hook(idx, d_queries, nq, k, d_q_filter, d_out_rows, d_out_scores);
 }
 
 int rass_index_search_ex(rass_index_t* idx, const float* queries, int nq, int k, const int32_t* q_filter,

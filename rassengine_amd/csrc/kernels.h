@@ -296,6 +296,15 @@ hipError_t launch_convert_tile16_bf16(const float* src, void* dst, int64_t strid
 hipError_t launch_unpack_rows_tile16b(const void* slab, int64_t stride, int64_t first_row, int64_t n, int dim,
                                       float* out, int64_t out_stride, hipStream_t stream);
 hipError_t launch_queries_to_bf16(const float* src, void* dst, int64_t n, hipStream_t stream);
+// The sample floor of a fused fp32 batch, chosen by bf16 MFMAs and scored exactly (sample_rep.hip): the slab's first 64 * grid
+// rows, all present, in 32 blocks of 2 * grid; per query and block the eligible row (tag != -1, q_filter < 0 or == tag) with
+// the largest bf16 score, lowest row on ties, goes to rep_row[nq][32] (-1: none) and its flat-kernel score to
+// sample_best[nq / 32][32][kMaxSampleGroups], entries 0..31 (-inf: none, or not finite).  nq: a multiple of 32; q_padded
+// [nq][stride] normalised; scratch: q_frag nq * stride * 2 bytes, rep_part nq * grid * 8 bytes.  Three launches.
+bool sample_rep_supported(int64_t stride, int grid);   // stride 128 * {1..8}, grid a multiple of 32 up to kMaxSampleGroups
+hipError_t launch_sample_rep(const float* slab, const int32_t* row_tag, int64_t stride, int grid, const float* q_padded,
+                             const int32_t* q_filter, int nq, void* q_frag, void* rep_part, int* rep_row, float* sample_best,
+                             hipStream_t stream);
 // out_*_group_stride (elements; 0 = contiguous [nq][k]): query q's results go to out + (q / 32) * group_stride + (q % 32) * k
 hipError_t launch_rerank_f32(const float* slab, int64_t stride, const float* q_padded, const int64_t* cand_rows, int nq,
                              int n_cand, int k, int64_t id_base, float* out_scores, int64_t* out_ids,

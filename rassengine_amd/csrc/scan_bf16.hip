@@ -23,6 +23,7 @@
 
 #include "kernels.h"
 #include "scan_core.h"
+#include "exact_score.h"
 
 namespace rass {
 
@@ -416,28 +417,7 @@ __device__ __forceinline__ void rerank_f32_body(const float* __restrict__ slab, 
     const int c = threadIdx.x >> 3, w = threadIdx.x & 7;
     const int64_t row = c < n_cand ? cand_rows[(int64_t)q * n_cand + c] : -1;
     float acc = 0.f;
-    if (row >= 0) {
-#pragma unroll
-        for (int half = 0; half < HALVES; ++half) {
-            const float* xb = slab + (row >> 4) * 16 * stride + (int64_t)(w * HALVES * CH + half * CH) * 256 + (int)(row & 15) * 4;
-            const float* qv = q_padded + (int64_t)q * stride + (w * HALVES * CH + half * CH) * 16;
-            f32x4 xv[CH][4];
-#pragma unroll
-            for (int j = 0; j < CH; ++j)
-#pragma unroll
-                for (int g = 0; g < 4; ++g) xv[j][g] = *reinterpret_cast<const f32x4*>(xb + j * 256 + g * 64);
-#pragma unroll
-            for (int j = 0; j < CH; ++j) {
-                f32x4 qq[4];
-#pragma unroll
-                for (int g = 0; g < 4; ++g) qq[g] = *reinterpret_cast<const f32x4*>(qv + j * 16 + 4 * g);
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-#pragma unroll
-                    for (int g = 0; g < 4; ++g) acc = fmaf(xv[j][g][i], qq[g][i], acc);
-            }
-        }
-    }
+    if (row >= 0) acc = flat_score_slice<CH, HALVES>(slab, stride, q_padded, q, row, w);
     part[c][w] = acc;
     __syncthreads();
     if (threadIdx.x < 32) {

@@ -334,6 +334,27 @@ class FlatIndex:
         self.engine.synchronize()
         return s, r, tau, cert
 
+    def sample_floor_device(self, d_queries, k: int, q_filter=None):
+        """The sample floor's parity hook for a fused fp32 batch (more than 32 queries on the device, a torch CUDA fp32 tensor
+        [nq, dim]): (representative LOCAL rows i32 [nq, 32], their flat-scan scores f32 [nq, 32]) as torch tensors; -1 / -inf
+        where a block of the sample has no row the query may rank (include/rass_engine.h)."""
+        import torch
+        nq = int(d_queries.shape[0])
+        assert d_queries.is_cuda and d_queries.dtype == torch.float32 and d_queries.is_contiguous() and d_queries.shape[1] == self.dim
+        dev = d_queries.device
+        rows = torch.empty((nq, 32), dtype=torch.int32, device=dev)
+        scores = torch.empty((nq, 32), dtype=torch.float32, device=dev)
+        f = None
+        if q_filter is not None:
+            f = torch.as_tensor(np.ascontiguousarray(q_filter, dtype=np.int32)).to(dev)
+        torch.cuda.current_stream().synchronize()     # the engine works on its own stream
+        N.check("rass_index_sample_floor_device",
+                self._L.rass_index_sample_floor_device(self._h, ctypes.c_void_p(d_queries.data_ptr()), nq, int(k),
+                                                       ctypes.c_void_p(f.data_ptr()) if f is not None else None,
+                                                       ctypes.c_void_p(rows.data_ptr()), ctypes.c_void_p(scores.data_ptr())))
+        self.engine.synchronize()
+        return rows, scores
+
     def candidates_device(self, d_queries, q_filter=None):
         """The active prefilter mode's candidate lists BEFORE the exact re-rank, for <= 32 queries on the device (a torch
         CUDA fp32 tensor [nq, dim]): (scores f32 [nq, 32], LOCAL rows i64 [nq, 32]) as torch tensors.  A parity hook: the
