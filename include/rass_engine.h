@@ -362,7 +362,8 @@ int rass_index_search_grouped_device(rass_index_t* idx, const float* d_queries, 
  * 1 <= k <= RASS_MAX_K_MULTIPASS (k > RASS_MAX_K in passes of RASS_MAX_K under the continuation bound, over the same work
  * list); 0 <= nq <= RASS_MAX_DEVICE_BATCH.  Outside those, n_bitmaps neither 1 nor nq, or words_per_bitmap too small:
  * RASS_ERR_INVALID.  fp32 indices with dim <= 1024; a bf16 index or a wide-row index answers RASS_ERR_UNSUPPORTED.  The
- * prefilter mode of the index is ignored: an allowed search always runs the exact fp32 scan.  IVF, cross-index batches
+ * prefilter mode of the index is ignored: an allowed search always runs the exact fp32 scan.  (An IVF over the index takes
+ * the same bitmaps in rass_ivf_search_allowed_delta.)  Cross-index batches
  * (rass_index_search_multi), the sharded multi-GPU front, the 64-query pair kernel and the range search have no allow-list
  * form; the grouped search and the aggregation take a bitmap in their key-column forms (rass_index_search_grouped_keys,
  * rass_index_aggregate_keys), which stream every tile.
@@ -394,6 +395,11 @@ int rass_index_allow_from_tag_values(rass_index_t* idx, const int32_t* values, i
  * the tile that exist) / out_mask (bit q set iff query q has a bit set in the tile).  Synchronises. */
 int rass_index_allow_plan(rass_index_t* idx, const uint32_t* d_allow, int n_bitmaps, int64_t words_per_bitmap, int nq,
                           int32_t* out_tile, int32_t* out_rows, uint32_t* out_mask, int64_t capacity, int64_t* out_n);
+/* out_counts[b] (HOST int64, 1 <= n_bitmaps <= RASS_MAX_DEVICE_BATCH of them) = the bits bitmap b has set below the index's
+ * row count: how many rows it names, tombstoned ones included — what a caller weighs an exact allowed search against an IVF
+ * probe within the bitmap by (rass_ivf_search_allowed_delta).  d_allow as in rass_index_search_allowed_device.  Synchronises. */
+int rass_index_allow_count(rass_index_t* idx, const uint32_t* d_allow, int n_bitmaps, int64_t words_per_bitmap,
+                           int64_t* out_counts);
 
 /* ATTRIBUTE COLUMNS: up to RASS_MAX_ATTRS typed per-row fields next to the tag — a keyword's dictionary code, an integer, a
  * date as days since 1970-01-01 — for the stored-field filters OpenSearch takes next to a k-NN clause (`term`, `terms`,
@@ -860,6 +866,48 @@ int rass_ivf_search_delta_device(rass_ivf_t* ivf, rass_index_t* src,
                                  const float* d_queries, int nq, int k, int nprobe,
                                  const int32_t* d_q_filter, const int32_t* d_q_filter_mask,
                                  float* d_out_scores, int64_t* d_out_ids);
+
+/* ---- The IVF probe WITHIN A ROW BITMAP: filtered k-NN that stays in the IVF.
+ * rass_index_search_allowed streams every 32-row tile of the source in which a bitmap has a bit: cheap under a selective
+ * filter, the whole slab under a broad one (a doc_type term, a year of dates, a must_not).  The reference's index filters
+ * inside its approximate walk (OpenSearch k-NN with `filter`, app/main.py:563-572), choosing "exact over the filtered set" or
+ * "ANN restricted to the set" by the size of the set; this is the second half.
+ *
+ * rass_ivf_search_allowed_delta[_device]: per query the exact top-k over ((the rows of its nprobe best lists) U (source rows
+ * >= covered)) AND (the rows its bitmap allows), ties (score desc, source ordinal asc); ids = source ordinals, or the source
+ * index's caller-assigned ids.  `allow`, n_bitmaps and words_per_bitmap as rass_index_search_allowed: uint32 words over SOURCE
+ * row ordinals, one bitmap per query or one shared, words_per_bitmap >= ceil(rows / 32) of the source now; bits of tombstoned
+ * rows, bits at or past the row count and surplus words allow nothing.  `q_filter` / `q_filter_mask` as rass_index_search_ex.
+ * Scores are the flat scan's: with nprobe >= nlist the answer equals rass_index_search_allowed on the source bit for bit; at
+ * any nprobe it equals rass_index_search_allowed with the bitmap restricted to the probed lists' rows and the delta.
+ * Per launch group of RASS_MAX_QBATCH queries: the coarse stage and the plan of every probe; a kernel that reads, for every
+ * planned tile, the bits of the source rows behind it (the slab is a permutation of the source) into slab-order words,
+ * narrows each tile's query mask to the queries that still have a row in it and drops the tiles nobody has (order kept);
+ * the allow-list scan over the slab on that work list; where the source holds rows behind `covered`, the allow-list scan
+ * of those; the merge.  The words live in a workspace of the IVF ([32][tiles] uint32, allocated by the first such search).
+ * *scanned_rows (host form; may be NULL) = the rows of the probe tiles kept + the rows of the delta tiles planned, summed
+ * over the launch groups; *d_scanned_rows (device form; may be NULL) the same as one device int64.
+ * 0 <= nq <= RASS_MAX_DEVICE_BATCH, group after group: the one-launch batch of rass_ivf_search_device_batch has no bitmap
+ * form.  RASS_ERR_UNSUPPORTED: a bf16 or int8 slab (their scans have no bitmap mode), k > RASS_MAX_K (one pass, no
+ * continuation: search the source index), dim > 1024.  RASS_ERR_INVALID: k or nprobe < 1, n_bitmaps neither 1 nor nq,
+ * words_per_bitmap too small, a source compacted since the build.  Every refusal leaves both objects usable.
+ * The device form is stream-ordered and synchronises nothing.
+ *
+ * rass_ivf_probe_lists: the coarse stage alone — out_list_ids (HOST) [nq][nprobe] int64, query q's nprobe best lists, best
+ * first (centroid score desc, list id asc), -1 past min(nprobe, nlist).  1 <= nprobe <= RASS_MAX_K (deeper probes pick
+ * their lists by a score threshold and keep no ranked list): RASS_ERR_UNSUPPORTED above.  For routing and for explaining a
+ * probe: these are exactly the lists rass_ivf_search* and rass_ivf_search_allowed_delta probe at that nprobe. */
+int rass_ivf_search_allowed_delta(rass_ivf_t* ivf, rass_index_t* src, const float* queries,
+                                  int nq, int k, int nprobe,
+                                  const uint32_t* allow, int n_bitmaps, int64_t words_per_bitmap,
+                                  const int32_t* q_filter, const int32_t* q_filter_mask,
+                                  float* out_scores, int64_t* out_ids, int64_t* scanned_rows);
+int rass_ivf_search_allowed_delta_device(rass_ivf_t* ivf, rass_index_t* src, const float* d_queries,
+                                         int nq, int k, int nprobe,
+                                         const uint32_t* d_allow, int n_bitmaps, int64_t words_per_bitmap,
+                                         const int32_t* d_q_filter, const int32_t* d_q_filter_mask,
+                                         float* d_out_scores, int64_t* d_out_ids, int64_t* d_scanned_rows);
+int rass_ivf_probe_lists(rass_ivf_t* ivf, const float* queries, int nq, int nprobe, int64_t* out_list_ids);
 
 /* ---- IVF builds whose list plan runs on the GPU, and an IVF extended without retraining.
  * The list plan is the step between "every row has a list" and "the slab is filled": list lengths, tile-aligned

@@ -60,6 +60,10 @@ try:
     RASS_IVF_ABSORB_FRACTION = float(os.getenv("RASS_IVF_ABSORB_FRACTION", "0"))
 except ValueError:
     RASS_IVF_ABSORB_FRACTION = 0.0
+# RASS_IVF_ALLOW: 1 = an index with an fp32 IVF answers its bitmap-filtered searches (search_allowed: `where=`, `within`) by
+# probing the IVF within the bitmap where the byte rule of ivf.IvfPolicy.allow_route says that is cheaper than the exact
+# allow scan; anything else (the default: 0) = every filtered search is the exact allow scan over the flat index, as before
+RASS_IVF_ALLOW = os.getenv("RASS_IVF_ALLOW", "0").strip() == "1"
 # Compaction of tombstoned rows (docstore.IndexState.compact, rass_index_compact): an `_id` overwrite appends the new row and
 # tombstones the old one, whose 4 KiB every later scan still streams.  RASS_COMPACT_FRACTION: 0 = never (the default);
 # > 0: add_documents compacts the index once its tombstones exceed that fraction of its rows and it holds at least

@@ -141,6 +141,21 @@ __global__ void allow_store_kernel(const float* __restrict__ scores, const int64
     }
 }
 
+// counts[b] += the set bits of bitmap b below n_rows (blockIdx.y = b; the caller zeroes counts).  One atomic per wave.
+__global__ __launch_bounds__(kAllowThreads) void allow_count_kernel(const uint32_t* __restrict__ allow, int64_t q_stride, int64_t n_rows,
+                                                                    unsigned long long* __restrict__ counts) {
+    const int64_t n_words = (n_rows + 31) / 32;
+    const uint32_t* bits = allow + (int64_t)blockIdx.y * q_stride;
+    unsigned long long c = 0;
+    for (int64_t w = (int64_t)blockIdx.x * kAllowThreads + threadIdx.x; w < n_words; w += (int64_t)gridDim.x * kAllowThreads) {
+        const int64_t rows_here = n_rows - w * 32;
+        const uint32_t valid = rows_here >= 32 ? 0xffffffffu : ((1u << rows_here) - 1u);   // the last word's bits past n_rows do not count
+        c += (unsigned long long)__popc(bits[w] & valid);
+    }
+    for (int off = 32; off > 0; off >>= 1) c += __shfl_xor(c, off, 64);
+    if ((threadIdx.x & 63) == 0 && c != 0) atomicAdd(&counts[blockIdx.y], c);
+}
+
 inline int plan_blocks(int64_t n_rows) { return (int)(((n_rows + 31) / 32 + kAllowThreads - 1) / kAllowThreads); }
 
 }  // namespace
@@ -186,6 +201,18 @@ hipError_t launch_allow_plan(const uint32_t* allow, int64_t q_stride, int nq, in
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(allow_plan_place_kernel, dim3(blocks), dim3(kAllowThreads), 0, stream, tile_mask, block_count, n_rows, n_tiles,
                        work_tile, work_rows, work_mask, n_work);
+    return hipGetLastError();
+}
+
+hipError_t launch_allow_count(const uint32_t* allow, int64_t q_stride, int n_bitmaps, int64_t n_rows, int64_t* counts, hipStream_t stream) {
+    if (n_bitmaps < 1 || n_bitmaps > 65535 || n_rows < 0 || q_stride < 0 || !counts) return hipErrorInvalidValue;
+    hipError_t e = hipMemsetAsync(counts, 0, (size_t)n_bitmaps * sizeof(int64_t), stream);
+    if (e != hipSuccess || n_rows == 0) return e;
+    if (!allow) return hipErrorInvalidValue;
+    const int64_t n_words = (n_rows + 31) / 32;
+    const int grid = (int)std::min<int64_t>((n_words + kAllowThreads - 1) / kAllowThreads, 1024);
+    hipLaunchKernelGGL(allow_count_kernel, dim3(grid, n_bitmaps), dim3(kAllowThreads), 0, stream, allow, q_stride, n_rows,
+                       reinterpret_cast<unsigned long long*>(counts));
     return hipGetLastError();
 }
 

@@ -1,23 +1,14 @@
 // api_allow.hip — the C ABI of include/rass_engine.h: the allow-list search rass_index_search_allowed(_device) (exact
-// top-k within a per-query row bitmap), the bitmap builders rass_index_allow_from_rows / _from_tag_values and the plan hook
-// rass_index_allow_plan.  Host-side C++ only: the kernels are scan_topk.hip (ScanMode kAllow) and allow.hip.  The objects
+// top-k within a per-query row bitmap), the bitmap builders rass_index_allow_from_rows / _from_tag_values, the plan hook
+// rass_index_allow_plan and a bitmap's popcount rass_index_allow_count.  Host-side C++ only: the kernels are scan_topk.hip (ScanMode kAllow) and allow.hip.  The objects
 // and the threading rules: api_internal.h.
 
 #include "api_internal.h"
 
 namespace rass {
 namespace host {
-namespace {
 
-// The work list of one launch group and the plan's workspace (eng->d_allow), sized by the index's tiles.
-struct AllowView {
-    int32_t* work_tile;
-    int32_t* work_rows;
-    uint32_t* work_mask;
-    int32_t* n_work;
-    unsigned char* plan_ws;
-    size_t total;
-};
+// The work list of one launch group and the plan's workspace (eng->d_allow), sized by the index's tiles (AllowView: api_internal.h).
 AllowView allow_layout(unsigned char* base, int64_t rows) {
     Carver c{base};
     AllowView L;
@@ -30,6 +21,15 @@ AllowView allow_layout(unsigned char* base, int64_t rows) {
     L.total = c.off;
     return L;
 }
+
+int check_words(int64_t rows, int64_t words) {
+    if (words < (rows + 31) / 32)
+        return fail(RASS_ERR_INVALID, "words_per_bitmap (" + std::to_string(words) + ") is smaller than ceil(rows / 32) = " +
+                                          std::to_string((rows + 31) / 32));
+    return RASS_OK;
+}
+
+namespace {
 
 // One launch group (<= 32 queries) of an allowed search: normalise -> plan -> per pass of <= 32 hits: the allow scan over the
 // work list, merge, store (which also leaves the next pass's continuation bound).  Always the exact fp32 scan: the prefilter
@@ -48,13 +48,6 @@ struct AllowRequest {
     float* out_scores = nullptr;        // [nq][k]
     int64_t* out_ids = nullptr;
 };
-
-int check_words(int64_t rows, int64_t words) {
-    if (words < (rows + 31) / 32)
-        return fail(RASS_ERR_INVALID, "words_per_bitmap (" + std::to_string(words) + ") is smaller than ceil(rows / 32) = " +
-                                          std::to_string((rows + 31) / 32));
-    return RASS_OK;
-}
 
 int allow_device_group(rass_index* idx, const AllowRequest& r) {
     rass_engine* eng = idx->eng;
@@ -293,6 +286,26 @@ int rass_index_allow_plan(rass_index_t* idx, const uint32_t* d_allow, int n_bitm
         HIP_TRY(hipMemcpyAsync(out_mask, W.work_mask, take * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
     }
+    return RASS_OK;
+}
+
+int rass_index_allow_count(rass_index_t* idx, const uint32_t* d_allow, int n_bitmaps, int64_t words_per_bitmap, int64_t* out_counts) {
+    if (!idx || !d_allow || !out_counts) return fail(RASS_ERR_INVALID, "NULL argument");
+    if (n_bitmaps < 1 || n_bitmaps > RASS_MAX_DEVICE_BATCH) return fail(RASS_ERR_INVALID, "n_bitmaps must be in [1, RASS_MAX_DEVICE_BATCH]");
+    if (words_per_bitmap < 0) return fail(RASS_ERR_INVALID, "words_per_bitmap is negative");
+    rass_engine* eng = idx->eng;
+    std::lock_guard<std::mutex> lk(eng->mu);
+    int rc = set_device(eng);
+    if (rc != RASS_OK) return rc;
+    hipStream_t st = eng->stream;
+    const int64_t n_rows = idx->rows.load(std::memory_order_acquire);
+    if ((rc = check_words(n_rows, words_per_bitmap)) != RASS_OK) return rc;
+    rc = grow_block(&eng->d_allow_io, &eng->allow_io_bytes, (size_t)n_bitmaps * sizeof(int64_t), st);
+    if (rc != RASS_OK) return rc;
+    int64_t* d_counts = reinterpret_cast<int64_t*>(eng->d_allow_io);
+    HIP_TRY(rass::launch_allow_count(d_allow, words_per_bitmap, n_bitmaps, n_rows, d_counts, st));
+    HIP_TRY(hipMemcpyAsync(out_counts, d_counts, (size_t)n_bitmaps * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
     return RASS_OK;
 }
 

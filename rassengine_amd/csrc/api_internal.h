@@ -11,7 +11,8 @@
 //                    the grouped (collapsed) search, the terms aggregation; their shared device-group driver
 //   api_ivf.hip      IVF: the host-planned and the device-planned build on one build tail, persistence over one section
 //                    list, the probe and the batch on one fine scan, the delta, the host API (host_groups)
-//   api_allow.hip    the allow-list search (top-k within a per-query row bitmap), its bitmap builders and its plan
+//   api_ivf_allow.hip  the IVF probe within a row bitmap (probe plan -> slab-order bitmap words -> the allow-list scan), the probed lists
+//   api_allow.hip    the allow-list search (top-k within a per-query row bitmap), its bitmap builders, its plan, a bitmap's popcount
 //   api_keys.hip     the key columns built from the attribute columns (what the grouped search and the aggregation group by)
 //   api_attr.hip     the attribute columns of a flat index and the predicate builder that turns clauses over them into bitmaps
 //   api_mmr.hip      the diversified (MMR) search and the Gram matrices of row lists
@@ -419,6 +420,10 @@ struct rass_ivf {
     int64_t* d_pair_ids = nullptr;
     unsigned char* d_batch = nullptr; // rass_ivf_search_device_batch: queries, coarse / fine lists and work lists of <= 32 groups
     size_t batch_bytes = 0;
+    // the probe within a row bitmap (api_ivf_allow.hip): the slab-order words [32][total_tiles], the compacted work list and
+    // the compaction's block counts of one launch group (IvfAllowView); grown on first use, used under eng->mu in stream order
+    unsigned char* d_allow_ws = nullptr;
+    size_t allow_ws_bytes = 0;
 };
 
 namespace rass {
@@ -638,6 +643,25 @@ int host_groups(rass_index* idx, const float* queries, int nq, const int32_t* q_
 // prefilter mode (the overflow fallback of the range search, whose answer may not depend on a candidate scan).
 int search_ex_once(rass_index* idx, const float* queries, int nq, int k, const int32_t* q_filter, const int32_t* q_filter_mask,
                    float* out_scores, int64_t* out_ids, bool exact = false);
+
+// ---- what the probe within a row bitmap (api_ivf_allow.hip) shares with api_allow.hip and api_ivf.hip
+// The work list of one launch group of an allowed search and the plan's workspace (eng->d_allow), sized by the rows scanned.
+struct AllowView {
+    int32_t* work_tile;
+    int32_t* work_rows;
+    uint32_t* work_mask;
+    int32_t* n_work;
+    unsigned char* plan_ws;
+    size_t total;
+};
+AllowView allow_layout(unsigned char* base, int64_t rows);
+int check_words(int64_t rows, int64_t words);   // RASS_ERR_INVALID where words < ceil(rows / 32)
+// The first two stages of a probe of one launch group (api_ivf.hip; the caller holds eng->mu): the top-nprobe centroids per
+// query — the flat fused scan for nprobe <= RASS_MAX_K (the lists, best first, stay at v->d_probe_ids [nq][min(nprobe, nlist)]),
+// the threshold path above — and the plan: the union of the probed lists as the work list v->d_work_* / d_n_work with per-tile
+// query masks, its rows in *v->d_scanned.  Leaves the group's normalised queries, zero-padded to pad_nq(nq) rows, at the head
+// of the engine scratch.  plan = false (nprobe <= RASS_MAX_K only): the coarse stage alone.
+int ivf_coarse_plan_locked(rass_ivf* v, const float* d_queries, int nq, int nprobe, bool plan = true);
 
 }  // namespace host
 }  // namespace rass

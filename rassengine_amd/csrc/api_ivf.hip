@@ -3,7 +3,8 @@
 //   build        the list plan of rass_ivf_build_prefix (host loops: the reference plan) and of rass_ivf_build_device /
 //                rass_ivf_absorb (ivf_build.hip) both end in ivf_build_tail, which materialises the IVF (fp32, bf16, int8 slab)
 //   persistence  rass_ivf_save / rass_ivf_load walk one section list (ivf_file_sections)
-//   search       the probe of one launch group (coarse scan or threshold path, plan, fine scan), the probe + flat delta, the
+//   search       the probe of one launch group (coarse scan or threshold path and plan: ivf_coarse_plan_locked, which the probe
+//                within a bitmap of api_ivf_allow.hip starts with as well; then the fine scan), the probe + flat delta, the
 //                batch of many groups — one fine scan and one merge tail (ivf_fine_scan / ivf_fine_merge) — and the host API
 //                on host_groups
 
@@ -21,7 +22,7 @@ static void ivf_free(rass_ivf* v) {
     for (void* p : {(void*)v->d_slab, (void*)v->d_slab_b16, (void*)v->d_slab_i8, (void*)v->d_slab_scale, (void*)v->d_cand_scores, (void*)v->d_cand_rows, (void*)v->d_tags, (void*)v->d_ids, (void*)v->d_centroids, (void*)v->d_list_tile0,
                     (void*)v->d_list_len, (void*)v->d_work_tile, (void*)v->d_work_rows, (void*)v->d_n_work,
                     (void*)v->d_work_mask, (void*)v->d_scanned, (void*)v->d_probe_scores, (void*)v->d_probe_ids,
-                    (void*)v->d_tau, (void*)v->d_list_mask, (void*)v->d_pair_scores, (void*)v->d_pair_ids, (void*)v->d_batch})
+                    (void*)v->d_tau, (void*)v->d_list_mask, (void*)v->d_pair_scores, (void*)v->d_pair_ids, (void*)v->d_batch, (void*)v->d_allow_ws})
         if (p) (void)hipFree(p);
     delete v;
 }
@@ -473,10 +474,11 @@ static int ivf_fine_merge(rass_ivf* v, const float* part_scores, const int64_t* 
 
 constexpr const char* kIvfI8MaxKMsg = "an int8 IVF slab serves k <= 16 (32 candidates per query)";
 
-// Caller holds eng->mu (the probe scratch of the IVF object and the engine scratch are shared).
-static int ivf_search_locked(rass_ivf_t* v, const float* d_queries, int nq, int k, int nprobe, const int32_t* d_q_filter,
-                             const int32_t* d_q_filter_mask, float* d_out_scores, int64_t* d_out_ids) {
-    if (!v || !d_queries || !d_out_scores || !d_out_ids) return fail(RASS_ERR_INVALID, "NULL argument");
+}  // extern "C"
+
+// The coarse stage and the plan of one launch group (declared in api_internal.h: the probe within a row bitmap starts the same way).
+int rass::host::ivf_coarse_plan_locked(rass_ivf* v, const float* d_queries, int nq, int nprobe, bool plan) {
+    if (!v || !d_queries) return fail(RASS_ERR_INVALID, "NULL argument");
     if (nprobe < 1) return fail(RASS_ERR_INVALID, "nprobe must be >= 1");
     if (int rc = check_nq(nq)) return rc;
     rass_engine* eng = v->eng;
@@ -485,16 +487,15 @@ static int ivf_search_locked(rass_ivf_t* v, const float* d_queries, int nq, int 
     hipStream_t st = eng->stream;
     const int np = std::min(nprobe, v->nlist);
     const int n_ctiles = (v->nlist + 31) / 32;
-    // what the coarse and the fine scan share: the caller's queries, one launch group, the engine's scratch and stream
-    ScanRequest s = scan_request(eng);
-    s.stride = v->stride, s.queries = d_queries, s.q_dim = v->dim, s.q_stride = v->dim, s.nq = nq;
+    if (!plan && np > RASS_MAX_K) return fail(RASS_ERR_UNSUPPORTED, "the probed lists are reported for nprobe <= RASS_MAX_K");
     if (np <= RASS_MAX_K || n_ctiles > kMaxGrid) {
         // (i) coarse: top-nprobe centroids per query with the flat fused scan
-        ScanRequest c = s;
+        ScanRequest c = scan_request(eng);
+        c.stride = v->stride, c.queries = d_queries, c.q_dim = v->dim, c.q_stride = v->dim, c.nq = nq;
         c.corpus = v->d_centroids, c.n_rows = v->nlist, c.k = std::min(np, RASS_MAX_K);
         c.out_scores = v->d_probe_scores, c.out_ids = v->d_probe_ids;
         rc = scan_launch(c);
-        if (rc != RASS_OK) return rc;
+        if (rc != RASS_OK || !plan) return rc;
         // (ii) plan: union of probed lists -> work tiles with per-tile query masks
         HIP_TRY(rass::launch_plan_probe(v->d_probe_ids, nq, std::min(np, RASS_MAX_K), v->nlist, v->d_list_tile0,
                                         v->d_list_len, v->d_work_tile, v->d_work_rows, v->d_work_mask, v->d_n_work,
@@ -513,6 +514,22 @@ static int ivf_search_locked(rass_ivf_t* v, const float* d_queries, int nq, int 
                                         v->d_work_rows, v->d_work_mask, v->d_n_work, v->d_scanned, st, v->d_list_mask,
                                         v->tile_rows));
     }
+    return RASS_OK;
+}
+
+extern "C" {
+
+// Caller holds eng->mu (the probe scratch of the IVF object and the engine scratch are shared).
+static int ivf_search_locked(rass_ivf_t* v, const float* d_queries, int nq, int k, int nprobe, const int32_t* d_q_filter,
+                             const int32_t* d_q_filter_mask, float* d_out_scores, int64_t* d_out_ids) {
+    if (!v || !d_queries || !d_out_scores || !d_out_ids) return fail(RASS_ERR_INVALID, "NULL argument");
+    int rc = ivf_coarse_plan_locked(v, d_queries, nq, nprobe);
+    if (rc != RASS_OK) return rc;
+    rass_engine* eng = v->eng;
+    hipStream_t st = eng->stream;
+    // what the fine scan takes over from the coarse one: the caller's queries, one launch group, the engine's scratch and stream
+    ScanRequest s = scan_request(eng);
+    s.stride = v->stride, s.queries = d_queries, s.q_dim = v->dim, s.q_stride = v->dim, s.nq = nq;
     // (iii) fine: the same fused scan over the planned tiles; slab positions -> source ids in the merge
     const IvfPlan plan{v->d_work_tile, v->d_work_rows, v->d_work_mask, v->d_n_work, v->total_tiles};
     const int32_t* row_tag = (v->any_tags || d_q_filter != nullptr) ? v->d_tags : nullptr;

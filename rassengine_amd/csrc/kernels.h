@@ -202,6 +202,27 @@ hipError_t launch_allow_plan(const uint32_t* allow, int64_t q_stride, int nq, in
 hipError_t launch_allow_store(const float* scores, const int64_t* rows, int nq, int kk, int k, int kdone, int64_t id_base,
                               const int64_t* id_map, float* out_scores, int64_t* out_ids, float* after_s, int64_t* after_i,
                               hipStream_t stream);
+// counts[b] = the set bits of bitmap b (allow + b * q_stride) below n_rows, b < n_bitmaps <= 65 535; counts is device int64.
+hipError_t launch_allow_count(const uint32_t* allow, int64_t q_stride, int n_bitmaps, int64_t n_rows, int64_t* counts, hipStream_t stream);
+
+// ---- an IVF probe within a row bitmap (ivf_allow.hip): the probe plan of ONE launch group (plan_probe_kernel's work list of
+// <= max_items items over 32-row tiles, *n_work of them) meets a bitmap over SOURCE rows (query q's words at allow + q *
+// q_stride, q_stride = 0: one shared bitmap; `words` uint32 each).  For every item and every q < nq the slab-order word goes
+// to slab_allow[q * slab_q_stride + tile] (a shared bitmap: one word per tile and slab_q_stride = 0; else slab_q_stride >=
+// every tile index + 1): bit r = the caller's bit of source row slab_ids[32 * tile + r], 0 where r >= the item's rows, the
+// position is padding (-1), the row lies at or past 32 * words, or the item's mask does not name q — what ScanArgs::allow
+// takes with the slab as the corpus.  work_mask[i] is narrowed in place to the queries whose word is non-zero; the items
+// that keep a query go, in their (ascending tile) order, to out_tile / out_rows / out_mask, *out_n = their number,
+// *scanned_rows = the sum of their rows.  workspace: ivf_allow_workspace_bytes(max_items).  Two launches; no workgroup waits
+// on another.  Plain vector loads, stores, ballots and atomics.
+size_t ivf_allow_workspace_bytes(int64_t max_items);
+hipError_t launch_ivf_allow_words(const int32_t* work_tile, const int32_t* work_rows, uint32_t* work_mask, const int32_t* n_work,
+                                  int64_t max_items, const int64_t* slab_ids, const uint32_t* allow, int64_t q_stride, int64_t words,
+                                  int nq, uint32_t* slab_allow, int64_t slab_q_stride, int32_t* out_tile, int32_t* out_rows,
+                                  uint32_t* out_mask, int32_t* out_n, int64_t* scanned_rows, void* workspace, hipStream_t stream);
+// *accum += *add_from (nullptr: nothing) + work_rows[0] + ... + work_rows[min(*n_work, max_items) - 1] (both nullptr: nothing).
+hipError_t launch_work_rows_add(const int32_t* work_rows, const int32_t* n_work, int64_t max_items, const int64_t* add_from, int64_t* accum,
+                                hipStream_t stream);
 
 // ---- attribute predicates (attr.hip): clauses over int32 columns -> the bitmaps of one launch group of nq <= 32 queries.
 // A clause {query, lo, hi, negate} of column c holds for row r when v = col[c][r] is not INT32_MIN and lo <= v <= hi, inverted

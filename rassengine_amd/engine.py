@@ -953,6 +953,30 @@ class FlatIndex:
                                               _np_ptr(tile), _np_ptr(rows), _np_ptr(mask), cap, ctypes.byref(n)))
         return tile[:n.value], rows[:n.value], mask[:n.value]
 
+    def allow_count(self, allow) -> np.ndarray:
+        """How many rows each bitmap names: its set bits below ``rows``, tombstoned rows included (``rass_index_allow_count``),
+        int64 [n_bitmaps] ([1] for a shared bitmap).  ``allow`` as ``search_allowed`` takes it: numpy uint32 words or a device
+        bitmap, [words] or [n, words], words >= ``allow_words``."""
+        import torch
+        on_device = not isinstance(allow, np.ndarray) and hasattr(allow, "data_ptr")
+        if on_device:
+            if not allow.is_cuda or allow.dtype != torch.int32 or not allow.is_contiguous():
+                raise ValueError("a device bitmap must be a contiguous int32 CUDA tensor")
+            d = allow
+        else:
+            a = np.ascontiguousarray(allow, dtype=np.uint32)
+            d = torch.from_numpy(a.view(np.int32)).to(f"cuda:{self.engine.device}")
+        if d.dim() not in (1, 2):
+            raise ValueError(f"allow must be [words] or [n, words], got {tuple(d.shape)}")
+        n_bitmaps, words = (1, int(d.shape[0])) if d.dim() == 1 else (int(d.shape[0]), int(d.shape[1]))
+        out = np.zeros(n_bitmaps, dtype=np.int64)
+        if n_bitmaps == 0:
+            return out
+        torch.cuda.current_stream(d.device).synchronize()     # the engine works on its own stream
+        N.check("rass_index_allow_count",
+                self._L.rass_index_allow_count(self._h, ctypes.c_void_p(d.data_ptr()), n_bitmaps, words, _np_ptr(out)))
+        return out
+
     def search_allowed(self, queries: np.ndarray, k: int, allow, q_filter: Optional[np.ndarray] = None,
                        q_filter_mask: Optional[np.ndarray] = None) -> Tuple[np.ndarray, np.ndarray]:
         """Exact cosine top-k among the rows a bitmap allows (``rass_index_search_allowed``).  ``allow``: uint32 words

@@ -491,6 +491,93 @@ class IvfIndex:
                                                      ctypes.c_void_p(d_q_filter_mask_ptr or 0),
                                                      ctypes.c_void_p(d_out_scores_ptr), ctypes.c_void_p(d_out_ids_ptr)))
 
+    def search_allowed_delta(self, flat: FlatIndex, queries: np.ndarray, k: int, nprobe: int, allow,
+                             q_filter: Optional[np.ndarray] = None, q_filter_mask: Optional[np.ndarray] = None
+                             ) -> Tuple[np.ndarray, np.ndarray, int]:
+        """``rass_ivf_search_allowed_delta``: ``search_delta`` within a row bitmap — per query the exact top-k over (the rows
+        of its ``nprobe`` best lists + ``flat``'s rows behind ``covered_rows``) that its bitmap allows.  ``allow`` as
+        ``FlatIndex.search_allowed`` takes it: uint32 words over ``flat``'s row ordinals as a numpy array or a device bitmap
+        (int32 CUDA tensor), [words] shared or [nq, words], words >= ``flat.allow_words``.  (scores, ids, rows scanned: the
+        probe tiles kept after the bitmap + the delta tiles planned, summed over the launch groups of 32.)  An fp32 slab,
+        k <= 32, nq <= 4096; at ``nprobe >= nlist`` the answer is ``flat.search_allowed``'s bit for bit."""
+        q = np.ascontiguousarray(queries, dtype=np.float32)
+        if q.ndim != 2 or q.shape[1] != self.dim:
+            raise ValueError(f"expected [nq, {self.dim}] queries, got {q.shape}")
+        nq, k = q.shape[0], int(k)
+        f = None if q_filter is None else np.ascontiguousarray(q_filter, dtype=np.int32)
+        m = None if q_filter_mask is None else np.ascontiguousarray(q_filter_mask, dtype=np.int32)
+        if (f is not None and f.shape != (nq,)) or (m is not None and (f is None or m.shape != (nq,))):
+            raise ValueError("q_filter / q_filter_mask must be one int32 per query (mask needs filter)")
+        on_device = not isinstance(allow, np.ndarray) and hasattr(allow, "data_ptr")
+        if not on_device:
+            allow = np.ascontiguousarray(allow, dtype=np.uint32)
+        elif not allow.is_cuda or allow.dtype != torch.int32 or not allow.is_contiguous():
+            raise ValueError("a device bitmap must be a contiguous int32 CUDA tensor")
+        shape = tuple(allow.shape)
+        if len(shape) not in (1, 2):
+            raise ValueError(f"allow must be [words] (shared) or [nq, words], got {shape}")
+        n_bitmaps, words = (1, shape[0]) if len(shape) == 1 else shape
+        scanned = ctypes.c_int64(0)
+        if not on_device:
+            out_s = np.empty((nq, k), dtype=np.float32)
+            out_i = np.empty((nq, k), dtype=np.int64)
+            N.check("rass_ivf_search_allowed_delta",
+                    self._L.rass_ivf_search_allowed_delta(
+                        self._h, flat._h, q.ctypes.data_as(ctypes.c_void_p), nq, k, int(nprobe),
+                        allow.ctypes.data_as(ctypes.c_void_p), int(n_bitmaps), int(words),
+                        None if f is None else f.ctypes.data_as(ctypes.c_void_p),
+                        None if m is None else m.ctypes.data_as(ctypes.c_void_p),
+                        out_s.ctypes.data_as(ctypes.c_void_p), out_i.ctypes.data_as(ctypes.c_void_p), ctypes.byref(scanned)))
+            return out_s, out_i, int(scanned.value)
+        dev = allow.device
+        dq = torch.from_numpy(q).to(dev)
+        df = torch.from_numpy(f).to(dev) if f is not None else None
+        dm = torch.from_numpy(m).to(dev) if m is not None else None
+        ds, di, dn = self.search_allowed_delta_device(flat, dq, k, nprobe, allow, df, dm)
+        self.engine.synchronize()
+        return ds.cpu().numpy(), di.cpu().numpy(), int(dn.item())
+
+    def search_allowed_delta_device(self, flat: FlatIndex, queries: torch.Tensor, k: int, nprobe: int, allow: torch.Tensor,
+                                    q_filter: Optional[torch.Tensor] = None, q_filter_mask: Optional[torch.Tensor] = None
+                                    ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """``rass_ivf_search_allowed_delta_device``: tensors in, tensors out — (scores f32 [nq, k], ids i64 [nq, k], rows
+        scanned i64 [1]) on the queries' device, enqueued on the ENGINE's stream (``engine.synchronize()`` before reading
+        them on another).  ``queries`` f32 [nq, dim], ``allow`` int32 [words] or [nq, words], filters int32 [nq]."""
+        dev = queries.device
+        nq = int(queries.shape[0])
+        if queries.dtype != torch.float32 or queries.dim() != 2 or queries.shape[1] != self.dim or not queries.is_contiguous():
+            raise ValueError(f"expected contiguous f32 [nq, {self.dim}] queries")
+        if allow.dtype != torch.int32 or not allow.is_contiguous() or allow.dim() not in (1, 2):
+            raise ValueError("a device bitmap must be a contiguous int32 CUDA tensor, [words] or [nq, words]")
+        for t in (q_filter, q_filter_mask):
+            if t is not None and (t.dtype != torch.int32 or tuple(t.shape) != (nq,) or not t.is_contiguous()):
+                raise ValueError("q_filter / q_filter_mask must be contiguous int32 [nq]")
+        n_bitmaps, words = (1, int(allow.shape[0])) if allow.dim() == 1 else (int(allow.shape[0]), int(allow.shape[1]))
+        ds = torch.empty((nq, int(k)), dtype=torch.float32, device=dev)
+        di = torch.empty((nq, int(k)), dtype=torch.int64, device=dev)
+        dn = torch.zeros((1,), dtype=torch.int64, device=dev)
+        torch.cuda.current_stream(dev).synchronize()      # the engine works on its own stream
+        N.check("rass_ivf_search_allowed_delta_device",
+                self._L.rass_ivf_search_allowed_delta_device(
+                    self._h, flat._h, ctypes.c_void_p(queries.data_ptr()), nq, int(k), int(nprobe),
+                    ctypes.c_void_p(allow.data_ptr()), n_bitmaps, words,
+                    ctypes.c_void_p(q_filter.data_ptr()) if q_filter is not None else None,
+                    ctypes.c_void_p(q_filter_mask.data_ptr()) if q_filter_mask is not None else None,
+                    ctypes.c_void_p(ds.data_ptr()), ctypes.c_void_p(di.data_ptr()), ctypes.c_void_p(dn.data_ptr())))
+        return ds, di, dn
+
+    def probe_lists(self, queries: np.ndarray, nprobe: int) -> np.ndarray:
+        """The lists a probe of ``nprobe`` <= 32 visits (``rass_ivf_probe_lists``): int64 [nq, nprobe], each query's best
+        lists by centroid score, best first, -1 past ``nlist``.  The coarse stage alone: nothing is scanned."""
+        q = np.ascontiguousarray(queries, dtype=np.float32)
+        if q.ndim != 2 or q.shape[1] != self.dim:
+            raise ValueError(f"expected [nq, {self.dim}] queries, got {q.shape}")
+        out = np.empty((q.shape[0], int(nprobe)), dtype=np.int64)
+        N.check("rass_ivf_probe_lists",
+                self._L.rass_ivf_probe_lists(self._h, q.ctypes.data_as(ctypes.c_void_p), q.shape[0], int(nprobe),
+                                             out.ctypes.data_as(ctypes.c_void_p)))
+        return out
+
     @property
     def dtype(self) -> str:
         return {v: k for k, v in SLAB_DTYPES.items()}[int(self._L.rass_ivf_dtype(self._h))]
@@ -572,21 +659,53 @@ class IvfPolicy:
     grown by more than ``rebuild_fraction`` of ``trained_rows`` (the rows covered when the centroids were last trained; an
     IVF loaded from disk takes its covered rows).  The delta ages much faster — it is scanned exactly by every search —
     and is ABSORBED once it exceeds ``absorb_fraction`` of the covered rows: the appended rows get a list of the existing
-    centroids and join the slab (``IvfIndex.absorb``: no training, no host pass over the rows)."""
+    centroids and join the slab (``IvfIndex.absorb``: no training, no host pass over the rows).
+
+    ``allow_probe`` (``RASS_IVF_ALLOW=1``; default False: every bitmap-filtered search is the exact flat allow scan, as
+    before) lets ``IvfBackedIndex.search_allowed`` probe the IVF within the bitmap where ``allow_route`` says "ivf".
+    ``allow_exact_factor`` (default 1.0) scales the probe's side of that comparison.  The default follows from the bytes the
+    two scans stream and NOTHING else: nobody has measured where the two really cross (the probe adds a coarse scan, the
+    bitmap's translation and scattered tiles, and a group of 32 queries streams the union of their lists; the flat scan's
+    bound assumes no two allowed rows share a tile).  ``scripts/probe_ivf_allow.py`` is where a better value would come
+    from: its first run (``profiles/probe_ivf_allow_*.json``: bitmaps of 1 - 50 % of the rows) only covers cases far on the
+    IVF's side — 10 - 23 x faster at 12.5 M rows — and shows what the rule does not look at: the probe is approximate, and
+    its recall within the filtered set drops once the filter leaves about one allowed row per cluster."""
 
     def __init__(self, nlist: int = 0, nprobe: int = 8, min_rows: int = 262144, rebuild_fraction: float = 0.25,
-                 dtype: str = "f32", train_rows: int = 0, iters: int = 10, seed: int = 0, absorb_fraction: float = 0.0):
+                 dtype: str = "f32", train_rows: int = 0, iters: int = 10, seed: int = 0, absorb_fraction: float = 0.0,
+                 allow_probe: bool = False, allow_exact_factor: float = 1.0):
         self.nlist, self.nprobe, self.min_rows = int(nlist), max(1, int(nprobe)), int(min_rows)
         self.rebuild_fraction, self.dtype = float(rebuild_fraction), dtype
         self.train_rows, self.iters, self.seed = int(train_rows), int(iters), int(seed)
         self.absorb_fraction = max(0.0, float(absorb_fraction))
+        self.allow_probe, self.allow_exact_factor = bool(allow_probe), float(allow_exact_factor)
 
     @classmethod
     def from_config(cls) -> "IvfPolicy":
         from . import config
         return cls(config.RASS_IVF_NLIST, config.RASS_IVF_NPROBE, config.RASS_IVF_MIN_ROWS,
                    config.RASS_IVF_REBUILD_FRACTION, config.RASS_IVF_DTYPE,
-                   absorb_fraction=config.RASS_IVF_ABSORB_FRACTION)
+                   absorb_fraction=config.RASS_IVF_ABSORB_FRACTION, allow_probe=config.RASS_IVF_ALLOW)
+
+    def allow_route(self, counts, nq: int, shared: bool, nprobe: int, covered: int, nlist: int) -> str:
+        """"ivf" or "flat" for a bitmap-filtered search, by the rows each would stream for the call's LARGEST launch group of
+        32 queries.  ``counts``: the set bits of the call's bitmaps (``FlatIndex.allow_count``) — one per query, or the one
+        count of a ``shared`` bitmap.  The flat allow scan of a group streams every 32-row tile with a bit set: at most
+        32 * C rows, C = the sum of the group's counts (the one count when shared).  The probe streams about
+        ``nprobe * covered / nlist`` rows.  "ivf" iff 32 * C > ``allow_exact_factor`` * nprobe * covered / nlist: equality
+        goes to "flat", and so does a call whose bitmaps are empty; an IVF that covers nothing (covered = 0: its probe streams
+        nothing, the delta scan is the flat allow scan) takes any non-empty call.  A pure function of its arguments (and the
+        factor)."""
+        c = [int(x) for x in np.asarray(counts).reshape(-1)]
+        nq, nlist = int(nq), int(nlist)
+        if nq <= 0 or not c or nlist <= 0:
+            return "flat"
+        if shared:
+            worst = c[0]
+        else:
+            worst = max(sum(c[g:g + 32]) for g in range(0, min(nq, len(c)), 32))
+        probe_rows = self.allow_exact_factor * int(nprobe) * int(covered) / nlist
+        return "ivf" if 32 * worst > probe_rows else "flat"
 
     @classmethod
     def manual(cls, nprobe: int = 8) -> "IvfPolicy":
@@ -630,6 +749,7 @@ class IvfBackedIndex(FlatIndex):
         self.ivf: Optional[IvfIndex] = None
         self.builds = 0                      # bumped by every swap (part of ``epoch``)
         self.trained_rows = 0                # rows covered when the IVF's centroids were last trained (IvfPolicy.action)
+        self.ivf_allowed = 0                 # search_allowed calls served by a probe of the IVF within the bitmap
         self._ivf_lock = threading.RLock()   # deletes and the build's final phase exclude each other
 
     # ---- bookkeeping
@@ -773,6 +893,38 @@ class IvfBackedIndex(FlatIndex):
         if ivf is None:
             return super().search(queries, k, q_filter, q_filter_mask)
         s, i, _ = ivf.search_delta(self, queries, int(k), int(nprobe or self.policy.nprobe), q_filter, q_filter_mask)
+        return s, i
+
+    def search_allowed(self, queries: np.ndarray, k: int, allow, q_filter: Optional[np.ndarray] = None,
+                       q_filter_mask: Optional[np.ndarray] = None, exact: bool = False, nprobe: Optional[int] = None
+                       ) -> Tuple[np.ndarray, np.ndarray]:
+        """``FlatIndex.search_allowed``, served by a probe of the IVF within the bitmap (``IvfIndex.search_allowed_delta``)
+        when ALL of these hold — and by the exact flat allow scan, exactly as without an IVF, otherwise: the policy's
+        ``allow_probe`` is on (``RASS_IVF_ALLOW=1``; off by default); ``exact`` is false; an fp32 IVF is present; k <= 32; the
+        bitmap is long enough for the index as it is now (a shorter one takes the flat path, which extends it); and
+        ``IvfPolicy.allow_route`` says the probe streams fewer rows than the flat scan would for the call's largest launch
+        group.  ``ivf_allowed`` counts the calls the IVF served."""
+        ivf = self.ivf if (self.policy.allow_probe and not exact) else None
+        if ivf is None or ivf.dtype != "f32" or not 1 <= int(k) <= 32:
+            return super().search_allowed(queries, k, allow, q_filter, q_filter_mask)
+        nq = int(np.shape(queries)[0])
+        if isinstance(allow, np.ndarray) or not hasattr(allow, "data_ptr"):
+            allow = np.ascontiguousarray(allow, dtype=np.uint32)
+        shape = tuple(allow.shape)
+        if nq == 0 or len(shape) not in (1, 2) or (len(shape) == 2 and shape[0] not in (1, nq)) or shape[-1] < self.allow_words:
+            return super().search_allowed(queries, k, allow, q_filter, q_filter_mask)   # its checks, its padding
+        nprobe = int(nprobe or self.policy.nprobe)
+        shared = len(shape) == 1 or shape[0] == 1
+        try:
+            route = self.policy.allow_route(self.allow_count(allow), nq, shared, nprobe, ivf.covered_rows, ivf.nlist)
+            if route != "ivf":
+                return super().search_allowed(queries, k, allow, q_filter, q_filter_mask)
+            s, i, _ = ivf.search_allowed_delta(self, queries, int(k), nprobe, allow, q_filter, q_filter_mask)
+        except N.RassError:
+            if self.allow_words <= shape[-1]:
+                raise
+            return super().search_allowed(queries, k, allow, q_filter, q_filter_mask)   # the index outgrew the bitmap meanwhile
+        self.ivf_allowed += 1
         return s, i
 
     def search_device(self, d_queries_ptr: int, nq: int, k: int, d_out_scores_ptr: int, d_out_ids_ptr: int,
