@@ -116,6 +116,22 @@ int rass_engine_synchronize(rass_engine_t* eng);
 
 /* ----------------------------------------------------------------- index */
 
+/* Scores that are not finite (DESIGN.md §3 "Scores that are not finite").
+ * Nothing refuses a row or a query that holds a NaN or an Inf: normalising a vector with one NaN stores an all-NaN row, one
+ * with an Inf stores [0, ..., NaN, ..., 0], and normalize = 0 stores what it is given.  The oracle's rule (oracle/rass_oracle.c,
+ * topk_insert) holds for every search form of this header, flat, prefiltered and IVF alike:
+ *  - A live row whose score for a query is NaN or -inf is, for that query, as if it were deleted.
+ *  - Such a row is never returned, never counted (totals, hits, bucket and group counts), never the representative of a group or
+ *    bucket, and never sets the status of a grouped or counted search.
+ *  - Such a row is never what fills or displaces a result slot: the other rows of the answer are the ones, and the bits, the
+ *    same index gives with that row deleted.
+ *  - A query that normalises to NaN gets the empty answer of its entry point: (-inf, -1) lists (-1 groups and ranks), totals,
+ *    bucket counts and group counts of 0.  It does not disturb the other queries of its call.
+ *  - rass_topk_merge* drop an entry whose score is NaN or -inf whatever its id; +inf ranks first, by id.
+ * An IVF keeps such a row in list 0, where no probe finds it; training leaves it out, and no centroid is ever not finite.
+ * Out of scope: refusing rows that are not finite at rass_index_add*; rows whose score overflows to +inf; and
+ * rass_index_rows_gram called directly on such a row, which keeps its IEEE results. */
+
 /* Replaces ensure_index_exists()'s knn_vector field (app/main.py:350-579,
  * vector field 563-572; name from get_index_name 346-347): look up the named
  * cosine index, creating it when absent.  O(1) when it exists, because the

@@ -425,7 +425,10 @@ __device__ __forceinline__ void rerank_f32_body(const float* __restrict__ slab, 
         float s = part[cc][0];
 #pragma unroll
         for (int ww = 1; ww < 8; ++ww) s += part[cc][ww];
-        const int64_t r = cc < n_cand ? cand_rows[(int64_t)q * n_cand + cc] : -1;
+        int64_t r = cc < n_cand ? cand_rows[(int64_t)q * n_cand + cc] : -1;
+        // NaN and -inf never rank: a candidate whose exact score is either (a NaN query reaches here behind the int8 stages,
+        // whose scores cannot hold a NaN) is no candidate, for the ranks and for the number of valid slots alike
+        if (!(s > -INFINITY)) r = -1;
         sc[cc] = r >= 0 ? s : -INFINITY;
         // the id that is reported and that breaks score ties: the slab row itself, or (an IVF's permuted slab) the source row
         rw[cc] = (r >= 0 && id_map != nullptr) ? id_map[r] : r;

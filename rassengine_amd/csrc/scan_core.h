@@ -276,6 +276,7 @@ constexpr int kFloorBits = 20;
 // that is below `cap`.  The counter runs on past cap: it is the exact total.  Which workgroup lands where depends on timing;
 // range_finish sorts the pairs under a total order, so the answer does not.
 __device__ __forceinline__ void emit_range(bool hit, float s, int row, unsigned* count, uint2* hits, int cap) {
+    hit = hit && s > -INFINITY;   // NaN and -inf never rank (include/rass_engine.h, "Scores that are not finite")
     const unsigned long long b = __ballot(hit);
     if (b == 0) return;   // wave-uniform
     const int lane = lane_id();
@@ -303,7 +304,8 @@ __device__ __forceinline__ uint64_t cand_key(float s, int32_t row) {
 __device__ __forceinline__ void emit_group_max(bool ok, float s, int row, int tag, int group_mask, int group_shift, int n_groups,
                                                unsigned long long* table_q, unsigned* status) {
     const unsigned g = (unsigned)(tag & group_mask) >> group_shift;
-    if (!ok) return;
+    // NaN and -inf never rank: such a row is no match, so it is in no group and sets no status (NaN's key would top every score's)
+    if (!ok || !(s > -INFINITY)) return;
     if (g >= (unsigned)n_groups) {
         __hip_atomic_store(status, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         return;
@@ -326,6 +328,7 @@ __device__ __forceinline__ void emit_group_count(bool hit, float s, int row, int
                                                  int n_groups, unsigned long long* best, unsigned* count, unsigned* status) {
     const unsigned g = (unsigned)(tag & group_mask) >> group_shift;
     const bool inside = g < (unsigned)n_groups;
+    hit = hit && s > -INFINITY;   // NaN and -inf never rank: no hit, no status
     if (hit && !inside) __hip_atomic_store(status, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     hit = hit && inside;
     const unsigned long long b = __ballot(hit);

@@ -325,18 +325,27 @@ __global__ __launch_bounds__(256) void quantize_tile16_i8_kernel(const float* __
         const float* sb = src + b * 16 * stride;
         signed char* db = dst + b * 16 * stride_i8;
         float mx = 0.f;
+        int bad = 0;   // the row holds a NaN or an Inf (fmaxf drops a NaN: mx alone does not tell)
         for (int jb = 0; jb < nch; ++jb) {
             const float* sc = sb + (int64_t)(4 * jb + g) * 256;
 #pragma unroll
             for (int gg = 0; gg < 4; ++gg) {
                 const f32x4 v = *reinterpret_cast<const f32x4*>(sc + (gg * 16 + m) * 4);
-                mx = fmaxf(mx, fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w))));
+                const float a = fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w)));
+                const float z = ((v.x - v.x) + (v.y - v.y)) + ((v.z - v.z) + (v.w - v.w));   // 0, or NaN (Inf - Inf, NaN - NaN)
+                bad |= (z != 0.f) ? 1 : 0;
+                mx = fmaxf(mx, a);
             }
         }
         mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
         mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-        const float inv = mx > 0.f ? 127.f / mx : 0.f;
-        const float sy = mx / 127.f;
+        bad |= __shfl_xor(bad, 16, 64);
+        bad |= __shfl_xor(bad, 32, 64);
+        // A row that is not finite must not get a finite int8 score: its bytes are zero and its scale carries a NaN, so that
+        // every scan's (float)dot * scale is NaN, which passes no floor, no tau and no threshold.  It adds nothing to the
+        // certified mode's row maxima either: it is no candidate, so no bound is ever asked of it.
+        const float inv = (mx > 0.f && !bad) ? 127.f / mx : 0.f;
+        const float sy = bad ? __uint_as_float(0x7fc00000u) : mx / 127.f;
         if (g == 0) scale[b * 16 + m] = sy;
         double rho2 = 0.0, nu2 = 0.0, y2 = 0.0;   // the certified mode's row terms (exact products in double)
         for (int jb = 0; jb < nch; ++jb) {
@@ -345,8 +354,9 @@ __global__ __launch_bounds__(256) void quantize_tile16_i8_kernel(const float* __
 #pragma unroll
             for (int gg = 0; gg < 4; ++gg) {
                 const f32x4 v = *reinterpret_cast<const f32x4*>(sc + (gg * 16 + m) * 4);
-                const int q0 = (int)rintf(v.x * inv), q1 = (int)rintf(v.y * inv), q2 = (int)rintf(v.z * inv), q3 = (int)rintf(v.w * inv);
-                if (stats) {
+                const int q0 = bad ? 0 : (int)rintf(v.x * inv), q1 = bad ? 0 : (int)rintf(v.y * inv);
+                const int q2 = bad ? 0 : (int)rintf(v.z * inv), q3 = bad ? 0 : (int)rintf(v.w * inv);
+                if (stats && !bad) {
                     const float vv[4] = {v.x, v.y, v.z, v.w};
                     const int qq[4] = {q0, q1, q2, q3};
 #pragma unroll
@@ -607,7 +617,8 @@ __global__ __launch_bounds__(kIThreads, 1) void scan_i8_cert_kernel(ScanI8CertAr
                 sl += src[wv * NQ * kIPitch + 16 * kIPitch];
             }
             const float a = __fmul_rn(rscale, __fadd_rn(__fmul_rn(s_hi, (float)sh), __fmul_rn(s_lo, (float)sl)));
-            const bool elig = q_ok && (r < rows) && (rtag != -1) && (qfilt < 0 || qfilt == (rtag & qmask));
+            // a row whose stored scale is NaN holds a value that is not finite (quantize_tile16_i8_kernel): it is as if deleted
+            const bool elig = q_ok && (r < rows) && (rtag != -1) && (qfilt < 0 || qfilt == (rtag & qmask)) && (a == a);
             if (sample) {
                 best = elig ? fmaxf(best, a) : best;
             } else {

@@ -145,11 +145,24 @@ def _repair(index: FlatIndex, cent: torch.Tensor, counts: torch.Tensor, best: to
     m_sample = min(n_blocks * BLOCK_ROWS, n, 1 << 24)
     rows_global = _sample_row(torch.arange(m_sample, device=dev), step)
     w = torch.clamp(1.0 - best[:m_sample].float(), min=0.0) ** 2
-    w = torch.where(rows_global < n, w, torch.zeros_like(w))
+    # (a row that no mean wins — it holds a NaN, its best is -inf — is never drawn)
+    w = torch.where((rows_global < n) & (best[:m_sample] > float("-inf")), w, torch.zeros_like(w))
     idx = torch.multinomial(w.cpu().double(), int(freed.numel()), replacement=False, generator=g)
     cent = cent.clone()
     cent[freed] = _gather_rows(index, torch.clamp(_sample_row(idx, step), max=n - 1).tolist(), dev)
     return cent, int(freed.numel())
+
+
+def _finite_rows(new: torch.Tensor, old: Optional[torch.Tensor]) -> torch.Tensor:
+    """``new`` with every row that holds a NaN or an Inf replaced by the same row of ``old`` where that one is finite, and by
+    a zero row otherwise (``old`` None: always).  A centroid seeded from an index row that is not finite would win no row,
+    never be probed and lose its list for good; a zero centroid scores 0 against every row and takes the mean of whatever
+    it wins at the next iteration."""
+    bad = ~torch.isfinite(new).all(dim=1)
+    if not bool(bad.any()):
+        return new
+    keep = torch.zeros_like(new) if old is None else torch.where(torch.isfinite(old).all(dim=1)[:, None], old, torch.zeros_like(old))
+    return torch.where(bad[:, None], keep, new)
 
 
 def _lloyd(index: FlatIndex, cent: torch.Tensor, iters: int, step: int, n_blocks: int, g: torch.Generator, repair: bool,
@@ -162,8 +175,12 @@ def _lloyd(index: FlatIndex, cent: torch.Tensor, iters: int, step: int, n_blocks
     rank = dist.get_rank(group) if dist.is_initialized() else 0
     one = torch.empty((1, index.dim), dtype=torch.float32, device=dev)
     counts = torch.zeros((nlist,), dtype=torch.float32, device=dev)
+    cent = _finite_rows(cent, None)                         # a seed may be a row that holds a NaN
     for it in range(iters):
-        assign, _slab = kmeans_assign(index, cent, 0, step, n_blocks)
+        assign, best, _slab = kmeans_assign(index, cent, 0, step, n_blocks, with_best=True)
+        # A row that no centroid wins (its every score is NaN: best stays -inf) is placed in list 0 by the kernel, which is
+        # where a build keeps it, findable by nothing.  Training leaves it out: its NaN would end in list 0's mean.
+        assign = torch.where(best > float("-inf"), assign, torch.full_like(assign, -1))
         sums, counts = kmeans_accumulate(index, assign, nlist, 0, step, n_blocks)
         if world > 1:
             dist.all_reduce(sums, group=group)
@@ -177,7 +194,7 @@ def _lloyd(index: FlatIndex, cent: torch.Tensor, iters: int, step: int, n_blocks
                 new[li] = _rows_chunk(index, int(r), 1, one)[0]
             if world > 1:
                 dist.broadcast(new, src=0, group=group)
-        cent = new
+        cent = _finite_rows(new, cent)                      # an empty list may have been re-seeded from a row that holds a NaN
         if repair and it % 2 == 1 and it < (2 * iters) // 3:
             # rank 0's sample decides what is merged and where the freed centroids go; everyone gets its result
             if rank == 0:

@@ -287,6 +287,75 @@ def test_merge_matches_oracle(gpu, oracle):
         assert np.array_equal(got[ri >= 0], rs[ri >= 0].astype(np.float32))
 
 
+def test_merge_of_lists_with_scores_that_are_not_finite(gpu, oracle):
+    """Foreign lists may carry valid ids with NaN, -inf and +inf scores (include/rass_engine.h, "Scores that are not
+    finite"): NaN and -inf never appear in the output, +inf ranks first, by id — through rass_topk_merge, _strided and
+    _strided_batch alike, against the oracle's merge and a numpy restatement of the rule."""
+    import ctypes
+    from rassengine_amd import _native as N
+    from rassengine_amd import ops
+    from rassengine_amd.dist import HipShard
+    rng = np.random.default_rng(90)
+    G, nq, k = 6, 32, 10
+    s = rng.standard_normal((G, nq, k)).astype(np.float32)
+    ids = rng.permutation(G * nq * k).reshape(G, nq, k).astype(np.int64)
+    kind = rng.random(s.shape)
+    s[kind < 0.15] = np.nan
+    s[(kind >= 0.15) & (kind < 0.25)] = -np.inf
+    s[(kind >= 0.25) & (kind < 0.30)] = np.inf
+    s[:, 3] = np.nan                                   # a query with nothing that ranks
+    s[:, 4, 1:] = -np.inf                              # a query with fewer than k rows that rank, two of them +inf
+    s[:2, 4, 0] = np.inf
+    ids[kind > 0.95] = -1
+    exp_s = np.full((nq, k), -np.inf, dtype=np.float32)
+    exp_i = np.full((nq, k), -1, dtype=np.int64)
+    for q in range(nq):
+        ss, ii = s[:, q].reshape(-1), ids[:, q].reshape(-1)
+        ok = (ii >= 0) & (ss > -np.inf)                # false for NaN
+        order = np.lexsort((ii[ok], -ss[ok].astype(np.float64)))[:k]
+        exp_s[q, :len(order)], exp_i[q, :len(order)] = ss[ok][order], ii[ok][order]
+    assert np.all(exp_i[3] == -1) and (exp_i[4] >= 0).sum() < k and np.all(np.isposinf(exp_s[4, :2])) and exp_i[4, 0] < exp_i[4, 1]
+    rs, ri = oracle.merge(s.astype(np.float64), ids)
+    assert np.array_equal(ri, exp_i) and np.array_equal(rs[ri >= 0].astype(np.float32), exp_s[ri >= 0])
+
+    def check(out_s, out_i):
+        gpu.cuda.synchronize()
+        got_s, got_i = out_s.cpu().numpy(), out_i.cpu().numpy()
+        assert np.array_equal(got_i, exp_i)
+        assert np.array_equal(got_s.view(np.uint32), exp_s.view(np.uint32))
+        assert not np.isnan(got_s).any() and not np.isneginf(got_s[got_i >= 0]).any()
+
+    check(*ops.topk_merge(gpu.from_numpy(s).cuda(), gpu.from_numpy(ids).cuda()))
+    ids_off, size = HipShard.record_bytes(nq, k)
+    buf = np.zeros((G, size), dtype=np.uint8)
+    for g in range(G):
+        buf[g, : nq * k * 4] = s[g].view(np.uint8).reshape(-1)
+        buf[g, ids_off: ids_off + nq * k * 8] = ids[g].view(np.uint8).reshape(-1)
+    d = gpu.from_numpy(buf.reshape(-1)).cuda()
+    # the batch form: two launch groups of 16 queries, [rank][group][record of 16 queries]
+    gq = nq // 2
+    ids_off2, size2 = HipShard.record_bytes(gq, k)
+    buf2 = np.zeros((G, 2, size2), dtype=np.uint8)
+    for g in range(G):
+        for h in range(2):
+            buf2[g, h, : gq * k * 4] = s[g, h * gq:(h + 1) * gq].copy().view(np.uint8).reshape(-1)
+            buf2[g, h, ids_off2: ids_off2 + gq * k * 8] = ids[g, h * gq:(h + 1) * gq].copy().view(np.uint8).reshape(-1)
+    d2 = gpu.from_numpy(buf2.reshape(-1)).cuda()
+    for batch in (False, True):
+        out_s = gpu.full((nq, k), 777.0, dtype=gpu.float32, device="cuda")
+        out_i = gpu.full((nq, k), -777, dtype=gpu.int64, device="cuda")
+        gpu.cuda.synchronize()
+        if not batch:
+            N.check("m", N.lib().rass_topk_merge_strided(ctypes.c_void_p(d.data_ptr()), ctypes.c_void_p(d.data_ptr() + ids_off),
+                                                         size // 4, size // 8, G, nq, k, ctypes.c_void_p(out_s.data_ptr()),
+                                                         ctypes.c_void_p(out_i.data_ptr()), None))
+        else:
+            N.check("m", N.lib().rass_topk_merge_strided_batch(
+                ctypes.c_void_p(d2.data_ptr()), ctypes.c_void_p(d2.data_ptr() + ids_off2), 2 * size2 // 4, 2 * size2 // 8, G, nq,
+                gq, size2 // 4, size2 // 8, k, ctypes.c_void_p(out_s.data_ptr()), ctypes.c_void_p(out_i.data_ptr()), None))
+        check(out_s, out_i)
+
+
 @pytest.mark.parametrize("n,dim,stride", [(1, 1024, 1024), (257, 1024, 1024), (100, 100, 128), (33, 7, 128),
                                           (1000, 384, 384), (5, 1023, 1024)])
 def test_normalize_rows(gpu, oracle, n, dim, stride):

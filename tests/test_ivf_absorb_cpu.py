@@ -208,3 +208,32 @@ def test_a_loaded_ivf_takes_its_covered_rows_as_trained_rows(monkeypatch, tmp_pa
     monkeypatch.setattr(M.IvfIndex, "load", staticmethod(lambda eng, f: FakeIvf(4000)))
     idx = M.IvfBackedIndex.load(engine, "u", path, M.IvfPolicy(nlist=16, min_rows=64, absorb_fraction=0.05))
     assert idx.ivf is None and idx.trained_rows == 0
+
+
+# ------------------------------------------------------------------------------------------------ training over rows that are not finite
+def test_a_centroid_that_is_not_finite_is_replaced_not_kept():
+    """``_finite_rows`` (include/rass_engine.h, "Scores that are not finite"): a new centroid holding a NaN or an Inf — a
+    seed or a re-seed drawn from such an index row — gives way to the same row of the old set where that one is finite, to a
+    zero row otherwise; finite rows pass through bit for bit, and a set without such a row is returned as it is."""
+    import torch
+    from rassengine_amd.ivf import _finite_rows
+    g = torch.Generator().manual_seed(1)
+    new = torch.randn((6, 8), generator=g)
+    old = torch.randn((6, 8), generator=g)
+    assert _finite_rows(new, old) is new and _finite_rows(new, None) is new
+    bad = new.clone()
+    bad[1, 3] = float("nan")
+    bad[2, 0] = float("inf")
+    bad[4] = float("nan")
+    bad[5, 7] = float("-inf")
+    prev = old.clone()
+    prev[2, 5] = float("nan")                                  # the old row 2 is no better: zeros
+    out = _finite_rows(bad, prev)
+    assert bool(torch.isfinite(out).all())
+    assert torch.equal(out[0], new[0]) and torch.equal(out[3], new[3])
+    assert torch.equal(out[1], old[1]) and torch.equal(out[4], old[4]) and torch.equal(out[5], old[5])
+    assert torch.equal(out[2], torch.zeros(8))
+    seeds = _finite_rows(bad, None)                            # the seeds have no older set
+    assert bool(torch.isfinite(seeds).all()) and torch.equal(seeds[0], new[0])
+    for r in (1, 2, 4, 5):
+        assert torch.equal(seeds[r], torch.zeros(8))

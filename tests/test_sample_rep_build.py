@@ -9,10 +9,14 @@ waited for nearly all of them at every tile).
 
 The exact re-rank (scan_bf16.hip, rerank_f32_kernel<1..8> and its wide form) shares its fmaf chain with the stage's rescore
 kernel through exact_score.h; factoring it out must not change its device code.  tests/golden/rerank_f32_device_code.json
-holds, per kernel, the SHA-256 of the instruction text and resource lines as scripts/compare_device_code.py normalises them,
-taken from the tree before the chain was factored out:
+holds, per kernel, the SHA-256 of the instruction text and resource lines as scripts/compare_device_code.py normalises them:
 
-    python tests/test_sample_rep_build.py OLD/rassengine_amd/csrc > tests/golden/rerank_f32_device_code.json
+    python tests/test_sample_rep_build.py TREE/rassengine_amd/csrc > tests/golden/rerank_f32_device_code.json
+
+First taken from the tree before the chain was factored out.  Taken again, from the tree that made the change, when
+rerank_f32_body began to count a candidate whose exact score is NaN or -inf as no candidate (include/rass_engine.h, "Scores
+that are not finite": one compare and a select ahead of the ranking; the fmaf chain of exact_score.h is untouched): all twelve
+kernels changed with it, on purpose.  Any later change of these kernels must again be one that is meant.
 """
 import hashlib
 import importlib.util
