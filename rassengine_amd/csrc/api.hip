@@ -1196,7 +1196,9 @@ const char* rass_scan_kernel_name(int dim, int nq) {
         return "";
     if (stride > kNarrowStride) {
         const int ch = (int)(stride / 128);
-        snprintf(buf, sizeof(buf), "scan_topk_f32_wide_kernel<%d, %d, false>", ch == 16 ? 4 : ch / 2, ch == 16 ? 4 : 2);
+        // <CHP, P, EXT, RANGE, GROUP, COUNT>: the plain top-k instantiation of launch_wide (scan_topk.hip)
+        snprintf(buf, sizeof(buf), "scan_topk_f32_wide_kernel<%d, %d, false, false, false, false>", ch == 16 ? 4 : ch / 2,
+                 ch == 16 ? 4 : 2);
         return buf;
     }
     snprintf(buf, sizeof(buf), "scan_topk_f32_kernel<%d, %d, 0, false>", (int)(stride / 128), nq <= 16 ? 1 : 2);

@@ -295,14 +295,19 @@ hipError_t launch_scan_i8_topk(const ScanI8Args& a, int grid, hipStream_t stream
     if (ivf && (!a.work_rows || !a.work_mask || !a.n_work || a.sample_best || a.wgs_per_group)) return hipErrorInvalidValue;
     if (a.wgs_per_group > 0 && (grid % a.wgs_per_group != 0 || a.sample_best)) return hipErrorInvalidValue;
     const bool two = a.nq > 16;
+#define RASS_I8_FLAT(C) return two ? launch_ivariant<C, 2, false>(a, grid, stream) : launch_ivariant<C, 1, false>(a, grid, stream);
 #define RASS_I8_CASE(C)                                                                                                     \
     if (ivf) return two ? launch_ivariant<C, 2, true>(a, grid, stream) : launch_ivariant<C, 1, true>(a, grid, stream);       \
-    return two ? launch_ivariant<C, 2, false>(a, grid, stream) : launch_ivariant<C, 1, false>(a, grid, stream);
+    RASS_I8_FLAT(C)
     if (a.row_stride == 512) { RASS_I8_CASE(1) }
     if (a.row_stride == 1024) { RASS_I8_CASE(2) }
-    if (a.row_stride == 1536) { RASS_I8_CASE(3) }   // wide rows (1 024 < dim <= 2 048)
-    RASS_I8_CASE(4)
+    // wide rows (1 024 < dim <= 2 048): flat scans only.  An IVF is built over dim <= 1 024, so its int8 slab has stride 512
+    // or 1 024 and a probe plan never comes with these strides: no IVF instantiation is compiled for them.
+    if (ivf) return hipErrorInvalidValue;
+    if (a.row_stride == 1536) { RASS_I8_FLAT(3) }
+    RASS_I8_FLAT(4)
 #undef RASS_I8_CASE
+#undef RASS_I8_FLAT
 }
 
 // A non-negative double (a norm summed in double: relative error < 2.3e-13 for <= 2 048 terms) -> a float that is not below it.

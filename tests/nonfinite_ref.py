@@ -98,13 +98,13 @@ def swaps_are_ties(i_gpu, i_ref, all64):
     return True
 
 
-def no_near_ties(rs):
-    """No two of each query's reference scores (best first, k + 1 of them, -inf padding) within 2 TOL_F64: then the ids are
+def no_near_ties(rs, tol=TOL_F64):
+    """No two of each query's reference scores (best first, k + 1 of them, -inf padding) within 2 ``tol``: then the ids are
     decided and the tie allowance of ``swaps_are_ties`` is never used."""
     rs = np.asarray(rs, dtype=np.float64)
     with np.errstate(invalid="ignore"):
         gap = rs[:, :-1] - rs[:, 1:]
-    return bool(np.all(~(gap <= 2 * TOL_F64)))          # inf - inf = NaN past the end: not a tie
+    return bool(np.all(~(gap <= 2 * tol)))              # inf - inf = NaN past the end: not a tie
 
 
 def clear_of(thr, all64, tags_ref):
