@@ -797,7 +797,9 @@ typedef struct rass_ivf rass_ivf_t;
  *   rass_kmeans_accumulate: d_sums[list][0..dim) += row, d_counts[list] += 1 for every processed row below
  *     rass_index_rows() (fp32 atomics; d_sums is nlist x dim row-major, caller-zeroed).
  * The all-reduce over ranks, the normalisation of the sums and the re-seeding of empty lists are O(nlist x dim)
- * and stay with the caller (rassengine_amd/ivf.py). */
+ * and stay with the caller (rassengine_amd/ivf.py).  That caller's training leaves tombstoned rows out: it sets their
+ * entries of d_assign to -1 before rass_kmeans_accumulate (which skips a list outside [0, nlist)) and draws no seed,
+ * re-seed or repair row among them.  The two primitives themselves do not look at the tags. */
 int rass_kmeans_assign(rass_index_t* idx, int64_t first_block, int64_t block_step,
                        int64_t n_blocks, const float* d_centroids_tile16, int nlist,
                        int32_t* d_assign, float* d_best);

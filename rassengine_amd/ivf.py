@@ -108,6 +108,20 @@ def _gather_rows(index: FlatIndex, rows, dev) -> torch.Tensor:
     return out
 
 
+def _live_sample(index: FlatIndex, step: int, n_blocks: int, dev) -> Optional[torch.Tensor]:
+    """Which entries of the strided sample are LIVE rows: device bool [n_blocks * 32], entry j speaking for the row a seed or
+    re-seed drawn at j would copy (``_sample_row`` clamped to the last row); None for an index without tombstones, which is
+    then trained exactly as before.  The k-means primitives compute a tombstoned row like any other (their contract); the
+    training leaves it out: an index that has seen many overwrites (delete + add) would otherwise put its centroids where
+    the stale rows are.  The mask is the tag column's own notion of a tombstone (``rass_index_keys_from_tag``)."""
+    n = index.rows
+    if index.count == n:
+        return None
+    live = index.group_keys_from_tag(0x7FFFFFFF)[:n] != index.KEY_NONE
+    rows = torch.clamp(_sample_row(torch.arange(n_blocks * BLOCK_ROWS, device=dev), step), max=n - 1)
+    return live[rows]
+
+
 def _repair(index: FlatIndex, cent: torch.Tensor, counts: torch.Tensor, best: torch.Tensor, step: int, n_blocks: int,
             g: torch.Generator, dev, dup_cos: float = 0.8) -> Tuple[torch.Tensor, int]:
     """One repair of a set of list means between two Lloyd iterations: lists whose means nearly coincide (cosine above
@@ -147,6 +161,9 @@ def _repair(index: FlatIndex, cent: torch.Tensor, counts: torch.Tensor, best: to
     w = torch.clamp(1.0 - best[:m_sample].float(), min=0.0) ** 2
     # (a row that no mean wins — it holds a NaN, its best is -inf — is never drawn)
     w = torch.where((rows_global < n) & (best[:m_sample] > float("-inf")), w, torch.zeros_like(w))
+    live = _live_sample(index, step, n_blocks, dev)
+    if live is not None:                                    # ... and neither is a tombstoned row
+        w = torch.where(live[:m_sample], w, torch.zeros_like(w))
     idx = torch.multinomial(w.cpu().double(), int(freed.numel()), replacement=False, generator=g)
     cent = cent.clone()
     cent[freed] = _gather_rows(index, torch.clamp(_sample_row(idx, step), max=n - 1).tolist(), dev)
@@ -176,11 +193,16 @@ def _lloyd(index: FlatIndex, cent: torch.Tensor, iters: int, step: int, n_blocks
     one = torch.empty((1, index.dim), dtype=torch.float32, device=dev)
     counts = torch.zeros((nlist,), dtype=torch.float32, device=dev)
     cent = _finite_rows(cent, None)                         # a seed may be a row that holds a NaN
+    live = _live_sample(index, step, n_blocks, dev) if iters > 0 else None
     for it in range(iters):
         assign, best, _slab = kmeans_assign(index, cent, 0, step, n_blocks, with_best=True)
         # A row that no centroid wins (its every score is NaN: best stays -inf) is placed in list 0 by the kernel, which is
-        # where a build keeps it, findable by nothing.  Training leaves it out: its NaN would end in list 0's mean.
-        assign = torch.where(best > float("-inf"), assign, torch.full_like(assign, -1))
+        # where a build keeps it, findable by nothing.  Training leaves it out: its NaN would end in list 0's mean.  A
+        # tombstoned row is left out as well: the kernel scores it like any other.
+        keep = best > float("-inf")
+        if live is not None:
+            keep = keep & live
+        assign = torch.where(keep, assign, torch.full_like(assign, -1))
         sums, counts = kmeans_accumulate(index, assign, nlist, 0, step, n_blocks)
         if world > 1:
             dist.all_reduce(sums, group=group)
@@ -189,8 +211,14 @@ def _lloyd(index: FlatIndex, cent: torch.Tensor, iters: int, step: int, n_blocks
         empty = counts == 0
         if bool(empty.any()):  # re-seed empty lists from (deterministic) sample rows; rank 0's win
             idx = torch.nonzero(empty).flatten()
+            live_h = None if live is None else live.cpu()
             for li in idx.tolist():
-                r = min(n - 1, ((li * 7919 + 13) % n_blocks) * step * BLOCK_ROWS + (li % BLOCK_ROWS))
+                j = ((li * 7919 + 13) % n_blocks) * BLOCK_ROWS + (li % BLOCK_ROWS)
+                if live_h is not None and not bool(live_h[j]):      # the next sample entry that is a live row, cyclically
+                    nxt = torch.nonzero(torch.roll(live_h, -j)).flatten()
+                    j = (j + int(nxt[0])) % live_h.numel() if nxt.numel() else j
+                    live_h[j] = False                                # two empty lists do not move on to the same row
+                r = min(n - 1, _sample_row(j, step))
                 new[li] = _rows_chunk(index, int(r), 1, one)[0]
             if world > 1:
                 dist.broadcast(new, src=0, group=group)
@@ -242,7 +270,8 @@ def train_centroids(index: FlatIndex, nlist: int, train_rows: int = 0, iters: in
                     group: Optional[dist.ProcessGroup] = None, seeding: str = "repair", fine_factor: int = 4) -> torch.Tensor:
     """Spherical k-means over a strided sample of the index's 32-row blocks (every ``step``-th block, about
     ``train_rows`` rows; 0 = all rows for one level, 64 rows per fine list for two); returns unit centroids [nlist, dim] on
-    the GPU, identical on every rank.
+    the GPU, identical on every rank.  Tombstoned rows are left out: they are no seeds, no re-seeds, no repair draws, and
+    they add to no list's mean (``_live_sample``).
 
     ``fine_factor`` > 1 (default 4) trains in TWO LEVELS: K' = fine_factor x nlist fine lists from K' random sample rows
     (plain Lloyd, ``iters`` iterations), then the fine means — each weighted by its list's size — are grouped into nlist
@@ -277,6 +306,11 @@ def train_centroids(index: FlatIndex, nlist: int, train_rows: int = 0, iters: in
     g = torch.Generator(device="cpu")
     g.manual_seed(seed)
     sample = min(n_blocks * BLOCK_ROWS, n)
+    # tombstoned rows are no training rows: seeds are drawn from the live sample entries, and the levels are sized by them
+    live = _live_sample(index, step, n_blocks, dev)
+    seeds_from = None if live is None else torch.nonzero(live[:sample]).flatten().cpu()
+    if seeds_from is not None:
+        sample = int(seeds_from.numel())
     # every rank must train the SAME number of first-level lists in the same mode (the broadcast of the seeds and the
     # all-reduce of sums / counts carry [k_first, dim] tensors): size them from the SMALLEST rank's sample, not from the
     # rank-local row count (shards hold unequal rows)
@@ -294,6 +328,8 @@ def train_centroids(index: FlatIndex, nlist: int, train_rows: int = 0, iters: in
     with _engine_on_torch_stream(index):
         # seeds: distinct sample rows (deterministic for a seed); every rank starts from rank 0's
         pick = torch.randperm(sample, generator=g)[:k_first]
+        if seeds_from is not None:
+            pick = seeds_from[pick]
         cent = _gather_rows(index, torch.clamp(_sample_row(pick, step), max=n - 1).tolist(), dev)
         if world > 1:
             dist.broadcast(cent, src=0, group=group)
