@@ -834,8 +834,10 @@ int rass_ivf_load(rass_engine_t* eng, const char* path, rass_ivf_t** out);
 int64_t rass_ivf_rows(const rass_ivf_t* ivf);
 int rass_ivf_nlist(const rass_ivf_t* ivf);
 int rass_ivf_dtype(const rass_ivf_t* ivf); /* rass_dtype of the row slab; -1 for NULL */
-/* Same contract as rass_index_search; nprobe >= 1 lists per query (capped at
- * nlist; nprobe > 32 selects by a per-query score threshold, ties may add lists).
+/* Same contract as rass_index_search; nprobe >= 1 lists per query, capped at nlist.
+ * nprobe <= 32 probes the first nprobe lists by (centroid score desc, list id asc); nprobe > 32
+ * probes every list whose coarse score is >= the nprobe-th best, so lists that tie with the
+ * nprobe-th are all probed (tests/test_gpu_ivf_probe.py pins both rules).
  * *scanned_rows (may be NULL) receives the rows the fine scans touched. */
 int rass_ivf_search(rass_ivf_t* ivf, const float* queries, int nq, int k,
                     int nprobe, const int32_t* q_filter, float* out_scores,
@@ -848,7 +850,9 @@ int rass_ivf_search_device(rass_ivf_t* ivf, const float* d_queries, int nq,
  * (the coarse lists are merged inside it) and ONE grouped merge for the whole batch — 4 + G launches instead of 5 G,
  * which is what an IVF probe at nprobe 1-2 (where two-level training puts recall 1.0) is bound by.  Outputs contiguous
  * [nq][k]; d_scanned_per_group (may be NULL): int64 per launch group, the rows its fine scan touched.  nprobe > 32 runs
- * group by group.  (The reference's k-NN lookup under concurrent load: app/main.py:1552; BASELINE configs[4].) */
+ * group by group, and so does an IVF whose list masks and coarse candidates exceed the plan workgroup's LDS
+ * (nlist + 64 * wpg * nprobe > 39 936 words, wpg = min(8, 256 / nprobe) coarse lists per query: above 23 552 lists at
+ * nprobe 32).  (The reference's k-NN lookup under concurrent load: app/main.py:1552; BASELINE configs[4].) */
 int rass_ivf_search_device_batch(rass_ivf_t* ivf, const float* d_queries, int nq, int k, int nprobe,
                                  const int32_t* d_q_filter, float* d_out_scores, int64_t* d_out_ids,
                                  int64_t* d_scanned_per_group);

@@ -698,6 +698,13 @@ static IvfBatchView ivf_batch_layout(unsigned char* base, const rass_ivf* v, int
     return L;
 }
 
+// Coarse workgroups per launch group of the batched probe: each leaves a top-np list per query, and the plan kernel merges a
+// query's wpg * np <= 256 candidates.
+static int ivf_batch_wpg(int nlist, int np) {
+    const int n_ctiles = (nlist + 31) / 32;
+    return std::max(1, std::min(8, std::min(n_ctiles, 256 / np)));
+}
+
 // A whole batch of launch groups (nq <= 1 024 queries) of an IVF probe with 4 + G launches instead of 5 G: ONE normalise,
 // ONE grouped coarse scan (kFlatGroups: every group's 32 queries over the centroid slab, 8 workgroups per group), ONE plan
 // launch (a workgroup per group; the coarse lists are merged inside it), the G fine scans over their groups' work lists,
@@ -710,8 +717,7 @@ static int ivf_search_batch_locked(rass_ivf_t* v, const float* d_queries, int nq
     hipStream_t st = eng->stream;
     const int np = std::min(nprobe, v->nlist);
     const int G = (nq + RASS_MAX_QBATCH - 1) / RASS_MAX_QBATCH;
-    const int n_ctiles = (v->nlist + 31) / 32;
-    const int wpg = std::max(1, std::min(8, std::min(n_ctiles, 256 / np)));      // coarse workgroups per group
+    const int wpg = ivf_batch_wpg(v->nlist, np);                                   // coarse workgroups per group
     const int64_t stride = v->stride;
     // fine-scan workgroups per group.  fp32 slab: ALL groups' fine scans are one launch (kIvfGroups) — the more groups, the
     // fewer workgroups each (32 at 32 groups: 1 024 in all, dispatched in group order, no launch boundary between groups);
@@ -785,8 +791,11 @@ int rass_ivf_search_device_batch(rass_ivf_t* v, const float* d_queries, int nq, 
     int rc = set_device(v->eng);
     if (rc != RASS_OK) return rc;
     std::lock_guard<std::mutex> lk(v->eng->mu);
-    if (std::min(nprobe, v->nlist) > RASS_MAX_K) {
-        // deep probes: the threshold path, group by group
+    const int np = std::min(nprobe, v->nlist);
+    if (np > RASS_MAX_K || rass::plan_lds_bytes(v->nlist, ivf_batch_wpg(v->nlist, np), np) > rass::kPlanMaxLdsBytes) {
+        // group by group: deep probes (the threshold path), and an IVF of so many lists that the batched plan's masks and
+        // candidates do not fit one CU's LDS (nlist + 64 * wpg * np > 39 936: above 23 552 lists at nprobe 32).  Either way
+        // the answer is rass_ivf_search_device's on each group of 32.
         for (int g = 0; g * RASS_MAX_QBATCH < nq; ++g) {
             const int b = std::min(RASS_MAX_QBATCH, nq - g * RASS_MAX_QBATCH);
             rc = ivf_search_locked(v, d_queries + (int64_t)g * RASS_MAX_QBATCH * v->dim, b, k, nprobe,

@@ -20,7 +20,7 @@ namespace rass {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-constexpr int kPlanThreads = 1024;
+constexpr int kPlanThreads = 1024;   // plan_lds_bytes (kernels.h) counts this many scan-scratch words
 
 // One workgroup.  probe_ids: [nq][nprobe] list ids from the coarse scan (-1 = none).
 __global__ __launch_bounds__(kPlanThreads) void plan_probe_kernel(const int64_t* __restrict__ probe_ids, int nq,
@@ -112,7 +112,8 @@ hipError_t launch_plan_probe(const int64_t* probe_ids, int nq, int nprobe, int n
                              int tile_rows) {
     if (nq < 1 || nq > 32 || nprobe < 1 || nlist < 1 || nlist > 32768) return hipErrorInvalidValue;
     if (tile_rows != 32 && tile_rows != 64) return hipErrorInvalidValue;   // the fp32 scan's tile / the bf16 scan's
-    const size_t lds = ((size_t)nlist + kPlanThreads) * sizeof(uint32_t);
+    const size_t lds = plan_lds_bytes(nlist, 0, 0);
+    if (lds > kPlanMaxLdsBytes) return hipErrorInvalidValue;
     static size_t attr = 0;
     if (lds > attr && lds > 48 * 1024) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&plan_probe_kernel),
@@ -241,7 +242,8 @@ hipError_t launch_plan_probe_groups(const float* cpart_scores, const int64_t* cp
     if (groups < 1 || nprobe < 1 || nprobe > 32 || n_clists < 1 || n_clists * nprobe > 256 || nlist < 1 || nlist > 32768)
         return hipErrorInvalidValue;
     if (tile_rows != 32 && tile_rows != 64) return hipErrorInvalidValue;
-    const size_t lds = ((size_t)nlist + kPlanThreads + 2 * 32 * (size_t)n_clists * nprobe) * sizeof(uint32_t);
+    const size_t lds = plan_lds_bytes(nlist, n_clists, nprobe);
+    if (lds > kPlanMaxLdsBytes) return hipErrorInvalidValue;   // more than a CU has: the caller plans group by group instead
     static size_t attr = 0;
     if (lds > attr && lds > 48 * 1024) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&plan_probe_groups_kernel),

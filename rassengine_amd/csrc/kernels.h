@@ -457,6 +457,14 @@ hipError_t launch_kmeans_accumulate(const float* rows, int64_t stride, int64_t f
                                     int dim, int nlist, hipStream_t stream);
 
 // ---- IVF (ivf.hip)
+// Dynamic LDS of the plan kernels, in one place for the launchers and the host code that chooses between them: [nlist] query
+// masks + [1 024] scan scratch, and for the batched plan (n_clists > 0) the scores and ids of the 32 queries' n_clists * nprobe
+// coarse candidates.  A workgroup gets at most kPlanMaxLdsBytes, the LDS of one CU: the plain plan fits at every nlist the IVF
+// takes (135 168 bytes at 32 768), the batched plan with 256 candidates only up to nlist 23 552 (200 704 bytes at 32 768).
+constexpr size_t kPlanMaxLdsBytes = 160 * 1024;
+constexpr size_t plan_lds_bytes(int nlist, int n_clists, int nprobe) {
+    return ((size_t)nlist + 1024 + 2 * 32 * (size_t)n_clists * (size_t)nprobe) * 4;
+}
 hipError_t launch_plan_probe(const int64_t* probe_ids, int nq, int nprobe, int nlist, const int32_t* list_tile0,
                              const int32_t* list_len, int32_t* work_tile, int32_t* work_rows, uint32_t* work_mask,
                              int32_t* n_work, int64_t* scanned_rows, hipStream_t stream,
