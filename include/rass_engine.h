@@ -653,6 +653,12 @@ int rass_index_candidates_exact_device(rass_index_t* idx, const float* d_queries
  * RASS_SCAN_SAMPLE_FLOOR=0). */
 int rass_index_sample_floor_device(rass_index_t* idx, const float* d_queries, int nq, int k, const int32_t* d_q_filter,
                                    int32_t* d_out_rows, float* d_out_scores);
+/* Beside it: the ONE floor per query that the batch computes from those 32 scores, once per call, for its step-kernel launches
+ * ([nq] floats): the largest value of the top 20 bits of the scores' order-preserving keys that at least k of the query's 32
+ * scores reach — at most the k-th largest of them, below it by < 2^-11 of its value — and -inf where fewer than k of them are
+ * above -inf.  Same conditions, same RASS_ERR_UNSUPPORTED. */
+int rass_index_step_floors_device(rass_index_t* idx, const float* d_queries, int nq, int k, const int32_t* d_q_filter,
+                                  float* d_out_floors);
 /* The candidate lists of the active prefilter mode for <= 32 device queries, BEFORE the exact re-rank: [nq][32] candidate
  * scores (bf16: fp32-accumulated dot of the bf16-rounded operands; int8: as above) and LOCAL rows, (score desc, row asc),
  * -inf / -1 past the end.  Parity hook of the integer path (tests compare it with the oracle bit for bit); stream-ordered.

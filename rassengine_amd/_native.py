@@ -162,6 +162,8 @@ SIGNATURES = {
                                                           ctypes.c_void_p]),
     "rass_index_sample_floor_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
                                                       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "rass_index_step_floors_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
+                                                     ctypes.c_void_p, ctypes.c_void_p]),
     "rass_index_save": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p]),
     "rass_index_load": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_char_p, c_void_pp]),
     "rass_index_fill_synthetic": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_uint64,

@@ -165,6 +165,7 @@ struct BatchView {
     unsigned char* rep_qfrag;      // the fp32 batch's sample stage (sample_rep.hip): [groups][32][stride] bf16 query fragments,
     unsigned char* rep_part;       // [groups][32][kMaxSampleGroups] (score, row) pairs
     int* rep_row;                  // and the representatives [groups][32][32]
+    float* step_floor;             // [groups][32]: one sample floor per query, for the step kernel (launch_step_floors)
     size_t total;
     size_t part_per_group;         // elements of one group's [grid][32][k] lists
     float* group_sample(int g) const { return sample_best + (int64_t)g * 32 * rass::kMaxSampleGroups; }
@@ -442,6 +443,7 @@ bool i8_sample_floor(int64_t rows, int grid);     // RASS_I8_SAMPLE_FLOOR, read 
 enum { kBatchSampleGroups = 0, kBatchSampleF32 = 1, kBatchSampleRep = 2 };
 int scan_batch_sample_mode();                   // RASS_SCAN_BATCH_SAMPLE, read per call: a kBatchSample* value
 bool scan_batch_pair();                           // RASS_SCAN_BATCH_PAIR, read once
+bool scan_batch_step();                           // RASS_SCAN_BATCH_STEP, read per call
 bool ivf_batch_one_launch();                      // RASS_IVF_BATCH_FINE, read per call
 
 // Workgroups of a scan over `tiles` tiles whose merge takes `lists_kept_per_wg` entries per query from each of them: one per
@@ -450,7 +452,8 @@ bool ivf_batch_one_launch();                      // RASS_IVF_BATCH_FINE, read p
 int scan_grid(int64_t tiles, int lists_kept_per_wg, int n_cus);
 
 // The optional event bracket of rass_engine_kernel_timing_*: records the before / after events around `launch` (which
-// returns a status: HIP_RC of the launcher's) and counts it; extra_groups = launch groups beyond one that it served (a pair pass: 1).
+// returns a status: HIP_RC of the launcher's) and counts it; extra_groups = launch groups beyond one that it served (a pair pass: 1;
+// a step-kernel launch over `pairs` pairs: 2 * pairs - 1).
 // eng = nullptr: no bracket.
 template <class F>
 int timed_launch(rass_engine* eng, hipStream_t st, F&& launch, int extra_groups = 0) {

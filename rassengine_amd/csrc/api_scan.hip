@@ -79,6 +79,13 @@ bool scan_batch_pair() {
     return on;
 }
 
+// RASS_SCAN_BATCH_STEP=0: the fused fp32 batch launches one scan per pair of full groups instead of one per run of up to
+// kStepMaxPairs pairs (scan_step.hip; the A/B and the tests' reference; results do not depend on it).  Read per call.
+bool scan_batch_step() {
+    const char* e = getenv("RASS_SCAN_BATCH_STEP");
+    return !(e && e[0] == '0');
+}
+
 // RASS_IVF_BATCH_FINE=groups: one fine-scan launch per group (the A/B of kIvfGroups); default: one launch for all groups.  Read per call.
 bool ivf_batch_one_launch() {
     const char* e = getenv("RASS_IVF_BATCH_FINE");
@@ -121,6 +128,7 @@ BatchView batch_layout(unsigned char* base, int groups, int grid, int k, int64_t
     L.rep_qfrag = candidates ? nullptr : c.take<unsigned char>((size_t)groups * 32 * stride * 2);
     L.rep_part = candidates ? nullptr : c.take<unsigned char>((size_t)groups * 32 * rass::kMaxSampleGroups * 8);
     L.rep_row = candidates ? nullptr : c.take<int>((size_t)groups * 32 * 32 * sizeof(int));
+    L.step_floor = candidates ? nullptr : c.take<float>((size_t)groups * 32 * sizeof(float));
     L.total = c.off;
     return L;
 }

@@ -199,7 +199,14 @@ int scan_launch_batch(rass_index* idx, const FlatRequest& r, int64_t gs, int64_t
     // Consecutive FULL groups go two per corpus pass (scan_topk_f32_pair_kernel: 64 queries per launch, the lists of both
     // groups written where the two launches would write them, bit for bit the same); an odd last full group and a ragged
     // last group keep the 32-query kernel.  RASS_SCAN_BATCH_PAIR=0: one launch per group (the A/B).
+    // Runs of 2..kStepMaxPairs consecutive pairs go to ONE launch of the step kernel (scan_step.hip: the pair kernel's loop over
+    // pairs x tiles, the same lists bit for bit; a 4 096-query call is four launches, which bounds a launch's duration on a
+    // 10 M-row slab); a single pair left over keeps the pair kernel.  The step kernel reads one ready-made floor per query:
+    // launch_step_floors, once, outside the timing brackets as the sample stage is.  RASS_SCAN_BATCH_STEP=0: one launch per pair.
     const bool pairs = scan_batch_pair() && rass::scan_pair_supported_stride(stride);
+    const int n_pairs = pairs ? nq / (2 * RASS_MAX_QBATCH) : 0;
+    const bool step = scan_batch_step() && n_pairs >= 2 && grid <= (rows + 31) / 32;
+    if (step && sample) HIP_TRY(rass::launch_step_floors(L.sample_best, sample_wgs, n_pairs * 64, k, L.step_floor, st));
     for (int g = 0; g < groups; ++g) {
         rass::ScanArgs a = group_args(g);
         if (sample && a.nq > 16) {
@@ -207,11 +214,20 @@ int scan_launch_batch(rass_index* idx, const FlatRequest& r, int64_t gs, int64_t
             a.sample_groups = sample_wgs;
         }
         const bool pair = pairs && a.nq == RASS_MAX_QBATCH && (g + 2) * RASS_MAX_QBATCH <= nq;
+        const int run = pair && step ? std::min(rass::kStepMaxPairs, n_pairs - g / 2) : 1;   // pairs start at even groups
         if (pair) {
             a.nq = 2 * RASS_MAX_QBATCH;
             a.q_group_stride = 32 * stride;
             a.part_group_stride = (int64_t)L.part_per_group;
             a.xcd_skew = scan_xcd_skew(a.nq, grid, eng->n_cus);
+        }
+        if (run >= 2) {
+            a.sample_best = nullptr, a.sample_groups = 0;
+            a.step_floors = sample ? L.step_floor + g * 32 : nullptr;
+            a.nq_total = 64 * run;
+            rc = timed_launch(eng, st, [&] { return HIP_RC(rass::launch_scan_topk_f32_step(a, grid, st)); }, /*extra_groups=*/2 * run - 1);
+            g += 2 * run - 1;   // this launch served 2 * run groups
+        } else if (pair) {
             rc = timed_launch(eng, st, [&] { return HIP_RC(rass::launch_scan_topk_f32_pair(a, grid, st)); }, /*extra_groups=*/1);
             ++g;   // this pass served two groups
         } else
@@ -225,8 +241,10 @@ int scan_launch_batch(rass_index* idx, const FlatRequest& r, int64_t gs, int64_t
 
 // The parity hook of the batch's sample stage (rass_index_sample_floor_device): the normalise launch and the stage as
 // scan_launch_batch enqueues them for this index, batch and k, then the representatives and their scores copied out.
+// d_floors != nullptr (rass_index_step_floors_device): the one floor per query the step kernel reads (launch_step_floors), [nq],
+// in place of the representatives.
 int sample_floor_hook(rass_index* idx, const float* d_queries, int nq, int k, const int32_t* d_q_filter, int32_t* d_rows,
-                      float* d_scores) {
+                      float* d_scores, float* d_floors = nullptr) {
     rass_engine* eng = idx->eng;
     hipStream_t st = eng->stream;
     const IndexView iv = index_view(idx, d_q_filter != nullptr, 0);
@@ -243,6 +261,11 @@ int sample_floor_hook(rass_index* idx, const float* d_queries, int nq, int k, co
     HIP_TRY(rass::launch_normalize_rows_f32(d_queries, idx->dim, L.q_padded, stride, nq, idx->dim, st, nq));
     HIP_TRY(rass::launch_sample_rep(iv.corpus, iv.row_tag, stride, plan.grid, L.q_padded, d_q_filter, nq, L.rep_qfrag, L.rep_part,
                                     L.rep_row, L.sample_best, st));
+    if (d_floors) {
+        HIP_TRY(rass::launch_step_floors(L.sample_best, 32, nq, k, L.step_floor, st));
+        HIP_TRY(hipMemcpyAsync(d_floors, L.step_floor, (size_t)nq * sizeof(float), hipMemcpyDeviceToDevice, st));
+        return RASS_OK;
+    }
     HIP_TRY(hipMemcpyAsync(d_rows, L.rep_row, (size_t)nq * 32 * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
     HIP_TRY(hipMemcpy2DAsync(d_scores, 32 * sizeof(float), L.sample_best, rass::kMaxSampleGroups * sizeof(float), 32 * sizeof(float),
                              (size_t)nq, hipMemcpyDeviceToDevice, st));
@@ -530,6 +553,18 @@ int rass_index_sample_floor_device(rass_index_t* idx, const float* d_queries, in
     int rc = set_device(eng);
     if (rc != RASS_OK) return rc;
     return sample_floor_hook(idx, d_queries, nq, k, d_q_filter, d_out_rows, d_out_scores);
+}
+
+int rass_index_step_floors_device(rass_index_t* idx, const float* d_queries, int nq, int k, const int32_t* d_q_filter,
+                                  float* d_out_floors) {
+    if (!idx || !d_queries || !d_out_floors) return fail(RASS_ERR_INVALID, "NULL argument");
+    if (nq < 1 || nq > RASS_MAX_DEVICE_BATCH) return fail(RASS_ERR_INVALID, "nq must be in [1, RASS_MAX_DEVICE_BATCH]");
+    if (int rc = check_k(k)) return rc;
+    rass_engine* eng = idx->eng;
+    std::lock_guard<std::mutex> lk(eng->mu);
+    int rc = set_device(eng);
+    if (rc != RASS_OK) return rc;
+    return sample_floor_hook(idx, d_queries, nq, k, d_q_filter, nullptr, nullptr, d_out_floors);
 }
 
 int rass_index_search_ex(rass_index_t* idx, const float* queries, int nq, int k, const int32_t* q_filter,

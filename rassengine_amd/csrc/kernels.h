@@ -74,7 +74,13 @@ struct ScanArgs {
     // threshold matches nothing).  range_count[q * kRangeCountStride] (zeroed by the caller) ends as the exact number of
     // hits; the first range_cap of them to arrive are stored, unsorted, at range_hits[q * range_cap + ..] as (score bits,
     // row of this slab).  launch_range_finish turns that into the answer.
-    const float* range_thr = nullptr;
+    union {
+        const float* range_thr = nullptr;
+        // The step kernel (scan_step.hip) only, never together with a range or group-count scan: floor[q] for every query of
+        // the launch, ready-made (launch_step_floors: what the prologue of a scan selects from sample_best), or nullptr = none.
+        // It shares range_thr's slot for the reason group_keys shares range_hits' (below).
+        const float* step_floors;
+    };
     unsigned* range_count = nullptr;
     union {
         uint2* range_hits = nullptr;
@@ -134,6 +140,13 @@ hipError_t launch_scan_topk_f32(const ScanArgs& a, int grid, hipStream_t stream)
 // part_* + part_group_stride.  Same scores and lists, bit for bit, as the two launches it replaces.  No EXT, no work list.
 bool scan_pair_supported_stride(int64_t row_stride);
 hipError_t launch_scan_topk_f32_pair(const ScanArgs& a, int grid, hipStream_t stream);
+// A run of 1..kStepMaxPairs consecutive pairs in ONE launch (scan_step.hip, scan_topk_f32_step_kernel): `a` as for the pair
+// launch of the run's first pair, except that a.nq_total = 64 * pairs, a.sample_best is not read and the floors come ready-made,
+// one per query of the run, from a.step_floors (launch_step_floors; nullptr: none).  Pair j reads and writes where the pair
+// launch with q_padded + 2 j * q_group_stride, q_filter + 64 j, part_* + 2 j * part_group_stride would: the same lists, bit for
+// bit.  grid <= the slab's tiles (scan_grid gives that for a slab with a row).
+constexpr int kStepMaxPairs = 16;
+hipError_t launch_scan_topk_f32_step(const ScanArgs& a, int grid, hipStream_t stream);
 
 // [n_lists][nq][k] sorted candidate lists -> [nq][k]; n_lists * k <= kMergeMaxCandidates.
 constexpr int kMergeMaxCandidates = 8192;
@@ -326,6 +339,10 @@ bool sample_rep_supported(int64_t stride, int grid);   // stride 128 * {1..8}, g
 hipError_t launch_sample_rep(const float* slab, const int32_t* row_tag, int64_t stride, int grid, const float* q_padded,
                              const int32_t* q_filter, int nq, void* q_frag, void* rep_part, int* rep_row, float* sample_best,
                              hipStream_t stream);
+// One floor per query, once per batch (sample_rep.hip, step_floors_kernel): floors[q] = what the prologue of a scan selects from
+// the first sample_groups entries of sample_best[q][kMaxSampleGroups] — the largest value whose top kFloorBits key bits at least
+// k entries reach, -inf when fewer than k entries are above -inf.  q = 0..nq-1, whichever stage filled sample_best.
+hipError_t launch_step_floors(const float* sample_best, int sample_groups, int nq, int k, float* floors, hipStream_t stream);
 // out_*_group_stride (elements; 0 = contiguous [nq][k]): query q's results go to out + (q / 32) * group_stride + (q % 32) * k
 hipError_t launch_rerank_f32(const float* slab, int64_t stride, const float* q_padded, const int64_t* cand_rows, int nq,
                              int n_cand, int k, int64_t id_base, float* out_scores, int64_t* out_ids,

@@ -18,6 +18,9 @@
 // is needed.  The K slots of a bf16 MFMA may hold any columns as long as A and B agree: a lane's fp32 chunks 2 ks and
 // 2 ks + 1 of the tile16 slab ([g][row][4] floats, columns 16 j + 4 g + i) make A's 8 slots of k-group g at k-step ks, and
 // the query fragment carries the same 8 columns.
+//
+// Also here: step_floors_kernel, which turns a query's sample_best entries (this stage's, or a sample pass's) into its ONE
+// floor, once per batch call, for the step kernel (scan_step.hip).
 
 #include <hip/hip_runtime.h>
 #include <limits.h>
@@ -264,6 +267,42 @@ hipError_t launch_sample_rep(const float* slab, const int32_t* row_tag, int64_t 
         default: return hipErrorInvalidValue;
     }
 #undef RASS_REP_CASE
+    return hipGetLastError();
+}
+
+// One floor per query, once per batch.  The scans of scan_topk.hip select a query's floor from its sample_best entries in their
+// prologue: every wave of every workgroup of every launch, 2 * kFloorBits ballot rounds over kMaxSampleGroups slots for each
+// of its queries — the same 1 024 floors found by 256 workgroups in 16 launches of a step.  Here a wave takes one query and
+// does that selection once, in the same words: score_key of every entry above -inf (0 otherwise), the largest value of the top
+// kFloorBits key bits that at least k keys reach, key_score of it, -inf when there is none.  The step kernel (scan_step.hip)
+// reads floors[q] where the others select.
+__global__ __launch_bounds__(256) void step_floors_kernel(const float* __restrict__ sample_best, int sample_groups, int nq, int k,
+                                                          float* __restrict__ floors) {
+    const int lane = lane_id();
+    const int q = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (q >= nq) return;   // wave-uniform
+    unsigned key[kMaxSampleGroups / 64];
+#pragma unroll
+    for (int j = 0; j < kMaxSampleGroups / 64; ++j) {
+        const int grp = lane + 64 * j;
+        const float v = grp < sample_groups ? sample_best[(int64_t)q * kMaxSampleGroups + grp] : -INFINITY;
+        key[j] = v == -INFINITY ? 0u : score_key(v);
+    }
+    unsigned T = 0;
+#pragma unroll 1
+    for (int b = 31; b >= 32 - kFloorBits; --b) {
+        const unsigned cand = T | (1u << b);
+        int c = 0;
+#pragma unroll
+        for (int j = 0; j < kMaxSampleGroups / 64; ++j) c += __popcll(__ballot(key[j] >= cand));
+        T = c >= k ? cand : T;
+    }
+    if (lane == 0) floors[q] = T ? key_score(T) : -INFINITY;
+}
+
+hipError_t launch_step_floors(const float* sample_best, int sample_groups, int nq, int k, float* floors, hipStream_t stream) {
+    if (sample_groups < 1 || sample_groups > kMaxSampleGroups || nq < 1 || k < 1) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(step_floors_kernel, dim3((nq + 3) / 4), dim3(256), 0, stream, sample_best, sample_groups, nq, k, floors);
     return hipGetLastError();
 }
 

@@ -355,6 +355,25 @@ class FlatIndex:
         self.engine.synchronize()
         return rows, scores
 
+    def step_floors_device(self, d_queries, k: int, q_filter=None):
+        """Beside sample_floor_device: the one floor per query (f32 [nq], a torch tensor) the batch computes from those 32
+        scores for its step-kernel launches (include/rass_engine.h)."""
+        import torch
+        nq = int(d_queries.shape[0])
+        assert d_queries.is_cuda and d_queries.dtype == torch.float32 and d_queries.is_contiguous() and d_queries.shape[1] == self.dim
+        dev = d_queries.device
+        floors = torch.empty((nq,), dtype=torch.float32, device=dev)
+        f = None
+        if q_filter is not None:
+            f = torch.as_tensor(np.ascontiguousarray(q_filter, dtype=np.int32)).to(dev)
+        torch.cuda.current_stream().synchronize()     # the engine works on its own stream
+        N.check("rass_index_step_floors_device",
+                self._L.rass_index_step_floors_device(self._h, ctypes.c_void_p(d_queries.data_ptr()), nq, int(k),
+                                                      ctypes.c_void_p(f.data_ptr()) if f is not None else None,
+                                                      ctypes.c_void_p(floors.data_ptr())))
+        self.engine.synchronize()
+        return floors
+
     def candidates_device(self, d_queries, q_filter=None):
         """The active prefilter mode's candidate lists BEFORE the exact re-rank, for <= 32 queries on the device (a torch
         CUDA fp32 tensor [nq, dim]): (scores f32 [nq, 32], LOCAL rows i64 [nq, 32]) as torch tensors.  A parity hook: the
