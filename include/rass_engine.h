@@ -462,6 +462,74 @@ int rass_index_allow_from_attr_clauses(rass_index_t* idx, const int32_t* clauses
  * may span several bitmaps laid out alike.  d_dst and d_src must not overlap.  Stream-ordered on the engine's stream. */
 int rass_index_allow_combine(rass_index_t* idx, uint32_t* d_dst, const uint32_t* d_src, int64_t words, int op);
 
+/* BOOSTED search: the exact top-k of
+ *     fused = boost[q] * T(cos) + bonus[q][row]
+ * over a flat index — an OpenSearch bool.should around a knn clause: the knn clause's boost, and per row the sum of what the
+ * other matching clauses are worth (text hits, recency ranges, per-document priors, decay), whatever their number or sign.
+ * The bonus is a dense fp32 COLUMN in device memory, d_bonus = float[n_bonus][bonus_stride]: n_bonus = nq (column q belongs to
+ * query q) or 1 (ONE column shared by every query, read in place).  Rows at or past bonus_rows (<= bonus_stride) read 0, so
+ * rows appended after a column was built carry no bonus.  boost: HOST float[nq], or NULL = 1.0 for every query; every value
+ * must be finite (negative, zero and fractional boosts are fine).  transform RASS_BOOST_RAW: T(s) = s; RASS_BOOST_OPENSEARCH:
+ * T(s) = 1 / (2 - s), the k-NN plugin's cosinesimil score.
+ * ARITHMETIC, all fp32: s is the flat scan's cosine, bit for bit what rass_index_search_ex reports for the row; T's
+ * subtraction and division, the product boost * T and the sum with the bonus are each ONE correctly rounded operation, in that
+ * order, never contracted into an fma.
+ * A row RANKS for query q when it is live, passes the filter exactly as in rass_index_search_ex, has s > -inf (the rule under
+ * "Scores that are not finite": a NaN or -inf cosine drops the row whatever its bonus) and has fused > -inf — so a bonus of
+ * -inf or NaN EXCLUDES the row, which is how a row bitmap composes with the column (rass_index_bonus_mask).  +inf is out of
+ * scope, as everywhere.  out_scores / out_ids are [nq][k]: fused descending, ties by row ordinal ascending, (-inf, -1) past
+ * the end; ids as rass_index_search_ex reports them.
+ * One corpus pass per launch group of RASS_MAX_QBATCH queries whatever the column holds; every tile is streamed; no sample
+ * floor (a floor is only valid under the score it was sampled with).  1 <= k <= RASS_MAX_K_MULTIPASS (k > RASS_MAX_K in passes
+ * of RASS_MAX_K chained on the device under the continuation bound, taken on the fused score); 0 <= nq <=
+ * RASS_MAX_DEVICE_BATCH.  Outside those, n_bonus neither 1 nor nq, bonus_rows outside [0, bonus_stride], a non-finite boost, an
+ * unknown transform, or a launch group whose columns span 2 GiB or more: RASS_ERR_INVALID, nothing is launched and the outputs
+ * are untouched.  fp32 indices with dim <= 1024: a bf16 index or a wide-row index answers RASS_ERR_UNSUPPORTED.  The prefilter
+ * mode is ignored.  IVF probes, cross-index batches and the sharded front have no boosted form.
+ * A column names row ordinals of ONE layout of the index (rass_index_layout_epoch).  Thread-safety as rass_index_search_ex. */
+#define RASS_BOOST_RAW 0
+#define RASS_BOOST_OPENSEARCH 1
+int rass_index_search_boosted(rass_index_t* idx, const float* queries, int nq, int k,
+                              const float* boost, int transform,
+                              const float* d_bonus, int n_bonus, int64_t bonus_rows, int64_t bonus_stride,
+                              const int32_t* q_filter, const int32_t* q_filter_mask,
+                              float* out_scores, int64_t* out_ids);
+/* Device-resident variant: every pointer is device memory (d_boost too; its values are the caller's to keep finite), the call
+ * is stream-ordered, nothing is synchronised and nothing is read back; every pass of a k > RASS_MAX_K search is enqueued by
+ * the one call.  Ids are id_base + row (ignored on an index with caller-assigned ids, which are reported). */
+int rass_index_search_boosted_device(rass_index_t* idx, const float* d_queries, int nq, int k,
+                                     const float* d_boost, int transform,
+                                     const float* d_bonus, int n_bonus, int64_t bonus_rows, int64_t bonus_stride,
+                                     const int32_t* d_q_filter, const int32_t* d_q_filter_mask,
+                                     int64_t id_base, float* d_out_scores, int64_t* d_out_ids);
+/* COLUMN BUILDERS.  They work on a caller-owned DEVICE block d_bonus = float[n_bonus][stride], stride a multiple of 32 and >=
+ * the index's rows at the call, 1 <= n_bonus <= RASS_MAX_DEVICE_BATCH.  Zero-filling is the caller's (hipMemsetAsync on the
+ * engine's stream).  Every value is built from separately rounded fp32 adds in a stated order: a host restatement reproduces a
+ * column word for word.  All are stream-ordered on the engine's stream; host arrays may be reused when a call returns.
+ * _scatter: bonus[q_of[i]][rows[i]] += values[i] for the n HOST triples.  The (column, row) pairs must be unique within a call:
+ *   duplicates, a column outside [0, n_bonus) or a row outside [0, rows) are RASS_ERR_INVALID and nothing is written (sum
+ *   duplicates first).  _scatter_device takes DEVICE arrays and checks nothing of their contents: uniqueness and range are the
+ *   caller's duty (each cell has one writer; no atomics).
+ * _from_attr_clauses: weighted predicates over the attribute columns.  `clauses` is a HOST array int32[n_clauses][5] = {query,
+ *   col, lo, hi, negate} with rass_index_allow_from_attr_clauses' semantics, RASS_ATTR_MISSING included; weights[i] is clause
+ *   i's fp32 weight.  Per (query, row): b = 0 (op RASS_BONUS_REPLACE) or the cell's value (RASS_BONUS_ADD), then b = b +
+ *   weight for every clause of that query that holds, in LIST order.  n_bonus = nq, or 1 for a shared column whose clauses all
+ *   name query 0; at most RASS_MAX_ATTR_CLAUSES clauses per query per call.  Rows [0, rows) of every column are written,
+ *   tombstoned rows too (they never rank); cells at or past the row count are left alone.
+ * _mask: bonus[q][r] = -inf where bit r of bitmap q is clear (d_allow = uint32[n_bitmaps][words] as
+ *   rass_index_search_allowed_device takes it, n_bitmaps = n_bonus or 1, words >= ceil(rows / 32)): a `where` filter inside a
+ *   boosted search, without another scan mode. */
+#define RASS_BONUS_REPLACE 0
+#define RASS_BONUS_ADD 1
+int rass_index_bonus_scatter(rass_index_t* idx, const int32_t* q_of, const int64_t* rows, const float* values, int64_t n,
+                             float* d_bonus, int n_bonus, int64_t stride);
+int rass_index_bonus_scatter_device(rass_index_t* idx, const int32_t* d_q_of, const int64_t* d_rows, const float* d_values,
+                                    int64_t n, float* d_bonus, int n_bonus, int64_t stride);
+int rass_index_bonus_from_attr_clauses(rass_index_t* idx, const int32_t* clauses, const float* weights, int64_t n_clauses,
+                                       int nq, int n_bonus, float* d_bonus, int64_t stride, int op);
+int rass_index_bonus_mask(rass_index_t* idx, float* d_bonus, int n_bonus, int64_t stride, const uint32_t* d_allow,
+                          int n_bitmaps, int64_t words);
+
 /* Semantic TERMS AGGREGATION: per-group hit counts above a min_score — OpenSearch's `"aggs": {"x": {"terms": {"field": ...}}}`
  * under a k-NN clause with a min_score, with a `cardinality` and the hit total thrown in.  The group of a row is a bit field
  * of its tag, as in rass_index_search_grouped.  A row is a HIT of query q when it is live, passes q_filter (NULL, exact, or

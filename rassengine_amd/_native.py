@@ -37,6 +37,8 @@ RASS_MAX_ATTR_CLAUSES = 64
 RASS_ATTR_ALL, RASS_ATTR_ANY = 0, 1
 RASS_ATTR_REPLACE, RASS_ATTR_AND, RASS_ATTR_OR, RASS_ATTR_ANDNOT = 0, 1, 2, 3
 RASS_KEY_NONE = -1
+RASS_BOOST_RAW, RASS_BOOST_OPENSEARCH = 0, 1
+RASS_BONUS_REPLACE, RASS_BONUS_ADD = 0, 1
 RASS_MAX_KEY_EDGES = 4097
 
 c_float_p = ctypes.POINTER(ctypes.c_float)
@@ -127,6 +129,21 @@ SIGNATURES = {
     "rass_index_allow_from_attr_clauses": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int,
                                                           ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int64]),
     "rass_index_allow_combine": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int]),
+    "rass_index_search_boosted": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
+                                                 ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int64,
+                                                 ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "rass_index_search_boosted_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
+                                                        ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64,
+                                                        ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
+                                                        ctypes.c_void_p, ctypes.c_void_p]),
+    "rass_index_bonus_scatter": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
+                                                ctypes.c_void_p, ctypes.c_int, ctypes.c_int64]),
+    "rass_index_bonus_scatter_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                       ctypes.c_int64, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64]),
+    "rass_index_bonus_from_attr_clauses": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
+                                                          ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int]),
+    "rass_index_bonus_mask": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_void_p,
+                                             ctypes.c_int, ctypes.c_int64]),
     "rass_index_aggregate": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int,
                                             ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                             ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),

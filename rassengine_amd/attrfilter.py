@@ -233,6 +233,41 @@ def compile_filter(where: Any, schema: Optional[AttrSchema], patients: PatientDi
     return Compiler(schema, patients, doc_types, now).compile(where)
 
 
+def compile_should(should: Any, schema: Optional[AttrSchema], patients: PatientDictionary, doc_types: PatientDictionary,
+                   now: Optional[_dt.datetime] = None) -> List[Tuple[int, int, int, int, float]]:
+    """The weighted should-clauses of ``HipIndexer.semantic_search_boosted`` as ``(col, lo, hi, negate, weight)`` rows for
+    ``FlatIndex.bonus_from_attr_clauses``, in list order.  ``should`` is ``[(leaf, weight), ...]``; a leaf is ``term``,
+    ``terms``, ``range`` (date math as in a filter) or ``exists`` over an attribute field, with a filter's encodings.  A
+    ``terms`` leaf becomes one clause per distinct value (a row holds one value, so it earns the weight once); a value that
+    was never indexed contributes no clause.  ``patientId`` / ``doc_type`` leaves (tag fields: no column), ``bool`` and every
+    other node raise ``ValueError``, as does a weight that is not a finite number."""
+    comp = Compiler(schema, patients, doc_types, now)
+    out: List[Tuple[int, int, int, int, float]] = []
+    for item in should or []:
+        if not isinstance(item, (list, tuple)) or len(item) != 2:
+            raise ValueError(f"a should entry is (leaf filter, weight), got {item!r}")
+        leaf, weight = item
+        if isinstance(weight, bool) or not isinstance(weight, (int, float, np.integer, np.floating)) or not np.isfinite(weight):
+            raise ValueError(f"a should weight must be a finite number, got {weight!r}")
+        if not isinstance(leaf, dict) or len(leaf) != 1:
+            raise ValueError(f"a should leaf is a dict with one key (term, terms, range, exists), got {leaf!r}")
+        kind, body = next(iter(leaf.items()))
+        if kind not in ("term", "terms", "range", "exists"):
+            raise ValueError(f"unsupported should clause {kind!r} (supported leaves: term, terms, range, exists)")
+        if kind == "exists":
+            field = body.get("field") if isinstance(body, dict) else None
+        else:
+            fields = [f for f in body if f != "boost"] if isinstance(body, dict) else []
+            field = fields[0] if len(fields) == 1 else None
+        if field in ("patientId", "doc_type"):
+            raise ValueError(f"unsupported should clause: {kind} on the tag field {field!r} (use filter_clause / patient_id / where)")
+        node = comp.compile(leaf)
+        if node[0] not in ("all", "any"):
+            raise ValueError(f"unsupported should clause {leaf!r}")
+        out += [(c, lo, hi, neg, float(weight)) for c, lo, hi, neg in node[1]]
+    return out
+
+
 def plan_calls(plan) -> int:
     """Builder calls a plan costs (for documentation and tests): one per 64 clauses of a leaf, one per tag set."""
     if plan[0] in ("all", "any"):

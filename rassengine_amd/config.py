@@ -78,6 +78,10 @@ RASS_COMPACT_MIN_ROWS = _int("RASS_COMPACT_MIN_ROWS", 65536)
 # next to the vectors and HipIndexer.semantic_search_filtered filters on them.  Empty (the default): no schema, no columns,
 # the files of an index are what they were.
 RASS_ATTR_FIELDS = os.getenv("RASS_ATTR_FIELDS", "").strip()
+# RASS_HYBRID_EXACT: 1 = the hybrid builders answer through the boosted scan (HipIndexer.semantic_search_boosted): the text
+# list, read at today's depth, becomes a bonus column and EVERY row gets boost * knn score + its text score, so a text hit
+# outside the k-NN list keeps its cosine.  Anything else (the default: 0) = the two ranked lists are fused on the host, as before.
+RASS_HYBRID_EXACT = os.getenv("RASS_HYBRID_EXACT", "0").strip() == "1"
 
 
 def get_index_name(user_id: str) -> str:

@@ -13,6 +13,7 @@
 //                    list, the probe and the batch on one fine scan, the delta, the host API (host_groups)
 //   api_ivf_allow.hip  the IVF probe within a row bitmap (probe plan -> slab-order bitmap words -> the allow-list scan), the probed lists
 //   api_allow.hip    the allow-list search (top-k within a per-query row bitmap), its bitmap builders, its plan, a bitmap's popcount
+//   api_boost.hip    the boosted search (top-k of boost * T(cos) + a per-row bonus column) and the builders of its columns
 //   api_keys.hip     the key columns built from the attribute columns (what the grouped search and the aggregation group by)
 //   api_attr.hip     the attribute columns of a flat index and the predicate builder that turns clauses over them into bitmaps
 //   api_mmr.hip      the diversified (MMR) search and the Gram matrices of row lists

@@ -148,6 +148,55 @@ hipError_t launch_scan_topk_f32_pair(const ScanArgs& a, int grid, hipStream_t st
 constexpr int kStepMaxPairs = 16;
 hipError_t launch_scan_topk_f32_step(const ScanArgs& a, int grid, hipStream_t stream);
 
+// ---- boosted scan (scan_boost.hip): exact top-k of fused = boost[q] * T(cos) + bonus[q][row] for one launch group.
+// `scan` carries what a flat EXT launch of launch_scan_topk_f32 would (corpus, row_tag, q_padded [32][row_stride] zero-padded,
+// q_filter / q_filter_mask, q_after_score / q_after_id — the continuation bound, on the FUSED score and the slab row —,
+// part_* [grid][nq][k], row_stride 128 * {1..8}, n_rows >= 1, nq <= 32, k <= 32, id_base 0: the lists hold slab rows); every
+// other field of it stays at its default.  bonus: query q's column at bonus + q * bonus_q_stride (0: one column shared by
+// every query), bonus_rows values each (<= bonus_q_stride where that is set); a row at or past bonus_rows reads 0.
+// bonus_bytes = 4 * ((nq - 1) * bonus_q_stride + bonus_rows) <= kBoostMaxBonusBytes: the records of the kernel's one buffer
+// descriptor.  boost [nq] or nullptr (1.0).  transform 0: T(s) = s; 1: T(s) = 1 / (2 - s).  A row ranks when it is live,
+// passes the filter and the bound, s > -inf and fused > -inf; order (fused desc, row asc).  No sample floor.
+// ScanArgs itself is untouched: the other scan kernels' argument block keeps its size and offsets.
+constexpr int64_t kBoostMaxBonusBytes = 0x7fffffff;
+struct BoostArgs {
+    ScanArgs scan;
+    const float* bonus = nullptr;
+    int64_t bonus_q_stride = 0;
+    int64_t bonus_rows = 0;
+    unsigned bonus_bytes = 0;
+    int transform = 0;
+    const float* boost = nullptr;
+};
+hipError_t launch_scan_boost_f32(const BoostArgs& a, int grid, hipStream_t stream);
+
+// ---- bonus columns (bonus.hip): the dense fp32 columns the boosted scan adds.  A column block is [n_bonus][stride] floats.
+// Plain vector loads and stores, no atomics.
+// bonus[q_of[i] * stride + rows[i]] = that value + values[i] (one rounded add) for i < n.  The (q, row) pairs must be UNIQUE
+// within a call and in range (the host entry checks; a device caller's duty): each cell has one writer.
+hipError_t launch_bonus_scatter(const int32_t* q_of, const int64_t* rows, const float* values, int64_t n, float* bonus, int64_t stride,
+                                hipStream_t stream);
+// Weighted clauses over the attribute columns for one launch group of nq <= 32 bonus columns.  A clause {col, lo, hi, negate}
+// holds for a row as attr.hip's does: v = col[c][row] is not INT32_MIN and lo <= v <= hi, inverted under negate; a NULL column
+// reads as INT32_MIN everywhere.  clauses[q_off[q] .. q_off[q + 1]) are query q's, in the CALLER'S list order (the host sorts
+// by query, stably); weights[j] belongs to clauses[j].  Per (query, row < n_rows): b = 0 (add = 0) or the cell's value (add =
+// 1), then b = b + weight (one rounded add each) for every clause of the query that holds, in that order.  Tombstoned rows
+// are written like any other.  Cells [n_rows, stride) are left alone.
+struct BonusClauseArgs {
+    const int32_t* col[8] = {};      // kAttrCols
+    const int4* clauses = nullptr;
+    const float* weights = nullptr;
+    const int32_t* q_off = nullptr;  // DEVICE int32 [nq + 1], q_off[0] = 0
+    int64_t n_rows = 0;
+    float* bonus = nullptr;
+    int64_t stride = 0;
+    int nq = 0, add = 0;
+};
+hipError_t launch_bonus_clauses(const BonusClauseArgs& a, hipStream_t stream);
+// bonus[q][r] = -inf where bit r of bitmap q (allow + q * allow_q_stride; 0: one shared bitmap) is clear, r < n_rows, q < n_bonus.
+hipError_t launch_bonus_mask(float* bonus, int n_bonus, int64_t stride, int64_t n_rows, const uint32_t* allow, int64_t allow_q_stride,
+                             hipStream_t stream);
+
 // [n_lists][nq][k] sorted candidate lists -> [nq][k]; n_lists * k <= kMergeMaxCandidates.
 constexpr int kMergeMaxCandidates = 8192;
 // `groups` (optional): ONE launch merges the lists of several launch groups of <= size queries each; nq is then

@@ -1077,6 +1077,177 @@ class FlatIndex:
                                                          ctypes.c_void_p(d_q_filter_mask_ptr or 0), int(id_base),
                                                          ctypes.c_void_p(d_out_scores_ptr), ctypes.c_void_p(d_out_ids_ptr)))
 
+    # ---- boosted search: exact top-k of boost * T(cos) + a per-row bonus column
+    BONUS_SLACK_ROWS = 2048      # cells a new column gets beyond the rows: rows appended meanwhile still fit (and read 0)
+    BOOST_TRANSFORMS = {"raw": N.RASS_BOOST_RAW, "opensearch": N.RASS_BOOST_OPENSEARCH}
+    BONUS_OPS = {"replace": N.RASS_BONUS_REPLACE, "add": N.RASS_BONUS_ADD}
+
+    def new_bonus(self, nq: Optional[int] = None):
+        """A zero bonus column block for ``search_boosted``: float32 CUDA [stride] (``nq=None``: one column shared by every
+        query) or [nq, stride]; stride = rows + slack, rounded up to 32.  Fill it with ``bonus_scatter``,
+        ``bonus_from_attr_clauses`` and ``bonus_mask``.  It names rows of one ``layout_epoch``; rows appended later read 0."""
+        import torch
+        stride = (self.rows + self.BONUS_SLACK_ROWS + 31) // 32 * 32
+        if nq is not None and not 1 <= int(nq) <= N.RASS_MAX_DEVICE_BATCH:
+            raise ValueError(f"nq must be in [1, {N.RASS_MAX_DEVICE_BATCH}], got {nq}")
+        return torch.zeros((stride,) if nq is None else (int(nq), stride), dtype=torch.float32, device=f"cuda:{self.engine.device}")
+
+    @staticmethod
+    def _bonus_shape(bonus) -> Tuple[int, int]:
+        """(n_bonus, stride) of a device column block, checked."""
+        import torch
+        if not hasattr(bonus, "data_ptr") or not bonus.is_cuda or bonus.dtype != torch.float32 or not bonus.is_contiguous():
+            raise ValueError("a bonus column block must be a contiguous float32 CUDA tensor")
+        if bonus.dim() not in (1, 2) or int(bonus.shape[-1]) % 32 != 0:
+            raise ValueError(f"bonus must be [stride] or [n, stride] with stride a multiple of 32, got {tuple(bonus.shape)}")
+        return (1, int(bonus.shape[0])) if bonus.dim() == 1 else (int(bonus.shape[0]), int(bonus.shape[1]))
+
+    def bonus_scatter(self, bonus, q_of, rows, values):
+        """``bonus[q_of[i], rows[i]] += values[i]`` (``rass_index_bonus_scatter``): one rounded fp32 add per entry.  The
+        (column, row) pairs must be unique within a call (sum duplicates first) and in range, or the call is refused.  For a
+        shared column ``q_of`` is all zeros (or None).  Returns ``bonus``."""
+        import torch
+        n_bonus, stride = self._bonus_shape(bonus)
+        r = np.ascontiguousarray(np.asarray(rows).reshape(-1), dtype=np.int64)
+        v = np.ascontiguousarray(np.asarray(values).reshape(-1), dtype=np.float32)
+        q = np.zeros(r.shape[0], dtype=np.int32) if q_of is None else np.ascontiguousarray(np.asarray(q_of).reshape(-1), dtype=np.int32)
+        if not (q.shape == r.shape == v.shape):
+            raise ValueError("q_of, rows and values must have one length")
+        torch.cuda.current_stream(bonus.device).synchronize()     # the engine works on its own stream
+        N.check("rass_index_bonus_scatter", self._L.rass_index_bonus_scatter(
+            self._h, _np_ptr(q), _np_ptr(r), _np_ptr(v), r.shape[0], ctypes.c_void_p(bonus.data_ptr()), n_bonus, stride))
+        return bonus
+
+    def bonus_from_attr_clauses(self, bonus, clauses, weights, op: str = "replace"):
+        """Weighted predicates over the attribute columns into ``bonus`` (``rass_index_bonus_from_attr_clauses``).
+        ``clauses``: int32 [n, 5] rows ``(query, col, lo, hi, negate)`` as ``allow_from_attr_clauses`` takes them (a shared
+        column's clauses name query 0); ``weights``: float32 [n].  Per (query, row): start from 0 (``op`` "replace") or the
+        cell's value ("add"), then add the weight of every clause of the query that holds, in list order, one rounded fp32
+        add each.  At most 64 clauses per query per call.  Returns ``bonus``."""
+        import torch
+        n_bonus, stride = self._bonus_shape(bonus)
+        c = np.ascontiguousarray(np.asarray(clauses, dtype=np.int64).reshape(-1, 5))
+        if c.size and (int(c.min()) < -(1 << 31) or int(c.max()) > (1 << 31) - 1):
+            raise OverflowError("clause fields must fit int32")
+        c = np.ascontiguousarray(c, dtype=np.int32)
+        w = np.ascontiguousarray(np.asarray(weights).reshape(-1), dtype=np.float32)
+        if w.shape[0] != c.shape[0]:
+            raise ValueError(f"{c.shape[0]} clauses but {w.shape[0]} weights")
+        if op not in self.BONUS_OPS:
+            raise ValueError(f"op must be replace / add, not {op!r}")
+        torch.cuda.current_stream(bonus.device).synchronize()     # the engine works on its own stream
+        N.check("rass_index_bonus_from_attr_clauses", self._L.rass_index_bonus_from_attr_clauses(
+            self._h, _np_ptr(c), _np_ptr(w), c.shape[0], n_bonus, n_bonus, ctypes.c_void_p(bonus.data_ptr()), stride,
+            self.BONUS_OPS[op]))
+        return bonus
+
+    def bonus_mask(self, bonus, allow):
+        """``bonus`` = -inf wherever the device bitmap ``allow`` ([words] shared, or one per column) has no bit
+        (``rass_index_bonus_mask``): the rows a ``where`` filter excludes never rank in ``search_boosted``.  Returns ``bonus``."""
+        import torch
+        n_bonus, stride = self._bonus_shape(bonus)
+        if not hasattr(allow, "data_ptr") or not allow.is_cuda or allow.dtype != torch.int32 or not allow.is_contiguous():
+            raise ValueError("a device bitmap must be a contiguous int32 CUDA tensor")
+        n_bitmaps, words = (1, int(allow.shape[0])) if allow.dim() == 1 else (int(allow.shape[0]), int(allow.shape[1]))
+        if n_bitmaps not in (1, n_bonus):
+            raise ValueError(f"{n_bitmaps} bitmaps for {n_bonus} bonus column(s)")
+        torch.cuda.current_stream(bonus.device).synchronize()     # the engine works on its own stream
+        N.check("rass_index_bonus_mask", self._L.rass_index_bonus_mask(
+            self._h, ctypes.c_void_p(bonus.data_ptr()), n_bonus, stride, ctypes.c_void_p(allow.data_ptr()), n_bitmaps, words))
+        return bonus
+
+    def _check_boosted(self, nq: int, k: int, boost, transform, n_bonus: int, stride: int, bonus_rows) -> Tuple[Optional[np.ndarray], int, int]:
+        """The argument checks of ``search_boosted``, made before any native call: (boost f32 [nq] or None, transform code,
+        bonus_rows)."""
+        if not 1 <= k <= N.RASS_MAX_K_MULTIPASS:
+            raise ValueError(f"k must be in [1, {N.RASS_MAX_K_MULTIPASS}], got {k}")
+        if nq > N.RASS_MAX_DEVICE_BATCH:
+            raise ValueError(f"at most {N.RASS_MAX_DEVICE_BATCH} queries per call, got {nq}")
+        if transform not in self.BOOST_TRANSFORMS:
+            raise ValueError(f"transform must be raw / opensearch, not {transform!r}")
+        if nq > 0 and n_bonus not in (1, nq):
+            raise ValueError(f"bonus must be [stride] (shared) or [nq, stride], got {n_bonus} columns for {nq} queries")
+        b = None
+        if boost is not None:
+            b = np.asarray(boost, dtype=np.float32)
+            b = np.ascontiguousarray(np.full(nq, b, dtype=np.float32) if b.ndim == 0 else b)
+            if b.shape != (nq,):
+                raise ValueError("boost must be one number, or one per query")
+            if not np.isfinite(b).all():
+                raise ValueError("boost must be finite")
+        rows = stride if bonus_rows is None else int(bonus_rows)
+        if not 0 <= rows <= stride:
+            raise ValueError(f"bonus_rows must be in [0, {stride}], got {rows}")
+        if self.dtype != "f32" or self.row_stride > 1024:
+            raise ValueError("boosted search needs an fp32 index with dim <= 1024")
+        return b, self.BOOST_TRANSFORMS[transform], rows
+
+    def search_boosted(self, queries: np.ndarray, k: int, bonus, boost=None, transform: str = "raw", bonus_rows: Optional[int] = None,
+                       q_filter: Optional[np.ndarray] = None, q_filter_mask: Optional[np.ndarray] = None,
+                       on_device: bool = False) -> Tuple[np.ndarray, np.ndarray]:
+        """Exact top-k of ``boost[q] * T(cos) + bonus[q][row]`` (``rass_index_search_boosted``).  ``bonus``: a device column
+        block from ``new_bonus`` ([stride] shared, [nq, stride] one per query), or a numpy array of that shape, uploaded.
+        ``boost``: one finite number or one per query (None: 1.0); ``transform`` "raw" (T(s) = s) or "opensearch" (T(s) =
+        1 / (2 - s)).  Rows at or past ``bonus_rows`` (default: the whole column) read 0.  A row ranks when it is live, passes
+        ``q_filter`` / ``q_filter_mask`` as in ``search``, has a cosine above -inf and a fused score above -inf: a bonus of
+        -inf or NaN excludes the row.  Returns (fused scores f32 [nq, k], ids i64 [nq, k]): best first, ties by id ascending,
+        (-inf, -1) padding; k <= 4096, nq <= 4096.  One corpus pass per 32 queries.  fp32 indices with dim <= 1024.
+        ``on_device``: go through the device-resident entry point.  Thread-safe."""
+        q = self._queries(queries)
+        nq, k = q.shape[0], int(k)
+        f, m = self._filters(q_filter, q_filter_mask, nq)
+        host = None
+        if isinstance(bonus, np.ndarray):
+            host = np.ascontiguousarray(bonus, dtype=np.float32)
+            if host.ndim not in (1, 2) or host.shape[-1] % 32 != 0:
+                raise ValueError(f"bonus must be [stride] or [n, stride] with stride a multiple of 32, got {host.shape}")
+            n_bonus, stride = (1, host.shape[0]) if host.ndim == 1 else host.shape
+        else:
+            n_bonus, stride = self._bonus_shape(bonus)
+        b, t_code, rows = self._check_boosted(nq, k, boost, transform, n_bonus, stride, bonus_rows)
+        out_s = np.empty((nq, k), dtype=np.float32)
+        out_i = np.empty((nq, k), dtype=np.int64)
+        if nq == 0:
+            return out_s, out_i
+        import torch
+        dev = f"cuda:{self.engine.device}"
+        if host is not None:
+            bonus = torch.from_numpy(host).to(dev)
+        torch.cuda.current_stream(bonus.device).synchronize()     # the engine works on its own stream
+        if on_device:
+            dq = torch.from_numpy(q).to(dev)
+            db = torch.from_numpy(b).to(dev) if b is not None else None
+            df = torch.from_numpy(f).to(dev) if f is not None else None
+            dm = torch.from_numpy(m).to(dev) if m is not None else None
+            ds = torch.empty((nq, k), dtype=torch.float32, device=dev)
+            di = torch.empty((nq, k), dtype=torch.int64, device=dev)
+            torch.cuda.current_stream(bonus.device).synchronize()
+            self.search_boosted_device(dq.data_ptr(), nq, k, bonus.data_ptr(), n_bonus, rows, stride, ds.data_ptr(), di.data_ptr(),
+                                       d_boost_ptr=db.data_ptr() if db is not None else 0, transform=transform,
+                                       d_q_filter_ptr=df.data_ptr() if df is not None else 0,
+                                       d_q_filter_mask_ptr=dm.data_ptr() if dm is not None else 0)
+            self.engine.synchronize()
+            return ds.cpu().numpy(), di.cpu().numpy()
+        N.check("rass_index_search_boosted", self._L.rass_index_search_boosted(
+            self._h, _np_ptr(q), nq, k, _np_ptr(b), t_code, ctypes.c_void_p(bonus.data_ptr()), n_bonus, rows, stride, _np_ptr(f),
+            _np_ptr(m), _np_ptr(out_s), _np_ptr(out_i)))
+        return out_s, out_i
+
+    def search_boosted_device(self, d_queries_ptr: int, nq: int, k: int, d_bonus_ptr: int, n_bonus: int, bonus_rows: int,
+                              bonus_stride: int, d_out_scores_ptr: int, d_out_ids_ptr: int, d_boost_ptr: int = 0,
+                              transform: str = "raw", id_base: int = 0, d_q_filter_ptr: int = 0, d_q_filter_mask_ptr: int = 0) -> None:
+        """Async, device-resident ``search_boosted`` (``rass_index_search_boosted_device``): nq <= 4096 in launch groups of
+        32, k <= 4096 (every pass enqueued by the one call).  The boosts are device memory: keeping them finite is the caller's."""
+        if transform not in self.BOOST_TRANSFORMS:
+            raise ValueError(f"transform must be raw / opensearch, not {transform!r}")
+        N.check("rass_index_search_boosted_device",
+                self._L.rass_index_search_boosted_device(self._h, ctypes.c_void_p(d_queries_ptr), int(nq), int(k),
+                                                         ctypes.c_void_p(d_boost_ptr or 0), self.BOOST_TRANSFORMS[transform],
+                                                         ctypes.c_void_p(d_bonus_ptr), int(n_bonus), int(bonus_rows), int(bonus_stride),
+                                                         ctypes.c_void_p(d_q_filter_ptr or 0),
+                                                         ctypes.c_void_p(d_q_filter_mask_ptr or 0), int(id_base),
+                                                         ctypes.c_void_p(d_out_scores_ptr), ctypes.c_void_p(d_out_ids_ptr)))
+
     MAX_MMR_FETCH = N.RASS_MAX_MMR_FETCH   # search_mmr: candidates per query; rows_gram: rows per list
 
     def rows_gram(self, rows) -> np.ndarray:

@@ -591,6 +591,91 @@ class HipIndexer:
                 return hits
         raise RuntimeError(f"{self.index_name}: the index was compacted during every one of {LAYOUT_ATTEMPTS} searches")
 
+    def semantic_search_boosted(self, query_emb: np.ndarray, k: int = TOP_K, boost: float = 1.0,
+                                text_hits: Optional[List[Tuple[Any, float]]] = None, should: Optional[List[Tuple[Dict, float]]] = None,
+                                where: Optional[Any] = None, filter_clause: Optional[Dict] = None, patient_id: Optional[str] = None,
+                                doc_type: Optional[str] = None, score_mode: Optional[str] = None) -> List[Tuple[Dict, float]]:
+        """A ``bool.should`` around the k-NN clause, answered exactly: the top ``k`` chunks by ``boost * knn_score + the sum of
+        what the other clauses are worth for the chunk`` over EVERY chunk of the index (``FlatIndex.search_boosted``), not
+        over two ranked lists cut at some depth.  ``text_hits``: ``[(doc | doc_id, score)]`` from a text engine, resolved
+        through ``doc_id -> row``; unknown or deleted ids are ignored, repeated ids are summed (fp32, list order).
+        ``should``: ``[(leaf filter, weight)]`` with ``term`` / ``terms`` / ``range`` (date math as in a filter) / ``exists``
+        leaves over the attribute fields (``attrfilter.compile_should``); weights of any sign.  ``where``: a filter as
+        ``semantic_search_filtered`` takes it; the chunks it excludes never rank.  ``filter_clause`` / ``patient_id`` /
+        ``doc_type`` as in ``semantic_search``.  ``knn_score`` is in ``score_mode``'s units (default ``RASS_SCORE_MODE``).
+        Returns ``[(doc_dict, float(fused))]`` best first; ``[]`` on an empty embedding or on any exception (logged)."""
+        if _empty(query_emb):
+            return []
+        try:
+            return self._boosted(query_emb, k, boost, text_hits, should, where, filter_clause, patient_id, doc_type, score_mode)
+        except Exception as e:
+            logger.error(f"Boosted search error: {e}")
+            return []
+
+    def _boosted(self, query_emb, k, boost, text_hits, should, where, filter_clause, patient_id, doc_type, score_mode
+                 ) -> List[Tuple[Dict, float]]:
+        st: Optional[IndexState] = REGISTRY.get(self.index_name, create=False)
+        if st is None:
+            return []
+        prep = self._prepare(st, query_emb, k, filter_clause, patient_id, doc_type)
+        if prep is None:
+            return []
+        q, k_eff, (fval, fmask) = prep
+        flt = dict(q_filter=np.array([fval], dtype=np.int32), q_filter_mask=np.array([fmask], dtype=np.int32)) if fmask else {}
+        if not hasattr(st.index, "search_boosted"):
+            raise NotImplementedError(f"{self.index_name}: {type(st.index).__name__} has no boosted search "
+                                      "(sharded indices cannot rank by a bonus column; use a flat fp32 index)")
+        boost = float(boost)
+        if not np.isfinite(boost):
+            raise ValueError(f"boost must be finite, got {boost!r}")
+        transform = "raw" if (score_mode or config.RASS_SCORE_MODE) == "cosine" else "opensearch"
+        from .attrfilter import MAX_CLAUSES, compile_filter, compile_should, run_plan
+        for _ in range(LAYOUT_ATTEMPTS):    # the column and the ids belong to ONE layout of the index, as in semantic_search_within
+            layout = _layout_epoch(st.index)
+            # under the state's lock from the first cell to the search: no row is appended in between (add_documents takes
+            # the lock), so no chunk slips past `where` with the zero bonus of a row the column has not seen
+            with st.lock:
+                if _layout_epoch(st.index) != layout:
+                    continue
+                rows, values = self._text_rows(st, text_hits)
+                clauses = compile_should(should, st.attrs, st.patients, st.doc_types)
+                bonus = st.index.new_bonus()
+                if rows:
+                    st.index.bonus_scatter(bonus, None, rows, values)
+                for i in range(0, len(clauses), MAX_CLAUSES):
+                    chunk = clauses[i:i + MAX_CLAUSES]
+                    st.index.bonus_from_attr_clauses(bonus, [(0, c, lo, hi, neg) for c, lo, hi, neg, _ in chunk],
+                                                     [w for *_, w in chunk], op="add")
+                if where is not None:
+                    st.index.bonus_mask(bonus, run_plan(st.index, compile_filter(where, st.attrs, st.patients, st.doc_types)))
+                scores, ids = st.index.search_boosted(q, k_eff, bonus, boost=boost, transform=transform, **flt)
+                out: List[Tuple[Dict, float]] = []
+                for s, row in zip(scores[0], ids[0]):
+                    if row < 0:
+                        break
+                    doc = st.row_doc[int(row)] if int(row) < len(st.row_doc) else None
+                    if doc is None:
+                        continue
+                    hit = dict(doc)
+                    if config.RASS_RETURN_EMBEDDING:
+                        hit["embedding"] = st.index.get_row(int(row)).tolist()  # reference quirk 5
+                    out.append((hit, float(s)))
+                return out
+        raise RuntimeError(f"{self.index_name}: the index was compacted during every one of {LAYOUT_ATTEMPTS} searches")
+
+    @staticmethod
+    def _text_rows(st: IndexState, text_hits) -> Tuple[List[int], List[float]]:
+        """``[(doc | doc_id, score)]`` -> (rows, fp32 values) with one entry per row: ids the index does not hold (never
+        indexed, deleted) are dropped, repeated ids summed in list order.  The caller holds ``st.lock``."""
+        acc: Dict[int, np.float32] = {}
+        for doc, s in text_hits or []:
+            key = doc.get("doc_id") if isinstance(doc, dict) else doc
+            row = st.doc_row.get(key) if key is not None else None
+            if row is None or row >= len(st.row_doc) or st.row_doc[row] is None:
+                continue
+            acc[row] = np.float32(acc[row] + np.float32(s)) if row in acc else np.float32(s)
+        return list(acc.keys()), [float(v) for v in acc.values()]
+
     def knn_scores(self, query_emb: np.ndarray, k: int = TOP_K, boost: float = 1.0,
                    filter_clause: Optional[Dict] = None, patient_id: Optional[str] = None,
                    doc_type: Optional[str] = None) -> List[Tuple[Dict, float]]:
@@ -752,6 +837,14 @@ class HipIndexer:
             k = max(1, int(k))
             text = self._text_engine()
             depth = k * FUSION_OVERFETCH if text is not None else k
+            if config.RASS_HYBRID_EXACT and text is not None:
+                # the text list at today's depth becomes a bonus column: every row gets boost * knn score + its text score
+                try:
+                    bm25 = getattr(text, method)(query, query_emb, k=depth, filter_clause=filter_clause, patient_id=patient_id)
+                except Exception as e:
+                    logger.error(f"{err_label} (text clauses): {e}")
+                    bm25 = []
+                return self._boosted(query_emb, k, boost, bm25, None, None, filter_clause, patient_id, doc_type, None)
             knn = self._knn(query_emb, depth, filter_clause, patient_id, boost=boost, doc_type=doc_type)
             if text is None:
                 return knn[:k]
