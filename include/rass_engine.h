@@ -530,6 +530,114 @@ int rass_index_bonus_from_attr_clauses(rass_index_t* idx, const int32_t* clauses
 int rass_index_bonus_mask(rass_index_t* idx, float* d_bonus, int n_bonus, int64_t stride, const uint32_t* d_allow,
                           int n_bitmaps, int64_t words);
 
+/* FUNCTION-SCORE search: the exact top-k of
+ *     t = T(cos),  a = boost[q] * t,  fused = combine(a, f[q][row])
+ * over a flat index — an OpenSearch function_score around a knn clause.  f is a dense fp32 FUNCTION COLUMN in device memory,
+ * d_fn = float[n_fn][fn_stride] with the layout and ownership of a bonus block: n_fn = nq (column q belongs to query q) or 1
+ * (ONE column shared by every query).  The column must cover EVERY row of the index at the call: fn_rows must equal the
+ * index's rows (live and tombstoned), else RASS_ERR_INVALID — "rows past the column read 0" has no meaning that holds in
+ * every mode.  boost, transform: as in rass_index_search_boosted.  combine is OpenSearch's boost_mode:
+ *     RASS_COMBINE_SUM a + f | _MULTIPLY a * f | _AVG (a + f) * 0.5f | _MAX f > a ? f : a | _MIN f < a ? f : a | _REPLACE f
+ * ARITHMETIC, all fp32: the cosine is the flat scan's, bit for bit; T, the product boost * t and every operation of the
+ * combine (avg: a rounded add, then a rounded product) are each ONE correctly rounded operation, never contracted into an
+ * fma; max and min are a compare and a select (which of two zeros of different sign is reported is thereby fixed).
+ * min_score: HOST float[nq], or NULL: the knn clause's radial min_score.  A row ranks for query q only with t >=
+ * min_score[q] — the gate is on the TRANSFORMED similarity, before the boost; -inf: no gate; a NaN: RASS_ERR_INVALID.
+ * A row RANKS for query q when it is live, passes the filter as in rass_index_search_ex, passes the gate, has cos > -inf, has
+ * f > -inf and has fused > -inf.  A NaN or -inf cell of the column EXCLUDES the row in EVERY mode, _MAX and _REPLACE
+ * included: rass_index_bonus_mask works on a function column as on a bonus column.  out_scores / out_ids are [nq][k]: fused
+ * descending, ties by row ordinal ascending, (-inf, -1) past the end; ids as rass_index_search_ex reports them.
+ * One corpus pass per launch group of RASS_MAX_QBATCH queries; every tile is streamed; no sample floor.  1 <= k <=
+ * RASS_MAX_K_MULTIPASS (k > RASS_MAX_K in passes of RASS_MAX_K chained on the device under the continuation bound, taken on
+ * the fused score); 0 <= nq <= RASS_MAX_DEVICE_BATCH.  Outside those, n_fn neither 1 nor nq, fn_rows outside [0, fn_stride]
+ * or not the index's rows, a non-finite boost, a NaN min_score, an unknown transform or combine, or a launch group whose
+ * columns span 2 GiB or more: RASS_ERR_INVALID, nothing is launched and the outputs are untouched.  Where the boosted search
+ * answers RASS_ERR_UNSUPPORTED (a bf16 index, a wide-row index) so does this one; IVF probes, cross-index batches and the
+ * sharded front have no function-score form.  A column names row ordinals of ONE layout.  Thread-safety as
+ * rass_index_search_ex. */
+#define RASS_COMBINE_SUM 0
+#define RASS_COMBINE_MULTIPLY 1
+#define RASS_COMBINE_AVG 2
+#define RASS_COMBINE_MAX 3
+#define RASS_COMBINE_MIN 4
+#define RASS_COMBINE_REPLACE 5
+int rass_index_search_scored(rass_index_t* idx, const float* queries, int nq, int k,
+                             const float* boost, int transform, int combine, const float* min_score,
+                             const float* d_fn, int n_fn, int64_t fn_rows, int64_t fn_stride,
+                             const int32_t* q_filter, const int32_t* q_filter_mask,
+                             float* out_scores, int64_t* out_ids);
+/* Device-resident variant: every pointer is device memory (d_boost and d_min_score too; keeping the boosts finite is the
+ * caller's; a NaN gate passes no row), the call is stream-ordered, nothing is synchronised and nothing is read back; every
+ * pass of a k > RASS_MAX_K search is enqueued by the one call.  Ids are id_base + row (ignored on an index with
+ * caller-assigned ids, which are reported). */
+int rass_index_search_scored_device(rass_index_t* idx, const float* d_queries, int nq, int k,
+                                    const float* d_boost, int transform, int combine, const float* d_min_score,
+                                    const float* d_fn, int n_fn, int64_t fn_rows, int64_t fn_stride,
+                                    const int32_t* d_q_filter, const int32_t* d_q_filter_mask,
+                                    int64_t id_base, float* d_out_scores, int64_t* d_out_ids);
+/* FUNCTION COLUMN BUILDER: OpenSearch's function_score.functions over the int32 attribute columns into a caller-owned DEVICE
+ * block d_fn = float[n_fn][stride] (stride a multiple of 32 and >= the index's rows, 1 <= n_fn <= RASS_MAX_DEVICE_BATCH; n_fn
+ * = 1: a shared column whose records all name query 0).  `fns` is a HOST array of n_fns records; the records of one query
+ * act in LIST order; at most RASS_MAX_SCORE_FNS (16) records per query per call.  With v the row's value in column `col`:
+ *   RASS_FN_GAUSS / _EXP / _LINEAR (decay): d = max(0, |v - origin| - offset); gauss exp(d * d * (ln(decay) / (scale * scale))),
+ *     exp exp(d * (ln(decay) / scale)), linear max(0, (s - d) / s) with s = scale / (1 - decay).  origin finite, scale > 0,
+ *     offset >= 0, 0 < decay < 1.  A row whose value is RASS_ATTR_MISSING gets 1.0 (OpenSearch's rule for decay on a missing field).
+ *   RASS_FN_FIELD_VALUE: modifier(factor * v); RASS_FN_MOD_NONE x, _LOG log10(x), _LOG1P log10(1 + x), _LOG2P log10(2 + x),
+ *     _LN ln(x), _LN1P ln(1 + x), _LN2P ln(2 + x), _SQUARE x * x, _SQRT sqrt(x), _RECIPROCAL 1 / x.  On a row without the value,
+ *     `missing` stands in for v; with `missing` NaN the function does not apply to that row.  A non-positive argument of a
+ *     logarithm (a negative one of sqrt) yields -inf / NaN, and the search then EXCLUDES the row — OpenSearch raises instead.
+ *   RASS_FN_WEIGHT: the constant 1.0 (a filter function worth only its weight).
+ * `filter`: -1, or an index into d_filters = uint32[n_filters][words] (the allow-list bitmap layout, words >= ceil(rows /
+ * 32)): the function applies to the rows whose bit is set.  A function applies to a row when its filter allows it and it is
+ * not a field_value miss; its value is weight * kind(v) (weight finite).  The applying functions of a query are folded in list order by
+ * score_mode — RASS_FN_SCORE_MULTIPLY, _SUM, _AVG (sum(value_i) / sum(weight_i)), _FIRST, _MAX, _MIN (compare and select), the
+ * first applying value starting the fold — and the result is capped: value > max_boost ? max_boost : value (+inf: no cap; NaN
+ * refused).  A row to which no function applies gets 1.0.
+ * ARITHMETIC: all of it in double on the device, each operation rounded on its own, and rounded to fp32 ONCE, at the store; the
+ * per-function constants are derived in double on the host.  A cell built from + - * / sqrt and comparisons alone is what an
+ * IEEE fp64 restatement gives; a cell through exp or a logarithm is within one fp32 ulp of it.
+ * Rows [0, rows) of every column are written, tombstoned rows too; the padding is left alone.  Parameters outside the ranges
+ * above, an unknown kind / modifier / score_mode, a record naming a query outside [0, n_fn), a column outside [0,
+ * RASS_MAX_ATTRS) or a filter outside [-1, n_filters), too many records for a query, a stride below the rows or words too
+ * short: RASS_ERR_INVALID and nothing is written.  Stream-ordered on the engine's stream; the host array may be reused when
+ * the call returns. */
+#define RASS_MAX_SCORE_FNS 16
+#define RASS_FN_GAUSS 0
+#define RASS_FN_EXP 1
+#define RASS_FN_LINEAR 2
+#define RASS_FN_FIELD_VALUE 3
+#define RASS_FN_WEIGHT 4
+#define RASS_FN_MOD_NONE 0
+#define RASS_FN_MOD_LOG 1
+#define RASS_FN_MOD_LOG1P 2
+#define RASS_FN_MOD_LOG2P 3
+#define RASS_FN_MOD_LN 4
+#define RASS_FN_MOD_LN1P 5
+#define RASS_FN_MOD_LN2P 6
+#define RASS_FN_MOD_SQUARE 7
+#define RASS_FN_MOD_SQRT 8
+#define RASS_FN_MOD_RECIPROCAL 9
+#define RASS_FN_SCORE_MULTIPLY 0
+#define RASS_FN_SCORE_SUM 1
+#define RASS_FN_SCORE_AVG 2
+#define RASS_FN_SCORE_FIRST 3
+#define RASS_FN_SCORE_MAX 4
+#define RASS_FN_SCORE_MIN 5
+typedef struct rass_score_fn {
+    int32_t query;      /* the column (query) the function belongs to, [0, n_fn) */
+    int32_t kind;       /* RASS_FN_* */
+    int32_t col;        /* attribute column (ignored by RASS_FN_WEIGHT) */
+    int32_t filter;     /* -1, or the bitmap of d_filters that gates the function */
+    int32_t modifier;   /* RASS_FN_MOD_* (RASS_FN_FIELD_VALUE only) */
+    int32_t reserved;   /* 0 */
+    double weight;
+    double origin, scale, offset, decay;    /* decay kinds */
+    double factor, missing;                 /* RASS_FN_FIELD_VALUE */
+} rass_score_fn_t;
+int rass_index_fn_from_attr(rass_index_t* idx, const rass_score_fn_t* fns, int64_t n_fns, int n_fn, int score_mode,
+                            double max_boost, const uint32_t* d_filters, int n_filters, int64_t words,
+                            float* d_fn, int64_t stride);
+
 /* Semantic TERMS AGGREGATION: per-group hit counts above a min_score — OpenSearch's `"aggs": {"x": {"terms": {"field": ...}}}`
  * under a k-NN clause with a min_score, with a `cardinality` and the hit total thrown in.  The group of a row is a bit field
  * of its tag, as in rass_index_search_grouped.  A row is a HIT of query q when it is live, passes q_filter (NULL, exact, or

@@ -39,6 +39,24 @@ RASS_ATTR_REPLACE, RASS_ATTR_AND, RASS_ATTR_OR, RASS_ATTR_ANDNOT = 0, 1, 2, 3
 RASS_KEY_NONE = -1
 RASS_BOOST_RAW, RASS_BOOST_OPENSEARCH = 0, 1
 RASS_BONUS_REPLACE, RASS_BONUS_ADD = 0, 1
+(RASS_COMBINE_SUM, RASS_COMBINE_MULTIPLY, RASS_COMBINE_AVG, RASS_COMBINE_MAX, RASS_COMBINE_MIN,
+ RASS_COMBINE_REPLACE) = range(6)
+RASS_MAX_SCORE_FNS = 16
+RASS_FN_GAUSS, RASS_FN_EXP, RASS_FN_LINEAR, RASS_FN_FIELD_VALUE, RASS_FN_WEIGHT = range(5)
+(RASS_FN_MOD_NONE, RASS_FN_MOD_LOG, RASS_FN_MOD_LOG1P, RASS_FN_MOD_LOG2P, RASS_FN_MOD_LN, RASS_FN_MOD_LN1P, RASS_FN_MOD_LN2P,
+ RASS_FN_MOD_SQUARE, RASS_FN_MOD_SQRT, RASS_FN_MOD_RECIPROCAL) = range(10)
+(RASS_FN_SCORE_MULTIPLY, RASS_FN_SCORE_SUM, RASS_FN_SCORE_AVG, RASS_FN_SCORE_FIRST, RASS_FN_SCORE_MAX,
+ RASS_FN_SCORE_MIN) = range(6)
+
+
+class ScoreFn(ctypes.Structure):
+    """``rass_score_fn_t``: one function record of ``rass_index_fn_from_attr``."""
+    _fields_ = [("query", ctypes.c_int32), ("kind", ctypes.c_int32), ("col", ctypes.c_int32), ("filter", ctypes.c_int32),
+                ("modifier", ctypes.c_int32), ("reserved", ctypes.c_int32), ("weight", ctypes.c_double),
+                ("origin", ctypes.c_double), ("scale", ctypes.c_double), ("offset", ctypes.c_double), ("decay", ctypes.c_double),
+                ("factor", ctypes.c_double), ("missing", ctypes.c_double)]
+
+
 RASS_MAX_KEY_EDGES = 4097
 
 c_float_p = ctypes.POINTER(ctypes.c_float)
@@ -144,6 +162,17 @@ SIGNATURES = {
                                                           ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int]),
     "rass_index_bonus_mask": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_void_p,
                                              ctypes.c_int, ctypes.c_int64]),
+    "rass_index_search_scored": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
+                                                ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
+                                                ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                ctypes.c_void_p]),
+    "rass_index_search_scored_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
+                                                       ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+                                                       ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p,
+                                                       ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p]),
+    "rass_index_fn_from_attr": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int,
+                                               ctypes.c_double, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_void_p,
+                                               ctypes.c_int64]),
     "rass_index_aggregate": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int,
                                             ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                             ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),

@@ -268,6 +268,116 @@ def compile_should(should: Any, schema: Optional[AttrSchema], patients: PatientD
     return out
 
 
+DECAY_KINDS = ("gauss", "exp", "linear")
+FN_MODIFIERS = ("none", "log", "log1p", "log2p", "ln", "ln1p", "ln2p", "square", "sqrt", "reciprocal")
+_DAY_SPAN = {"d": 1, "w": 7}
+
+
+def _number(x: Any, what: str) -> float:
+    if isinstance(x, bool) or not isinstance(x, (int, float, np.integer, np.floating)) or not np.isfinite(x):
+        raise ValueError(f"{what} must be a finite number, got {x!r}")
+    return float(x)
+
+
+def _day_span(x: Any, what: str) -> float:
+    """A decay ``scale`` / ``offset`` on a date field, in days: ``"30d"`` / ``"2w"``, or a number of days.  The column holds
+    whole UTC days, so a span in hours, minutes, seconds or milliseconds is refused."""
+    if isinstance(x, str):
+        s = x.strip()
+        if len(s) >= 2 and s[:-1].isdigit() and s[-1] in _DAY_SPAN:
+            return float(int(s[:-1]) * _DAY_SPAN[s[-1]])
+        if s[:-1].isdigit() or s[:-2].isdigit():
+            raise ValueError(f"{what}: {x!r} is finer than a day (or not a d / w span): the date columns hold whole UTC days")
+        raise ValueError(f"{what}: {x!r} is not a span like '30d' or '2w'")
+    return _number(x, what)
+
+
+def compile_functions(functions: Any, schema: Optional[AttrSchema], patients: PatientDictionary, doc_types: PatientDictionary,
+                      now: Optional[_dt.datetime] = None) -> Tuple[List[dict], List[Any]]:
+    """OpenSearch ``function_score.functions`` entries as (records, filter plans) for ``FlatIndex.fn_from_attr``.  An entry is
+    ``{"gauss" | "exp" | "linear": {field: {"origin", "scale", "offset", "decay"}}}``, ``{"field_value_factor": {"field",
+    "factor", "modifier", "missing"}}`` or ``{"weight": w}`` alone; each may carry a ``"filter"`` (a clause as
+    ``compile_filter`` takes it) and a ``"weight"``.  Fields are the int and date attribute fields of the schema (a keyword
+    field has no numeric value).  On a date field ``origin`` is a date as a ``range`` bound takes it (``YYYY-MM-DD``, ISO
+    date-times, ``now``, ``now-30d``, with an optional ``/d`` rounding; default ``now``) and ``scale`` / ``offset`` are day
+    spans (``"30d"``, ``"2w"``, or a number of days); a span finer than a day is a ``ValueError``.  ``decay`` defaults to 0.5,
+    ``offset`` to 0.  A record is a dict ``{kind, col, weight, filter, ...}`` whose ``filter`` is None or an index into the
+    returned list of filter PLANS (each entry's ``filter`` compiled once, as ``compile_filter`` compiles it): resolve each with
+    ``run_plan`` and hand the bitmaps to ``fn_from_attr``.  A bare number as ``scale`` / ``offset`` on a date field is DAYS
+    here (OpenSearch reads a bare number on a date as milliseconds).  Every malformed entry raises ``ValueError`` naming it.  Pure Python: no GPU is touched."""
+    comp = Compiler(schema, patients, doc_types, now)
+    records: List[dict] = []
+    filters: List[Any] = []
+    for entry in functions or []:
+        if not isinstance(entry, dict):
+            raise ValueError(f"a function entry is a dict, got {entry!r}")
+        keys = [k for k in entry if k not in ("filter", "weight")]
+        if len(keys) > 1:
+            raise ValueError(f"a function entry holds one function, got {sorted(keys)}")
+        rec: dict = {"weight": 1.0, "filter": None}
+        if "weight" in entry:
+            rec["weight"] = _number(entry["weight"], "a function's weight")
+        if not keys:
+            if "weight" not in entry:
+                raise ValueError(f"a function entry without a function needs a weight, got {entry!r}")
+            rec.update(kind="weight", col=0)
+        elif keys[0] in DECAY_KINDS:
+            field, body = _one_field(entry[keys[0]], keys[0])
+            where = comp.schema.column(field)
+            if where is None or where[1] == "keyword":
+                raise ValueError(f"{keys[0]} decay needs an int or date attribute field, not {field!r}")
+            if not isinstance(body, dict) or "scale" not in body:
+                raise ValueError(f"{keys[0]} on {field!r}: expected {{origin, scale, offset, decay}}, got {body!r}")
+            unknown = set(body) - {"origin", "scale", "offset", "decay"}
+            if unknown:
+                raise ValueError(f"{keys[0]} on {field!r}: unsupported option(s) {sorted(unknown)}")
+            col, kind = where
+            what = f"{keys[0]} on {field!r}"
+            if kind == "date":
+                raw = body.get("origin", "now")
+                if isinstance(raw, str) and raw.strip().endswith("/d"):     # rounding down to the day: what the column holds
+                    raw = raw.strip()[:-2]
+                origin = date_bound_days(raw, comp.now)
+                if origin is None:
+                    raise ValueError(f"{what}: origin {body.get('origin')!r} is not a date or now±N(d|w|M|y)")
+                scale, offset = _day_span(body["scale"], f"{what}: scale"), _day_span(body.get("offset", 0), f"{what}: offset")
+            else:
+                if "origin" not in body:
+                    raise ValueError(f"{what}: an int field needs an origin")
+                origin = _number(body["origin"], f"{what}: origin")
+                scale, offset = _number(body["scale"], f"{what}: scale"), _number(body.get("offset", 0), f"{what}: offset")
+            decay = _number(body.get("decay", 0.5), f"{what}: decay")
+            if not scale > 0:
+                raise ValueError(f"{what}: scale must be > 0, got {body['scale']!r}")
+            if offset < 0:
+                raise ValueError(f"{what}: offset must be >= 0, got {body.get('offset')!r}")
+            if not 0 < decay < 1:
+                raise ValueError(f"{what}: decay must be in (0, 1), got {decay!r}")
+            rec.update(kind=keys[0], col=col, origin=float(origin), scale=scale, offset=offset, decay=decay)
+        elif keys[0] == "field_value_factor":
+            body = entry[keys[0]]
+            if not isinstance(body, dict) or "field" not in body:
+                raise ValueError(f"field_value_factor: expected {{field, factor, modifier, missing}}, got {body!r}")
+            unknown = set(body) - {"field", "factor", "modifier", "missing"}
+            if unknown:
+                raise ValueError(f"field_value_factor: unsupported option(s) {sorted(unknown)}")
+            where = comp.schema.column(body["field"])
+            if where is None or where[1] == "keyword":
+                raise ValueError(f"field_value_factor needs an int or date attribute field, not {body['field']!r}")
+            mod = body.get("modifier") or "none"
+            if mod not in FN_MODIFIERS:
+                raise ValueError(f"field_value_factor: modifier must be one of {FN_MODIFIERS}, not {mod!r}")
+            rec.update(kind="field_value_factor", col=where[0], factor=_number(body.get("factor", 1.0), "field_value_factor: factor"),
+                       modifier=mod, missing=None if body.get("missing") is None else _number(body["missing"], "field_value_factor: missing"))
+        else:
+            raise ValueError(f"unsupported function {keys[0]!r} (supported: gauss, exp, linear, field_value_factor, weight)")
+        if entry.get("filter") is not None:
+            rec["filter"] = len(filters)
+            filters.append(comp.compile(entry["filter"]))     # malformed filters raise here, before any GPU work
+        records.append(rec)
+    return records, filters
+
+
 def plan_calls(plan) -> int:
     """Builder calls a plan costs (for documentation and tests): one per 64 clauses of a leaf, one per tag set."""
     if plan[0] in ("all", "any"):

@@ -1,8 +1,9 @@
 // api_boost.hip — the C ABI of include/rass_engine.h: the boosted search rass_index_search_boosted(_device) (exact top-k of
 // boost * T(cos) + a per-row bonus column) and the builders of its columns: rass_index_bonus_scatter(_device),
 // rass_index_bonus_from_attr_clauses, rass_index_bonus_mask.  Host-side C++ only: the kernels are scan_boost.hip and bonus.hip;
-// the merge and the store of a pass are the allow-list search's (merge_topk.hip, allow.hip).  The objects and the threading
-// rules: api_internal.h.
+// the merge and the store of a pass are the allow-list search's (merge_topk.hip, allow.hip).  The pass driver
+// (boost_device_group) also serves the function-score search (api_fscore.hip, scan_fscore.hip).  The objects and the
+// threading rules: api_internal.h.
 
 #include <cmath>
 #include <tuple>
@@ -11,27 +12,8 @@
 
 namespace rass {
 namespace host {
-namespace {
 
-// One launch group (<= 32 queries) of a boosted search: normalise -> per pass of <= 32 hits: the boosted scan over every
-// tile, merge, store (which also leaves the next pass's continuation bound, on the fused score).  Everything is a device
-// pointer; the caller holds eng->mu, has set the device and has checked the arguments that do not depend on the row count.
-struct BoostRequest {
-    const float* queries = nullptr;     // [nq][dim]
-    int nq = 0;
-    int k = 0;
-    const float* boost = nullptr;       // [nq] or nullptr
-    int transform = 0;
-    const float* bonus = nullptr;       // query q's column at bonus + q * q_stride
-    int64_t q_stride = 0;               // 0: one column shared by every query
-    int64_t bonus_rows = 0;
-    const int32_t* q_filter = nullptr;
-    const int32_t* q_filter_mask = nullptr;
-    int64_t id_base = 0;
-    float* out_scores = nullptr;        // [nq][k]
-    int64_t* out_ids = nullptr;
-};
-
+// One launch group of a boosted or a function-score search: api_internal.h.
 int boost_device_group(rass_index* idx, const BoostRequest& r) {
     rass_engine* eng = idx->eng;
     hipStream_t st = eng->stream;
@@ -42,6 +24,9 @@ int boost_device_group(rass_index* idx, const BoostRequest& r) {
     if (iv.rows < 0 || iv.rows > kMaxScanRows) return fail(RASS_ERR_INVALID, "n_rows out of range for one scan");
     if (scratch_layout(nullptr, RASS_MAX_QBATCH, RASS_MAX_K).total > eng->scratch_bytes)
         return fail(RASS_ERR_INVALID, "scan workspace too small");
+    if (r.combine >= 0 && r.bonus_rows != iv.rows)
+        return fail(RASS_ERR_INVALID, "the function column covers " + std::to_string(r.bonus_rows) + " rows, the index holds " +
+                                          std::to_string(iv.rows) + ": fn_rows must equal the index's rows");
     if (iv.rows == 0) {   // nothing to scan: the empty answer
         HIP_TRY(rass::launch_fill_i32(reinterpret_cast<int32_t*>(r.out_scores), (int64_t)nq * k, (int32_t)0xff800000u, st));
         HIP_TRY(hipMemsetAsync(r.out_ids, 0xff, (size_t)nq * k * sizeof(int64_t), st));
@@ -76,7 +61,16 @@ int boost_device_group(rass_index* idx, const BoostRequest& r) {
         a.bonus_bytes = (unsigned)bonus_bytes;
         a.transform = r.transform;
         a.boost = r.boost;
-        int rc = timed_launch(eng, st, [&] { return HIP_RC(rass::launch_scan_boost_f32(a, grid, st)); });
+        int rc;
+        if (r.combine >= 0) {
+            rass::FscoreArgs f;
+            f.scan = a.scan;
+            f.fn = r.bonus, f.fn_q_stride = r.q_stride, f.fn_rows = r.bonus_rows, f.fn_bytes = (unsigned)bonus_bytes;
+            f.transform = r.transform, f.mode = r.combine, f.boost = r.boost, f.min_score = r.min_score;
+            rc = timed_launch(eng, st, [&] { return HIP_RC(rass::launch_scan_fscore_f32(f, grid, st)); });
+        } else {
+            rc = timed_launch(eng, st, [&] { return HIP_RC(rass::launch_scan_boost_f32(a, grid, st)); });
+        }
         if (rc != RASS_OK) return rc;
         HIP_TRY(rass::launch_merge_topk(L.part_scores, L.part_ids, grid, nq, kk, L.cand_scores, L.cand_ids, st));
         HIP_TRY(rass::launch_allow_store(L.cand_scores, L.cand_ids, nq, kk, k, kdone, iv.id_map ? 0 : r.id_base, iv.id_map, r.out_scores,
@@ -85,6 +79,8 @@ int boost_device_group(rass_index* idx, const BoostRequest& r) {
     }
     return RASS_OK;
 }
+
+namespace {
 
 // The argument checks the entry points share (everything that does not need the row count).
 int check_boosted(const rass_index* idx, int nq, int k, int transform, const float* d_bonus, int n_bonus, int64_t bonus_rows,

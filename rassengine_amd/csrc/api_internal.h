@@ -14,6 +14,8 @@
 //   api_ivf_allow.hip  the IVF probe within a row bitmap (probe plan -> slab-order bitmap words -> the allow-list scan), the probed lists
 //   api_allow.hip    the allow-list search (top-k within a per-query row bitmap), its bitmap builders, its plan, a bitmap's popcount
 //   api_boost.hip    the boosted search (top-k of boost * T(cos) + a per-row bonus column) and the builders of its columns
+//   api_fscore.hip   the function-score search (top-k of combine(boost * T(cos), a function column), gated by similarity) and
+//                    the builder of its columns; one pass driver with the boosted search (boost_device_group)
 //   api_keys.hip     the key columns built from the attribute columns (what the grouped search and the aggregation group by)
 //   api_attr.hip     the attribute columns of a flat index and the predicate builder that turns clauses over them into bitmaps
 //   api_mmr.hip      the diversified (MMR) search and the Gram matrices of row lists
@@ -660,6 +662,30 @@ struct AllowView {
 };
 AllowView allow_layout(unsigned char* base, int64_t rows);
 int check_words(int64_t rows, int64_t words);   // RASS_ERR_INVALID where words < ceil(rows / 32)
+// One launch group (<= 32 queries) of a boosted or a function-score search (api_boost.hip): normalise -> per pass of <= 32
+// hits: the scan over every tile, merge, store (which also leaves the next pass's continuation bound, on the fused score).
+// combine < 0: the boosted scan (scan_boost.hip), rows at or past bonus_rows read 0.  combine = RASS_COMBINE_*: the
+// function-score scan (scan_fscore.hip) with that mode and the gate min_score ([nq] or nullptr); bonus_rows must then equal the
+// index's rows at the call (RASS_ERR_INVALID otherwise).  Everything is a device pointer; the caller holds eng->mu, has set
+// the device and has checked the arguments that do not depend on the row count.
+struct BoostRequest {
+    const float* queries = nullptr;     // [nq][dim]
+    int nq = 0;
+    int k = 0;
+    const float* boost = nullptr;       // [nq] or nullptr
+    int transform = 0;
+    const float* bonus = nullptr;       // query q's column at bonus + q * q_stride
+    int64_t q_stride = 0;               // 0: one column shared by every query
+    int64_t bonus_rows = 0;
+    const int32_t* q_filter = nullptr;
+    const int32_t* q_filter_mask = nullptr;
+    int64_t id_base = 0;
+    float* out_scores = nullptr;        // [nq][k]
+    int64_t* out_ids = nullptr;
+    int combine = -1;
+    const float* min_score = nullptr;   // [nq] or nullptr (function-score scan only)
+};
+int boost_device_group(rass_index* idx, const BoostRequest& r);
 // The first two stages of a probe of one launch group (api_ivf.hip; the caller holds eng->mu): the top-nprobe centroids per
 // query — the flat fused scan for nprobe <= RASS_MAX_K (the lists, best first, stay at v->d_probe_ids [nq][min(nprobe, nlist)]),
 // the threshold path above — and the plan: the union of the probed lists as the work list v->d_work_* / d_n_work with per-tile

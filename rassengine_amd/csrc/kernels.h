@@ -197,6 +197,55 @@ hipError_t launch_bonus_clauses(const BonusClauseArgs& a, hipStream_t stream);
 hipError_t launch_bonus_mask(float* bonus, int n_bonus, int64_t stride, int64_t n_rows, const uint32_t* allow, int64_t allow_q_stride,
                              hipStream_t stream);
 
+// ---- function-score scan (scan_fscore.hip): exact top-k of fused = combine(boost[q] * T(cos), fn[q][row]) for one launch
+// group.  `scan`, `boost` and `transform` as in BoostArgs.  fn: query q's function column at fn + q * fn_q_stride (0: one
+// column shared by every query), fn_rows values each — fn_rows must equal scan.n_rows (no "rows past the column" here);
+// fn_bytes = 4 * ((nq - 1) * fn_q_stride + fn_rows) <= kBoostMaxBonusBytes.  mode: RASS_COMBINE_* (0 sum a + f, 1 multiply
+// a * f, 2 avg (a + f) * 0.5f, 3 max f > a ? f : a, 4 min f < a ? f : a, 5 replace f), every operation rounded on its own.
+// min_score [nq] or nullptr: a row ranks for q only with T(cos) >= min_score[q] (-inf: no gate).  A row ranks when the boosted
+// scan's conditions hold (on this fused score), the gate passes and f > -inf (a NaN or -inf cell excludes the row in EVERY
+// mode); order (fused desc, row asc).  No sample floor.
+constexpr int kCombineModes = 6;
+struct FscoreArgs {
+    ScanArgs scan;
+    const float* fn = nullptr;
+    int64_t fn_q_stride = 0;
+    int64_t fn_rows = 0;
+    unsigned fn_bytes = 0;
+    int transform = 0;
+    int mode = 0;
+    const float* boost = nullptr;
+    const float* min_score = nullptr;
+};
+hipError_t launch_scan_fscore_f32(const FscoreArgs& a, int grid, hipStream_t stream);
+
+// ---- function columns (score_fn.hip): a column block [nq][stride] filled from function records over the attribute columns,
+// for one launch group of nq <= 32 columns.  recs[q_off[q] .. q_off[q + 1]) are column q's functions in the caller's list
+// order.  kind 0 gauss exp(d * d * c), 1 exp exp(d * c), 2 linear max(0, (c - d) / c) with d = max(0, |v - p0| - p1) and c the
+// host-derived constant (1.0 on a missing value); 3 field_value_factor modifier(p0 * v) (v = `missing` on a missing value;
+// NaN there: the function does not apply); 4 weight 1.0.  filter: -1 or a bitmap index into filters[.][words]; a function
+// applies where its bit is set.  A function's value is weight * kind(v); the applying ones are folded in list order by
+// score_mode (0 multiply, 1 sum, 2 avg = sum(value) / sum(weight), 3 first, 4 max, 5 min; max / min as compare and select),
+// the result capped as value > max_boost ? max_boost : value; no applying function: 1.0.  ALL of it in double, rounded to
+// fp32 once at the store.  Rows [0, n_rows) of each column are written, tombstoned rows too; the padding is left alone.
+struct ScoreFnRec {
+    int32_t kind, col, filter, modifier;
+    double weight, p0, p1, c, missing;
+};
+struct ScoreFnArgs {
+    const int32_t* col[8] = {};      // kAttrCols
+    const ScoreFnRec* recs = nullptr;
+    const int32_t* q_off = nullptr;  // DEVICE int32 [nq + 1]
+    const uint32_t* filters = nullptr;
+    int64_t words = 0;
+    int64_t n_rows = 0;
+    float* out = nullptr;
+    int64_t stride = 0;
+    int nq = 0, score_mode = 0;
+    double max_boost = 0;
+};
+hipError_t launch_score_fn(const ScoreFnArgs& a, hipStream_t stream);
+
 // [n_lists][nq][k] sorted candidate lists -> [nq][k]; n_lists * k <= kMergeMaxCandidates.
 constexpr int kMergeMaxCandidates = 8192;
 // `groups` (optional): ONE launch merges the lists of several launch groups of <= size queries each; nq is then

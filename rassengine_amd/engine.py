@@ -1156,7 +1156,8 @@ class FlatIndex:
             self._h, ctypes.c_void_p(bonus.data_ptr()), n_bonus, stride, ctypes.c_void_p(allow.data_ptr()), n_bitmaps, words))
         return bonus
 
-    def _check_boosted(self, nq: int, k: int, boost, transform, n_bonus: int, stride: int, bonus_rows) -> Tuple[Optional[np.ndarray], int, int]:
+    def _check_boosted(self, nq: int, k: int, boost, transform, n_bonus: int, stride: int, bonus_rows,
+                       what: str = "boosted") -> Tuple[Optional[np.ndarray], int, int]:
         """The argument checks of ``search_boosted``, made before any native call: (boost f32 [nq] or None, transform code,
         bonus_rows)."""
         if not 1 <= k <= N.RASS_MAX_K_MULTIPASS:
@@ -1179,7 +1180,7 @@ class FlatIndex:
         if not 0 <= rows <= stride:
             raise ValueError(f"bonus_rows must be in [0, {stride}], got {rows}")
         if self.dtype != "f32" or self.row_stride > 1024:
-            raise ValueError("boosted search needs an fp32 index with dim <= 1024")
+            raise ValueError(f"{what} search needs an fp32 index with dim <= 1024")
         return b, self.BOOST_TRANSFORMS[transform], rows
 
     def search_boosted(self, queries: np.ndarray, k: int, bonus, boost=None, transform: str = "raw", bonus_rows: Optional[int] = None,
@@ -1247,6 +1248,153 @@ class FlatIndex:
                                                          ctypes.c_void_p(d_q_filter_ptr or 0),
                                                          ctypes.c_void_p(d_q_filter_mask_ptr or 0), int(id_base),
                                                          ctypes.c_void_p(d_out_scores_ptr), ctypes.c_void_p(d_out_ids_ptr)))
+
+    # ---- function-score search: exact top-k of combine(boost * T(cos), a function column), gated by the similarity
+    COMBINE_MODES = {"sum": N.RASS_COMBINE_SUM, "multiply": N.RASS_COMBINE_MULTIPLY, "avg": N.RASS_COMBINE_AVG,
+                     "max": N.RASS_COMBINE_MAX, "min": N.RASS_COMBINE_MIN, "replace": N.RASS_COMBINE_REPLACE}
+    FN_KINDS = {"gauss": N.RASS_FN_GAUSS, "exp": N.RASS_FN_EXP, "linear": N.RASS_FN_LINEAR,
+                "field_value_factor": N.RASS_FN_FIELD_VALUE, "weight": N.RASS_FN_WEIGHT}
+    FN_MODIFIERS = {"none": N.RASS_FN_MOD_NONE, "log": N.RASS_FN_MOD_LOG, "log1p": N.RASS_FN_MOD_LOG1P, "log2p": N.RASS_FN_MOD_LOG2P,
+                    "ln": N.RASS_FN_MOD_LN, "ln1p": N.RASS_FN_MOD_LN1P, "ln2p": N.RASS_FN_MOD_LN2P, "square": N.RASS_FN_MOD_SQUARE,
+                    "sqrt": N.RASS_FN_MOD_SQRT, "reciprocal": N.RASS_FN_MOD_RECIPROCAL}
+    FN_SCORE_MODES = {"multiply": N.RASS_FN_SCORE_MULTIPLY, "sum": N.RASS_FN_SCORE_SUM, "avg": N.RASS_FN_SCORE_AVG,
+                      "first": N.RASS_FN_SCORE_FIRST, "max": N.RASS_FN_SCORE_MAX, "min": N.RASS_FN_SCORE_MIN}
+    MAX_SCORE_FNS = N.RASS_MAX_SCORE_FNS
+
+    @classmethod
+    def _fn_records(cls, functions):
+        """``functions`` (dicts, see ``fn_from_attr``) as a ctypes array of ``rass_score_fn_t``."""
+        functions = list(functions or [])
+        recs = (N.ScoreFn * max(1, len(functions)))()
+        for r, f in zip(recs, functions):
+            if not isinstance(f, dict) or f.get("kind") not in cls.FN_KINDS:
+                raise ValueError(f"a function is a dict whose kind is one of {sorted(cls.FN_KINDS)}, got {f!r}")
+            unknown = set(f) - {"query", "kind", "col", "filter", "weight", "origin", "scale", "offset", "decay", "factor",
+                                "modifier", "missing"}
+            if unknown:
+                raise ValueError(f"unknown function field(s) {sorted(unknown)}")
+            mod = f.get("modifier") or "none"
+            if mod not in cls.FN_MODIFIERS:
+                raise ValueError(f"modifier must be one of {sorted(cls.FN_MODIFIERS)}, not {mod!r}")
+            r.query, r.kind, r.col = int(f.get("query", 0)), cls.FN_KINDS[f["kind"]], int(f.get("col", 0))
+            r.filter = -1 if f.get("filter") is None else int(f["filter"])
+            r.modifier, r.reserved, r.weight = cls.FN_MODIFIERS[mod], 0, float(f.get("weight", 1.0))
+            r.origin, r.scale, r.offset = float(f.get("origin", 0.0)), float(f.get("scale", 1.0)), float(f.get("offset", 0.0))
+            r.decay, r.factor = float(f.get("decay", 0.5)), float(f.get("factor", 1.0))
+            r.missing = float("nan") if f.get("missing") is None else float(f["missing"])
+        return recs, len(functions)
+
+    def fn_from_attr(self, column, functions, score_mode: str = "multiply", max_boost: Optional[float] = None, filters=None):
+        """Fill the device column block ``column`` (from ``new_bonus``: [stride] shared, or [nq, stride]) from a list of
+        functions over the attribute columns (``rass_index_fn_from_attr``): OpenSearch's ``function_score.functions``.
+        A function is a dict: ``kind`` "gauss" / "exp" / "linear" (``col``, ``origin``, ``scale`` > 0, ``offset`` >= 0, 0 <
+        ``decay`` < 1; a missing value gives 1.0), "field_value_factor" (``col``, ``factor``, ``modifier`` none / log / log1p
+        / log2p / ln / ln1p / ln2p / square / sqrt / reciprocal, ``missing``: the stand-in for a missing value, None = the
+        function skips the row) or "weight" (the constant 1.0); ``query`` (the column it belongs to, default 0), ``weight``
+        (default 1.0), ``filter`` (None, or an index into ``filters``).  ``filters``: int32 CUDA [n, words] (or [words], or a
+        list of [words] tensors) row bitmaps as ``allow_from_attr_clauses`` / ``run_plan`` build them.  A query's applying functions are folded in list
+        order by ``score_mode`` (multiply / sum / avg / first / max / min), capped at ``max_boost``; a row no function applies
+        to gets 1.0.  At most 16 functions per query per call.  Double arithmetic on the device, rounded to fp32 once.  A
+        non-positive argument of a log modifier gives -inf / NaN, which ``search_scored`` treats as "row excluded".
+        Returns ``column``."""
+        import torch
+        n_fn, stride = self._bonus_shape(column)
+        if score_mode not in self.FN_SCORE_MODES:
+            raise ValueError(f"score_mode must be one of {sorted(self.FN_SCORE_MODES)}, not {score_mode!r}")
+        recs, n = self._fn_records(functions)
+        cap = float("inf") if max_boost is None else float(max_boost)
+        n_filters, words, fptr = 0, 0, None
+        if isinstance(filters, (list, tuple)):      # one bitmap per entry, each [words]
+            filters = torch.stack(list(filters)).contiguous() if filters else None
+        if filters is not None:
+            if not hasattr(filters, "data_ptr") or not filters.is_cuda or filters.dtype != torch.int32 or not filters.is_contiguous():
+                raise ValueError("filters must be a contiguous int32 CUDA tensor [n, words] (or [words])")
+            n_filters, words = (1, int(filters.shape[0])) if filters.dim() == 1 else (int(filters.shape[0]), int(filters.shape[1]))
+            fptr = ctypes.c_void_p(filters.data_ptr())
+        torch.cuda.current_stream(column.device).synchronize()     # the engine works on its own stream
+        N.check("rass_index_fn_from_attr", self._L.rass_index_fn_from_attr(
+            self._h, ctypes.cast(recs, ctypes.c_void_p), n, n_fn, self.FN_SCORE_MODES[score_mode], cap, fptr, n_filters, words,
+            ctypes.c_void_p(column.data_ptr()), stride))
+        return column
+
+    def search_scored(self, queries: np.ndarray, k: int, column, boost=None, transform: str = "raw", combine: str = "multiply",
+                      min_score=None, q_filter: Optional[np.ndarray] = None, q_filter_mask: Optional[np.ndarray] = None,
+                      on_device: bool = False) -> Tuple[np.ndarray, np.ndarray]:
+        """Exact top-k of ``combine(boost[q] * T(cos), column[q][row])`` (``rass_index_search_scored``): OpenSearch's
+        ``function_score`` around a k-NN clause.  ``column``: a device block ([stride] shared, [nq, stride] one per query)
+        from ``new_bonus`` filled by ``fn_from_attr`` (and ``bonus_mask``), or a numpy array of that shape, uploaded; it must
+        hold a value for every row of the index.  ``combine``: sum / multiply / avg / max / min / replace (``boost_mode``).
+        ``min_score``: one number or one per query, a gate on T(cos) (None / -inf: no gate).  ``boost`` / ``transform`` /
+        filters as in ``search_boosted``.  A row ranks when it is live, passes the filters and the gate, and its cosine, its
+        column value and its fused score are all above -inf: a NaN or -inf cell excludes the row in every mode.  Returns
+        (fused f32 [nq, k], ids i64 [nq, k]): best first, ties by id ascending, (-inf, -1) padding.  fp32 indices with dim <=
+        1024.  ``on_device``: go through the device-resident entry point.  Thread-safe."""
+        q = self._queries(queries)
+        nq, k = q.shape[0], int(k)
+        f, m = self._filters(q_filter, q_filter_mask, nq)
+        host = None
+        if isinstance(column, np.ndarray):
+            host = np.ascontiguousarray(column, dtype=np.float32)
+            if host.ndim not in (1, 2) or host.shape[-1] % 32 != 0:
+                raise ValueError(f"column must be [stride] or [n, stride] with stride a multiple of 32, got {host.shape}")
+            n_fn, stride = (1, host.shape[0]) if host.ndim == 1 else host.shape
+        else:
+            n_fn, stride = self._bonus_shape(column)
+        if combine not in self.COMBINE_MODES:
+            raise ValueError(f"combine must be one of {sorted(self.COMBINE_MODES)}, not {combine!r}")
+        rows = self.rows
+        if stride < rows:
+            raise ValueError(f"the column holds {stride} cells, the index {rows} rows")
+        b, t_code, _ = self._check_boosted(nq, k, boost, transform, n_fn, stride, rows, what="function-score")
+        gate = None if min_score is None else self._thresholds(min_score, nq)
+        out_s = np.empty((nq, k), dtype=np.float32)
+        out_i = np.empty((nq, k), dtype=np.int64)
+        if nq == 0:
+            return out_s, out_i
+        import torch
+        dev = f"cuda:{self.engine.device}"
+        if host is not None:
+            column = torch.from_numpy(host).to(dev)
+        torch.cuda.current_stream(column.device).synchronize()     # the engine works on its own stream
+        if on_device:
+            dq = torch.from_numpy(q).to(dev)
+            db = torch.from_numpy(b).to(dev) if b is not None else None
+            dg = torch.from_numpy(gate).to(dev) if gate is not None else None
+            df = torch.from_numpy(f).to(dev) if f is not None else None
+            dm = torch.from_numpy(m).to(dev) if m is not None else None
+            ds = torch.empty((nq, k), dtype=torch.float32, device=dev)
+            di = torch.empty((nq, k), dtype=torch.int64, device=dev)
+            torch.cuda.current_stream(column.device).synchronize()
+            self.search_scored_device(dq.data_ptr(), nq, k, column.data_ptr(), n_fn, rows, stride, ds.data_ptr(), di.data_ptr(),
+                                      d_boost_ptr=db.data_ptr() if db is not None else 0, transform=transform, combine=combine,
+                                      d_min_score_ptr=dg.data_ptr() if dg is not None else 0,
+                                      d_q_filter_ptr=df.data_ptr() if df is not None else 0,
+                                      d_q_filter_mask_ptr=dm.data_ptr() if dm is not None else 0)
+            self.engine.synchronize()
+            return ds.cpu().numpy(), di.cpu().numpy()
+        N.check("rass_index_search_scored", self._L.rass_index_search_scored(
+            self._h, _np_ptr(q), nq, k, _np_ptr(b), t_code, self.COMBINE_MODES[combine], _np_ptr(gate),
+            ctypes.c_void_p(column.data_ptr()), n_fn, rows, stride, _np_ptr(f), _np_ptr(m), _np_ptr(out_s), _np_ptr(out_i)))
+        return out_s, out_i
+
+    def search_scored_device(self, d_queries_ptr: int, nq: int, k: int, d_fn_ptr: int, n_fn: int, fn_rows: int, fn_stride: int,
+                             d_out_scores_ptr: int, d_out_ids_ptr: int, d_boost_ptr: int = 0, transform: str = "raw",
+                             combine: str = "multiply", d_min_score_ptr: int = 0, id_base: int = 0, d_q_filter_ptr: int = 0,
+                             d_q_filter_mask_ptr: int = 0) -> None:
+        """Async, device-resident ``search_scored`` (``rass_index_search_scored_device``): nq <= 4096 in launch groups of 32,
+        k <= 4096 (every pass enqueued by the one call).  Boosts and gates are device memory: their values are the caller's."""
+        if transform not in self.BOOST_TRANSFORMS:
+            raise ValueError(f"transform must be raw / opensearch, not {transform!r}")
+        if combine not in self.COMBINE_MODES:
+            raise ValueError(f"combine must be one of {sorted(self.COMBINE_MODES)}, not {combine!r}")
+        N.check("rass_index_search_scored_device",
+                self._L.rass_index_search_scored_device(self._h, ctypes.c_void_p(d_queries_ptr), int(nq), int(k),
+                                                        ctypes.c_void_p(d_boost_ptr or 0), self.BOOST_TRANSFORMS[transform],
+                                                        self.COMBINE_MODES[combine], ctypes.c_void_p(d_min_score_ptr or 0),
+                                                        ctypes.c_void_p(d_fn_ptr), int(n_fn), int(fn_rows), int(fn_stride),
+                                                        ctypes.c_void_p(d_q_filter_ptr or 0),
+                                                        ctypes.c_void_p(d_q_filter_mask_ptr or 0), int(id_base),
+                                                        ctypes.c_void_p(d_out_scores_ptr), ctypes.c_void_p(d_out_ids_ptr)))
 
     MAX_MMR_FETCH = N.RASS_MAX_MMR_FETCH   # search_mmr: candidates per query; rows_gram: rows per list
 

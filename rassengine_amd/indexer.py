@@ -58,6 +58,8 @@ BOOST_HYBRID_STRUCTURED = 2.0  # app/main.py:1754
 BOOST_MULTI_INTENT = 1.5       # app/main.py:2003
 # how much deeper than k the two ranked lists are read before they are fused by doc_id
 FUSION_OVERFETCH = 4
+# semantic_search_recent sorts by an fp32 copy of an int32 field: exact for |v| < 2^24, and +-2^24 stands for "no value"
+RECENT_MAX_ABS = float(1 << 24)
 
 
 def _score_out(cos: float, mode: Optional[str] = None) -> float:
@@ -649,6 +651,128 @@ class HipIndexer:
                 if where is not None:
                     st.index.bonus_mask(bonus, run_plan(st.index, compile_filter(where, st.attrs, st.patients, st.doc_types)))
                 scores, ids = st.index.search_boosted(q, k_eff, bonus, boost=boost, transform=transform, **flt)
+                out: List[Tuple[Dict, float]] = []
+                for s, row in zip(scores[0], ids[0]):
+                    if row < 0:
+                        break
+                    doc = st.row_doc[int(row)] if int(row) < len(st.row_doc) else None
+                    if doc is None:
+                        continue
+                    hit = dict(doc)
+                    if config.RASS_RETURN_EMBEDDING:
+                        hit["embedding"] = st.index.get_row(int(row)).tolist()  # reference quirk 5
+                    out.append((hit, float(s)))
+                return out
+        raise RuntimeError(f"{self.index_name}: the index was compacted during every one of {LAYOUT_ATTEMPTS} searches")
+
+    def semantic_search_scored(self, query_emb: np.ndarray, k: int = TOP_K, functions: Optional[List[Dict]] = None,
+                               score_mode: str = "multiply", boost_mode: str = "multiply", max_boost: Optional[float] = None,
+                               min_score: Optional[float] = None, boost: float = 1.0, where: Optional[Any] = None,
+                               filter_clause: Optional[Dict] = None, patient_id: Optional[str] = None,
+                               doc_type: Optional[str] = None, knn_score_mode: Optional[str] = None) -> List[Tuple[Dict, float]]:
+        """An OpenSearch ``function_score`` around the k-NN clause, answered exactly over EVERY chunk of the index
+        (``FlatIndex.search_scored``): the top ``k`` chunks by ``boost_mode(boost * knn_score, functions' value)``.
+        ``functions``: ``function_score.functions`` entries (``gauss`` / ``exp`` / ``linear`` decay, ``field_value_factor``,
+        ``weight``, each with an optional ``filter`` and ``weight``; ``attrfilter.compile_functions``), folded per chunk by
+        ``score_mode`` (multiply / sum / avg / first / max / min) and capped at ``max_boost``; a chunk no function applies to
+        is worth 1.0.  ``boost_mode``: multiply / sum / avg / max / min / replace.  ``min_score``: only chunks whose
+        ``knn_score`` (before the boost) is at least this rank.  ``where``: a filter as ``semantic_search_filtered`` takes it.
+        ``filter_clause`` / ``patient_id`` / ``doc_type`` as in ``semantic_search``.  ``knn_score`` is in
+        ``knn_score_mode``'s units (default ``RASS_SCORE_MODE``).  A log modifier over a non-positive value excludes the chunk
+        (OpenSearch raises).  Returns ``[(doc_dict, float(fused))]`` best first; ``[]`` on an empty embedding or on any
+        exception (logged)."""
+        if _empty(query_emb):
+            return []
+        try:
+            return self._scored(query_emb, k, functions, score_mode, boost_mode, max_boost, min_score, boost, where, filter_clause,
+                                patient_id, doc_type, knn_score_mode)
+        except Exception as e:
+            logger.error(f"Function-score search error: {e}")
+            return []
+
+    def semantic_search_recent(self, query_emb: np.ndarray, k: int = TOP_K, field: str = "conditionOnsetDateTime",
+                               min_score: Optional[float] = None, order: str = "desc", missing: str = "exclude",
+                               where: Optional[Any] = None, filter_clause: Optional[Dict] = None, patient_id: Optional[str] = None,
+                               doc_type: Optional[str] = None, knn_score_mode: Optional[str] = None) -> List[Tuple[Dict, float]]:
+        """The vector counterpart of the reference's ``temporal_search`` sort (app/main.py:1866-1918): the ``k`` chunks with
+        ``knn_score >= min_score`` ordered by ``field`` (an int or date attribute field), ``order`` "desc" (latest first) or
+        "asc"; ties by row.  ``missing`` "exclude" drops the chunks without the field, "_last" places them after every chunk
+        that has it.  Exact over the whole index, however many chunks pass ``min_score``: ``boost_mode`` replace over a
+        ``field_value_factor`` (negated for "asc").  Exact only while the field's values are exactly representable in fp32 and
+        apart from the stand-in for "no value" (|v| < 2^24; days since 1970 are): checked with ``attr_minmax`` under the same
+        lock as the search, else ``ValueError``.  Returns ``[(doc_dict,
+        float(sort value))]`` — the field's value (days since 1970 for a date), NaN for a chunk without it; ``[]`` on an
+        empty embedding or on any exception (logged)."""
+        if _empty(query_emb):
+            return []
+        try:
+            if order not in ("desc", "asc"):
+                raise ValueError(f"order must be desc / asc, not {order!r}")
+            if missing not in ("exclude", "_last"):
+                raise ValueError(f"missing must be exclude / _last, not {missing!r}")
+            st: Optional[IndexState] = REGISTRY.get(self.index_name, create=False)
+            if st is None:
+                return []
+            col = st.attrs.column(field) if st.attrs is not None else None
+            if col is None or col[1] == "keyword":
+                raise ValueError(f"{field!r} is not an int or date attribute field of {self.index_name}")
+            sign = 1.0 if order == "desc" else -1.0
+            fvf = {"field": field, "factor": sign}
+            if missing == "_last":
+                fvf["missing"] = -sign * RECENT_MAX_ABS     # below every stored value after the factor
+            hits = self._scored(query_emb, k, [{"field_value_factor": fvf}], "first", "replace", None, min_score, 1.0, where,
+                                filter_clause, patient_id, doc_type, knn_score_mode,
+                                missing_excludes=missing == "exclude", exact_field=(field, col[0]))
+            return [(d, float("nan") if s == -RECENT_MAX_ABS else sign * s) for d, s in hits]
+        except Exception as e:
+            logger.error(f"Recent search error: {e}")
+            return []
+
+    def _scored(self, query_emb, k, functions, score_mode, boost_mode, max_boost, min_score, boost, where, filter_clause, patient_id,
+                doc_type, knn_score_mode, missing_excludes: bool = False, exact_field: Optional[Tuple[str, int]] = None
+                ) -> List[Tuple[Dict, float]]:
+        st: Optional[IndexState] = REGISTRY.get(self.index_name, create=False)
+        if st is None:
+            return []
+        prep = self._prepare(st, query_emb, k, filter_clause, patient_id, doc_type)
+        if prep is None:
+            return []
+        q, k_eff, (fval, fmask) = prep
+        flt = dict(q_filter=np.array([fval], dtype=np.int32), q_filter_mask=np.array([fmask], dtype=np.int32)) if fmask else {}
+        if not hasattr(st.index, "search_scored") or not hasattr(st.index, "fn_from_attr"):
+            raise NotImplementedError(f"{self.index_name}: {type(st.index).__name__} has no function-score search "
+                                      "(sharded indices cannot rank by a function column; use a flat fp32 index)")
+        boost = float(boost)
+        if not np.isfinite(boost):
+            raise ValueError(f"boost must be finite, got {boost!r}")
+        gate = None if min_score is None else float(min_score)
+        if gate is not None and np.isnan(gate):
+            raise ValueError("min_score must not be NaN")
+        transform = "raw" if (knn_score_mode or config.RASS_SCORE_MODE) == "cosine" else "opensearch"
+        from .attrfilter import compile_filter, compile_functions, run_plan
+        for _ in range(LAYOUT_ATTEMPTS):    # the column and the ids belong to ONE layout of the index, as in _boosted
+            layout = _layout_epoch(st.index)
+            # under the state's lock from the first cell to the search: no row is appended in between (add_documents takes
+            # the lock), so the column covers every row the scan sees
+            with st.lock:
+                if _layout_epoch(st.index) != layout:
+                    continue
+                if exact_field is not None and hasattr(st.index, "attr_minmax"):     # semantic_search_recent: see its docstring
+                    lo, hi, _ = st.index.attr_minmax(exact_field[1])
+                    if lo is not None and max(abs(int(lo)), abs(int(hi))) >= RECENT_MAX_ABS:
+                        raise ValueError(f"{exact_field[0]!r} holds values of 2^24 or beyond in size: not exactly representable in "
+                                         "fp32 (or equal to the stand-in for a missing value), the order would not be exact")
+                records, plans = compile_functions(functions, st.attrs, st.patients, st.doc_types)
+                bitmaps = [run_plan(st.index, plan) for plan in plans] or None
+                column = st.index.new_bonus()
+                st.index.fn_from_attr(column, records, score_mode=score_mode, max_boost=max_boost, filters=bitmaps)
+                if missing_excludes:    # semantic_search_recent: the one function skipped the rows without the field (1.0 there)
+                    exists = {"exists": {"field": functions[0]["field_value_factor"]["field"]}}
+                    st.index.bonus_mask(column, run_plan(st.index, compile_filter(exists, st.attrs, st.patients, st.doc_types)))
+                if where is not None:
+                    st.index.bonus_mask(column, run_plan(st.index, compile_filter(where, st.attrs, st.patients, st.doc_types)))
+                scores, ids = st.index.search_scored(q, k_eff, column, boost=boost, transform=transform, combine=boost_mode,
+                                                     min_score=gate, **flt)
                 out: List[Tuple[Dict, float]] = []
                 for s, row in zip(scores[0], ids[0]):
                     if row < 0:
