@@ -724,6 +724,38 @@ int rass_index_search_grouped_keys_device(rass_index_t* idx, const float* d_quer
                                           const int32_t* d_q_filter, const int32_t* d_q_filter_mask,
                                           int64_t id_base, float* d_out_scores, int64_t* d_out_ids,
                                           int32_t* d_out_groups, int64_t* d_group_total, int32_t* d_status);
+/* INNER HITS of the grouped search over a key column: the group_size best rows of each of a query's k best groups — OpenSearch's
+ * collapse + inner_hits {size: n}, or terms -> top_hits — and, optionally, the CAPPED list: the exact top-k of all live matching
+ * rows with at most group_size rows taken from any one group ("the best k chunks, at most m per source document").  One corpus
+ * pass per launch group, whatever group_size is.  Arguments as rass_index_search_grouped_keys(_device), plus:
+ * group_size in [1, RASS_MAX_GROUP_SIZE], with n_groups * group_size <= 1048576 (the engine-owned table of a 32-query launch
+ *   group then stays within the grouped search's 256 MiB; it is grown on demand, and RASS_ERR_OOM leaves the engine as it was);
+ * out_scores / out_ids [nq][k][group_size]: group j of query q (the grouped search's j-th: out_groups [nq][k] and
+ *   out_group_total [nq] are exactly what rass_index_search_grouped_keys reports) holds its rows best first under (score
+ *   descending, row ascending); entry [q][j][0] is the grouped search's [q][j]; (-inf, -1) past a group's last matching row and
+ *   for a missing group;
+ * out_capped_scores / out_capped_ids [nq][k], both or neither (NULL: skipped): the capped list, best first under (score
+ *   descending, row ordinal ascending) whatever ids the rows carry, (-inf, -1) past the end.  It needs k * group_size <=
+ *   RASS_MAX_K_MULTIPASS.  With group_size >= the largest group it is the plain top-k.
+ * k <= RASS_MAX_K_MULTIPASS; any bound broken: RASS_ERR_INVALID.  fp32 flat indices with dim <= 1024 only: a bf16 index or a
+ * wide-row index answers RASS_ERR_UNSUPPORTED.  The prefilter mode is ignored: always the exact fp32 scan, and a score is the
+ * flat scan's bit for bit.  The host variant takes any nq in launch groups of 32 and fails with RASS_ERR_INVALID where a
+ * matching row's key is >= n_groups; the device variant takes nq <= RASS_MAX_DEVICE_BATCH in launch groups of 32, is
+ * stream-ordered, synchronises nothing and reports that condition as *d_status = 1 (0 otherwise). */
+#define RASS_MAX_GROUP_SIZE 16
+int rass_index_search_group_hits_keys(rass_index_t* idx, const float* queries, int nq, int k,
+                                      const int32_t* d_keys, int64_t n_keys, int32_t n_groups, int group_size,
+                                      const uint32_t* d_allow, int n_bitmaps, int64_t words_per_bitmap,
+                                      const int32_t* q_filter, const int32_t* q_filter_mask,
+                                      float* out_scores, int64_t* out_ids, int32_t* out_groups,
+                                      int64_t* out_group_total, float* out_capped_scores, int64_t* out_capped_ids);
+int rass_index_search_group_hits_keys_device(rass_index_t* idx, const float* d_queries, int nq, int k,
+                                             const int32_t* d_keys, int64_t n_keys, int32_t n_groups, int group_size,
+                                             const uint32_t* d_allow, int n_bitmaps, int64_t words_per_bitmap,
+                                             const int32_t* d_q_filter, const int32_t* d_q_filter_mask,
+                                             int64_t id_base, float* d_out_scores, int64_t* d_out_ids,
+                                             int32_t* d_out_groups, int64_t* d_group_total,
+                                             float* d_out_capped_scores, int64_t* d_out_capped_ids, int32_t* d_status);
 int rass_index_aggregate_keys(rass_index_t* idx, const float* queries, int nq, const float* min_score, int size,
                               const int32_t* d_keys, int64_t n_keys, int32_t n_groups,
                               const uint32_t* d_allow, int n_bitmaps, int64_t words_per_bitmap,

@@ -244,8 +244,10 @@ struct GroupRequest : EmitRequest {
     int32_t* status = nullptr;          // [1]
 };
 
-// The table block at least `need` bytes.  The new block is allocated BEFORE the old one is let go: a failure leaves the engine
-// as it was.  Growth waits for the stream first: an earlier call on it may still use the old block.
+}  // namespace
+
+// The table block at least `need` bytes (api_internal.h; api_grouptop.hip grows it too).  The new block is allocated BEFORE the
+// old one is let go: a failure leaves the engine as it was.  Growth waits for the stream first: an earlier call on it may still use the old block.
 int grow_group_table(rass_engine* eng, size_t need, hipStream_t st, const char* who) {
     if (eng->group_bytes >= need) return RASS_OK;
     unsigned char* block = nullptr;
@@ -263,6 +265,8 @@ int grow_group_table(rass_engine* eng, size_t need, hipStream_t st, const char* 
     eng->group_bytes = need;
     return RASS_OK;
 }
+
+namespace {
 
 int group_device_group(rass_index* idx, const GroupRequest& r) {
     rass_engine* eng = idx->eng;

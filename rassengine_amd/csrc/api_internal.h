@@ -16,6 +16,8 @@
 //   api_boost.hip    the boosted search (top-k of boost * T(cos) + a per-row bonus column) and the builders of its columns
 //   api_fscore.hip   the function-score search (top-k of combine(boost * T(cos), a function column), gated by similarity) and
 //                    the builder of its columns; one pass driver with the boosted search (boost_device_group)
+//   api_grouptop.hip the grouped search with inner hits (the group_size best rows of each top group, the capped list) over a
+//                    key column, on a scan family of its own (scan_grouptop.hip) and the grouped search's table block
 //   api_keys.hip     the key columns built from the attribute columns (what the grouped search and the aggregation group by)
 //   api_attr.hip     the attribute columns of a flat index and the predicate builder that turns clauses over them into bitmaps
 //   api_mmr.hip      the diversified (MMR) search and the Gram matrices of row lists
@@ -662,6 +664,9 @@ struct AllowView {
 };
 AllowView allow_layout(unsigned char* base, int64_t rows);
 int check_words(int64_t rows, int64_t words);   // RASS_ERR_INVALID where words < ceil(rows / 32)
+// The engine's table block (eng->d_group) at least `need` bytes (api_emit.hip): allocated before the old block is let go, so
+// RASS_ERR_OOM leaves the engine as it was; `who` names the search in the message.
+int grow_group_table(rass_engine* eng, size_t need, hipStream_t st, const char* who);
 // One launch group (<= 32 queries) of a boosted or a function-score search (api_boost.hip): normalise -> per pass of <= 32
 // hits: the scan over every tile, merge, store (which also leaves the next pass's continuation bound, on the fused score).
 // combine < 0: the boosted scan (scan_boost.hip), rows at or past bonus_rows read 0.  combine = RASS_COMBINE_*: the

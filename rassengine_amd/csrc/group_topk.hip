@@ -14,6 +14,10 @@
 // empty slot — doc_count descending, then group key ascending, OpenSearch's default bucket order.  Slots are distinct, so these
 // keys are unique too and the select, the gather and the sort are the ones above.  A listed bucket's score and id come from
 // the slot of the group-max table the scan kept next to the counters; the counters' sum is the query's number of hits.
+//
+// group_hits_finish_kernel runs behind the select of a grouped search with inner hits (scan_grouptop.hip; kernels.h
+// launch_group_hits_finish): the table then has group_size planes, the select has read plane 0, and the finish reads every plane
+// of the slots it chose.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -191,6 +195,82 @@ __global__ __launch_bounds__(kGroupSelThreads) void group_select_kernel(const un
         og[i] = g;
         if (COUNT) out_counts[(int64_t)q * k + i] = c;
     }
+}
+
+// The inner hits of a group-top scan (kernels.h launch_group_hits_finish): levels 0 .. gs - 1 of every slot the select chose,
+// and, where the caller asks, the capped list — those k * gs keys sorted by the bitonic network above, the k largest written.
+// A row of the capped answer lies in a group whose best row ranks at least as high; were that group not among the k best
+// groups, k groups would each own a better row and the row could not be in the top k: the selected groups suffice.
+__global__ __launch_bounds__(kGroupSelThreads) void group_hits_finish_kernel(const unsigned long long* __restrict__ table, int nq,
+                                                                             int n_groups, int k, int gs, int64_t id_base,
+                                                                             const int64_t* __restrict__ id_map,
+                                                                             const int32_t* __restrict__ groups, float* out_scores,
+                                                                             int64_t* out_ids, float* __restrict__ cap_scores,
+                                                                             int64_t* __restrict__ cap_ids,
+                                                                             const unsigned* __restrict__ status,
+                                                                             int32_t* __restrict__ out_status, int accumulate) {
+    __shared__ unsigned long long keys[kGroupMaxK];
+    const int q = blockIdx.x, tid = threadIdx.x;
+    const int64_t plane = (int64_t)nq * n_groups;
+    const unsigned long long* tab = table + (int64_t)q * n_groups;
+    const int32_t* grp = groups + (int64_t)q * k;
+    const int n = k * gs;
+    const bool capped = cap_scores != nullptr;
+    if (tid == 0 && q == 0) {
+        const int s = *status != 0u ? 1 : 0;
+        if (!accumulate || s) *out_status = s;
+    }
+    auto put = [&](float* os, int64_t* oi, int64_t at, unsigned long long key) {
+        float s = -INFINITY;
+        int64_t id = -1;
+        if (key != 0ull) {
+            const int64_t row = (int64_t)(0xffffffffu - (unsigned)key);
+            s = key_score((unsigned)(key >> 32));
+            id = id_map ? id_map[row] : id_base + row;
+        }
+        os[at] = s;
+        oi[at] = id;
+    };
+    for (int i = tid; i < n; i += kGroupSelThreads) {
+        const int j = i / gs, l = i - j * gs;
+        const int g = grp[j];
+        const unsigned long long key = g >= 0 ? tab[(int64_t)l * plane + g] : 0ull;
+        put(out_scores, out_ids, (int64_t)q * n + i, key);
+        if (capped) keys[i] = key;
+    }
+    if (!capped) return;   // uniform over the launch
+    int n2 = 1;
+    while (n2 < n) n2 <<= 1;
+    for (int i = n + tid; i < n2; i += kGroupSelThreads) keys[i] = 0ull;
+    __syncthreads();
+    for (int size = 2; size <= n2; size <<= 1)
+        for (int stride = size >> 1; stride > 0; stride >>= 1) {
+            for (int i = tid; i < n2; i += kGroupSelThreads) {
+                const int j = i ^ stride;
+                if (j > i) {
+                    const unsigned long long a = keys[i], b = keys[j];
+                    const bool descending = (i & size) == 0;
+                    if ((a < b) == descending) keys[i] = b, keys[j] = a;
+                }
+            }
+            __syncthreads();
+        }
+    for (int i = tid; i < k; i += kGroupSelThreads) put(cap_scores, cap_ids, (int64_t)q * k + i, i < n2 ? keys[i] : 0ull);
+}
+
+hipError_t launch_group_hits_finish(const unsigned long long* table, int nq, int n_groups, int k, int group_size, int64_t id_base,
+                                    const int64_t* id_map, const int32_t* groups, float* out_scores, int64_t* out_ids,
+                                    float* cap_scores, int64_t* cap_ids, const unsigned* status, int32_t* out_status, bool accumulate,
+                                    hipStream_t stream) {
+    if (nq < 1 || k < 1 || k > kGroupMaxK || n_groups < 1 || n_groups > kGroupMaxGroups || group_size < 1 ||
+        group_size > kGroupHitsMaxSize || (int64_t)n_groups * group_size > kGroupMaxGroups || !table || !groups || !out_scores ||
+        !out_ids || !status || !out_status)
+        return hipErrorInvalidValue;
+    if ((cap_scores == nullptr) != (cap_ids == nullptr)) return hipErrorInvalidValue;
+    if (cap_scores != nullptr && (int64_t)k * group_size > kGroupMaxK) return hipErrorInvalidValue;   // the keys' 32 KiB of LDS
+    hipLaunchKernelGGL(group_hits_finish_kernel, dim3(nq), dim3(kGroupSelThreads), 0, stream, table, nq, n_groups, k, group_size, id_base,
+                       id_map, groups, out_scores, out_ids, cap_scores, cap_ids, status, out_status, accumulate ? 1 : 0);
+    return hipGetLastError();
 }
 
 hipError_t launch_group_select(const unsigned long long* table, int nq, int n_groups, int k, int64_t id_base, const int64_t* id_map,

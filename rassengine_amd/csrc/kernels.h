@@ -170,6 +170,24 @@ struct BoostArgs {
 };
 hipError_t launch_scan_boost_f32(const BoostArgs& a, int grid, hipStream_t stream);
 
+// ---- group-top scan (scan_grouptop.hip): the group_size best rows of every (query, group) for one launch group, in one pass.
+// `scan` carries what a key-column group-max launch of launch_scan_topk_f32 would (corpus, row_tag or nullptr, q_padded
+// [32][row_stride] zero-padded, q_filter / q_filter_mask, group_keys / group_key_rows, group_n, group_status, allow /
+// allow_q_stride, row_stride 128 * {1..8}, n_rows >= 1, nq <= 32); every other field of it stays at its default.
+// scan.group_table is LEVEL-MAJOR, [group_size][nq][group_n] 64-bit slots zeroed by the caller: level l of (q, g) at
+// group_table[l * level_stride + q * group_n + g], level_stride >= nq * group_n.  It ends holding, per (q, g), the candidate
+// keys (scan_core.h cand_key) of the group's matching rows from the largest down, 0 past the group's last row: plane 0 is what
+// the group-max scan leaves, so launch_group_select reads it as it stands.  1 <= group_size <= kGroupHitsMaxSize and
+// group_n * group_size <= kGroupMaxGroups (below).  No ranking: no TopList, no sample floor, no continuation bound.
+// ScanArgs itself is untouched.
+constexpr int kGroupHitsMaxSize = 16;
+struct GroupTopArgs {
+    ScanArgs scan;
+    int64_t level_stride = 0;
+    int group_size = 0;
+};
+hipError_t launch_scan_grouptop_f32(const GroupTopArgs& a, int grid, hipStream_t stream);
+
 // ---- bonus columns (bonus.hip): the dense fp32 columns the boosted scan adds.  A column block is [n_bonus][stride] floats.
 // Plain vector loads and stores, no atomics.
 // bonus[q_of[i] * stride + rows[i]] = that value + values[i] (one rounded add) for i < n.  The (q, row) pairs must be UNIQUE
@@ -290,6 +308,17 @@ hipError_t launch_group_count_select(const unsigned* counts, const unsigned long
                                      const int64_t* id_map, int32_t* out_groups, int64_t* out_counts, float* out_scores, int64_t* out_ids,
                                      int64_t* n_buckets, int64_t* total_hits, const unsigned* status, int32_t* out_status,
                                      hipStream_t stream);
+// The inner hits of a group-top scan (scan_grouptop.hip) behind launch_group_select over plane 0 of its table, one workgroup
+// per query.  table is level-major [group_size][nq][n_groups]; groups [nq][k] is what the select wrote (-1 past the end).
+// out_scores / out_ids [nq][k][group_size] = levels 0 .. group_size - 1 of each selected slot, decoded and translated as the
+// select does; (-inf, -1) past a group's last row and for a missing group.  They may overlap what the select wrote as
+// out_scores / out_ids: neither is read.  cap_scores / cap_ids [nq][k] (both or neither; k * group_size <= kGroupMaxK): the k
+// largest of those k * group_size keys, best first under (score desc, row asc), (-inf, -1) past the end.
+// *out_status = the scan's status word as 0 / 1; with `accumulate` it is only ever raised (a call's later launch groups).
+hipError_t launch_group_hits_finish(const unsigned long long* table, int nq, int n_groups, int k, int group_size, int64_t id_base,
+                                    const int64_t* id_map, const int32_t* groups, float* out_scores, int64_t* out_ids,
+                                    float* cap_scores, int64_t* cap_ids, const unsigned* status, int32_t* out_status, bool accumulate,
+                                    hipStream_t stream);
 
 // ---- allow-list search (allow.hip): row bitmaps, their work list, and the store of a pass.  A bitmap is uint32 words, bit
 // (r & 31) of word r >> 5 allows row r.  Plain vector loads, stores and atomics.

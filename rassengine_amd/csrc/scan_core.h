@@ -315,6 +315,37 @@ __device__ __forceinline__ void emit_group_max(bool ok, float s, int row, int ta
     if (key > __hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(slot, key);
 }
 
+// The emission of a group-top scan (scan_grouptop.hip), in the place of insert_candidates: emit_group_max with a CHAIN of
+// `levels` slots per (query, group) — level l of group g at table[slot_q + l * level_stride + g], all zeroed by the caller — that ends
+// as the group's `levels` largest candidate keys, best first, whatever order the workgroups ran in.  The key enters level 0
+// by a 64-bit atomicMax that returns what the slot held; the smaller of the two, the displaced one, moves down a level, until
+// it falls into an empty slot or off the end.  Level 0 takes in every key and ends as their maximum; every other key is handed
+// to level 1 exactly once (as the loser of one exchange), so level 1 ends as the second largest, and so on by induction.  Keys
+// are unique (rows are distinct).  The pre-read of the LAST level skips a key that cannot be among the `levels` largest: slots
+// only grow, so a stale value costs extra atomics and never an answer.  g: the row's group (>= 0); one >= n_groups on a
+// matching row is left out and sets *status.  Plain vector loads and atomics, relaxed, agent scope.
+__device__ __forceinline__ void emit_group_top(bool ok, float s, int row, int g, int n_groups, unsigned long long* table,
+                                               unsigned slot_q, unsigned level_stride, int levels, unsigned* status) {
+    // NaN and -inf never rank: such a row is no match, so it is in no group and sets no status
+    if (!ok || !(s > -INFINITY)) return;
+    if ((unsigned)g >= (unsigned)n_groups) {
+        __hip_atomic_store(status, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        return;
+    }
+    unsigned long long key = cand_key(s, row);
+    // the whole table is addressed by one 32-bit slot index (levels * nq * n_groups <= 2^25) from a wave-uniform base
+    unsigned slot = slot_q + (unsigned)g;
+    if (key <= __hip_atomic_load(table + (slot + (unsigned)(levels - 1) * level_stride), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return;
+    for (int l = 0; l < levels - 1; ++l, slot += level_stride) {
+        const unsigned long long old = __hip_atomic_fetch_max(table + slot, key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        key = old < key ? old : key;   // the displaced one moves down a level
+        if (key == 0ull) return;       // it displaced an empty slot
+    }
+    // the last level: what it displaces falls off the end, so nothing is read back and the lane does not wait (with one level
+    // this is emit_group_max's atomic)
+    (void)__hip_atomic_fetch_max(table + slot, key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
 // The emission of a group-count scan (kGroupCount), in the place of insert_candidates: a half-wave holds one query's 32 rows
 // of a tile, `hit` says which of them count (live, filters passed, a real query, score >= the query's threshold).  A hit
 // whose group key is >= n_groups is left out and sets *status, as in emit_group_max.  Slot of a hit: q * n_groups + g of

@@ -785,6 +785,66 @@ class FlatIndex:
                     ctypes.c_void_p(d_out_scores_ptr), ctypes.c_void_p(d_out_ids_ptr), ctypes.c_void_p(d_out_groups_ptr),
                     ctypes.c_void_p(d_group_total_ptr), ctypes.c_void_p(d_status_ptr)))
 
+    MAX_GROUP_SIZE = N.RASS_MAX_GROUP_SIZE   # search_group_hits: rows kept per group
+
+    @staticmethod
+    def _check_group_hits(k, n_groups, group_size, capped) -> Tuple[int, int, int]:
+        k, _, n_groups = FlatIndex._check_grouped(k, 1, n_groups)
+        group_size = int(group_size)
+        if not 1 <= group_size <= FlatIndex.MAX_GROUP_SIZE:
+            raise ValueError(f"group_size must be in [1, {FlatIndex.MAX_GROUP_SIZE}], got {group_size}")
+        if n_groups * group_size > FlatIndex.MAX_GROUPS:
+            raise ValueError(f"n_groups * group_size must not exceed {FlatIndex.MAX_GROUPS}, got {n_groups} * {group_size}")
+        if capped and k * group_size > N.RASS_MAX_K_MULTIPASS:
+            raise ValueError(f"the capped list needs k * group_size <= {N.RASS_MAX_K_MULTIPASS}, got {k} * {group_size}")
+        return k, n_groups, group_size
+
+    def search_group_hits(self, queries: np.ndarray, k: int, keys, n_groups: int, group_size: int, allow=None,
+                          q_filter: Optional[np.ndarray] = None, q_filter_mask: Optional[np.ndarray] = None, capped: bool = False):
+        """``search_grouped_by_keys`` with inner hits (``rass_index_search_group_hits_keys``): the ``group_size`` best rows of
+        each of a query's ``k`` best groups, in one corpus pass.  ``keys`` / ``allow`` / filters as in
+        ``search_grouped_by_keys``.  Returns ``(scores [nq, k, group_size], ids, groups [nq, k], totals [nq])``: a group's rows
+        best first (score descending, row ascending), ``[q, j, 0]`` being what ``search_grouped_by_keys`` reports at
+        ``[q, j]``, ``(-inf, -1)`` past a group's last matching row.  ``capped=True`` appends ``(capped_scores [nq, k],
+        capped_ids)``: the exact top-k of all matching rows with at most ``group_size`` rows of any one group (needs
+        ``k * group_size <= 4096``).  fp32 indices with dim <= 1024."""
+        q = self._queries(queries)
+        nq = q.shape[0]
+        k, n_groups, group_size = self._check_group_hits(k, n_groups, group_size, capped)
+        f, m = self._filters(q_filter, q_filter_mask, nq)
+        self._check_keys(keys, allow, nq)
+        out_s = np.empty((nq, k, group_size), dtype=np.float32)
+        out_i = np.empty((nq, k, group_size), dtype=np.int64)
+        out_g = np.empty((nq, k), dtype=np.int32)
+        total = np.empty((nq,), dtype=np.int64)
+        cap_s = np.empty((nq, k), dtype=np.float32) if capped else None
+        cap_i = np.empty((nq, k), dtype=np.int64) if capped else None
+        if nq > 0:
+            fn = "rass_index_search_group_hits_keys"
+            self._by_keys(fn, keys, allow, lambda d_keys, n_keys, d_allow, n_bitmaps, words: self._L.rass_index_search_group_hits_keys(
+                self._h, _np_ptr(q), nq, k, d_keys, n_keys, n_groups, group_size, d_allow, n_bitmaps, words, _np_ptr(f), _np_ptr(m),
+                _np_ptr(out_s), _np_ptr(out_i), _np_ptr(out_g), _np_ptr(total), _np_ptr(cap_s), _np_ptr(cap_i)))
+        return (out_s, out_i, out_g, total, cap_s, cap_i) if capped else (out_s, out_i, out_g, total)
+
+    def search_group_hits_device(self, d_queries_ptr: int, nq: int, k: int, d_keys_ptr: int, n_keys: int, n_groups: int,
+                                 group_size: int, d_out_scores_ptr: int, d_out_ids_ptr: int, d_out_groups_ptr: int,
+                                 d_group_total_ptr: int, d_status_ptr: int, d_out_capped_scores_ptr: int = 0,
+                                 d_out_capped_ids_ptr: int = 0, d_allow_ptr: int = 0, n_bitmaps: int = 0, words_per_bitmap: int = 0,
+                                 id_base: int = 0, d_q_filter_ptr: int = 0, d_q_filter_mask_ptr: int = 0) -> None:
+        """Async, device-resident ``search_group_hits`` (``rass_index_search_group_hits_keys_device``): nq <= 4096 in launch
+        groups of 32.  Outputs ``[nq, k, group_size]`` scores / ids, ``[nq, k]`` groups, ``[nq]`` totals and, where both
+        capped pointers are given, the ``[nq, k]`` capped list.  Nothing is padded: ``n_keys`` below the index's rows is
+        refused.  ``*d_status`` = 1 where a matching row's key was >= ``n_groups``."""
+        k, n_groups, group_size = self._check_group_hits(k, n_groups, group_size, bool(d_out_capped_scores_ptr))
+        N.check("rass_index_search_group_hits_keys_device",
+                self._L.rass_index_search_group_hits_keys_device(
+                    self._h, ctypes.c_void_p(d_queries_ptr), int(nq), k, ctypes.c_void_p(d_keys_ptr), int(n_keys), n_groups,
+                    group_size, ctypes.c_void_p(d_allow_ptr or 0), int(n_bitmaps), int(words_per_bitmap),
+                    ctypes.c_void_p(d_q_filter_ptr or 0), ctypes.c_void_p(d_q_filter_mask_ptr or 0), int(id_base),
+                    ctypes.c_void_p(d_out_scores_ptr), ctypes.c_void_p(d_out_ids_ptr), ctypes.c_void_p(d_out_groups_ptr),
+                    ctypes.c_void_p(d_group_total_ptr), ctypes.c_void_p(d_out_capped_scores_ptr or 0),
+                    ctypes.c_void_p(d_out_capped_ids_ptr or 0), ctypes.c_void_p(d_status_ptr)))
+
     def search_counts_by_keys(self, queries: np.ndarray, min_score, size: int, keys, n_groups: int, allow=None,
                               q_filter: Optional[np.ndarray] = None, q_filter_mask: Optional[np.ndarray] = None
                               ) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray, np.ndarray, np.ndarray]:

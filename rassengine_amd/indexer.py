@@ -331,6 +331,78 @@ class HipIndexer:
                 return hits, int(totals[0])
         raise RuntimeError(f"{self.index_name}: the index was compacted during every one of {LAYOUT_ATTEMPTS} searches")
 
+    def semantic_search_collapsed_hits(self, query_emb: np.ndarray, k: int = TOP_K, collapse: str = "patientId",
+                                       inner_hits: int = 3, filter_clause: Optional[Dict] = None,
+                                       patient_id: Optional[str] = None, where: Optional[Any] = None
+                                       ) -> Tuple[List[List[Tuple[Dict, float]]], int]:
+        """``semantic_search_collapsed`` with ``"inner_hits": {"size": inner_hits}``: the ``inner_hits`` (1 .. 16) best chunks
+        of each of the k best values of ``collapse``, in one pass over the index whatever ``inner_hits`` is
+        (``FlatIndex.search_group_hits``).  Returns ``(groups, total_groups)``: ``groups[j]`` is a best-first list of
+        ``(doc_dict, float(score))`` — ``groups[j][0]`` is what ``semantic_search_collapsed`` returns at position j, a value
+        with fewer matching chunks has a shorter list — and the exact number of distinct values among the matching chunks.
+        ``collapse``, ``where`` and the filters as in ``semantic_search_collapsed``; every field, ``patientId`` and
+        ``doc_type`` included, goes through a key column built on the GPU.  fp32 flat indices with dim <= 1024.  An empty
+        embedding or an unindexed patient gives ``([], 0)``; errors raise."""
+        def finish(st, out, layout):
+            scores, ids, _groups, totals = out[:4]
+            groups: List[List[Tuple[Dict, float]]] = []
+            for j in range(scores.shape[1]):
+                if ids[0, j, 0] < 0:
+                    break
+                hits = self._hits(st, scores[0, j], ids[0, j], 1.0, None, layout)
+                if hits is None:
+                    return None
+                if hits:
+                    groups.append(hits)
+            return groups, int(totals[0])
+        got = self._group_hits("collapse", query_emb, k, collapse, inner_hits, filter_clause, patient_id, where, False, finish)
+        return ([], 0) if got is None else got
+
+    def semantic_search_capped(self, query_emb: np.ndarray, k: int = TOP_K, per: str = "patientId", max_per_group: int = 1,
+                               filter_clause: Optional[Dict] = None, patient_id: Optional[str] = None,
+                               where: Optional[Any] = None) -> List[Tuple[Dict, float]]:
+        """The k best chunks with at most ``max_per_group`` (1 .. 16) of them from any one value of ``per`` — the usual way
+        to keep one long document from filling a context window — exactly, in one pass over the index
+        (``FlatIndex.search_group_hits`` with ``capped=True``; needs ``k * max_per_group <= 4096``).  ``per``, ``where`` and
+        the filters as ``collapse`` in ``semantic_search_collapsed``.  Returns ``[(doc_dict, float(score))]`` best first in
+        ``semantic_search``'s score units.  An empty embedding or an unindexed patient gives ``[]``; errors raise."""
+        got = self._group_hits("per", query_emb, k, per, max_per_group, filter_clause, patient_id, where, True,
+                               lambda st, out, layout: self._hits(st, out[4][0], out[5][0], 1.0, None, layout))
+        return [] if got is None else got
+
+    def _group_hits(self, what, query_emb, k, field, group_size, filter_clause, patient_id, where, capped, finish):
+        """What the two methods above share: the key column (and bitmap) and ``FlatIndex.search_group_hits`` under one layout
+        epoch per attempt, as ``semantic_search_collapsed`` runs its keyed path; ``finish(st, out, layout)`` maps the ids (None:
+        a compaction landed, search again).  None: the empty answer."""
+        st: Optional[IndexState] = REGISTRY.get(self.index_name, create=False)
+        by = _GroupBy(what, field, st)
+        if _empty(query_emb) or st is None:
+            return None
+        prep = self._prepare(st, query_emb, k, filter_clause, patient_id, None)
+        if prep is None:
+            return None
+        q, k_eff, (fval, fmask) = prep
+        if not hasattr(st.index, "search_group_hits"):
+            raise NotImplementedError(f"{self.index_name}: {type(st.index).__name__} has no grouped search with inner hits "
+                                      "(IVF-backed and sharded indices cannot collapse; use a flat fp32 index)")
+        if int(getattr(st.index, "dim", 0)) > 1024:
+            raise NotImplementedError(f"{self.index_name}: the grouped search with inner hits needs dim <= 1024 (no wide-row form)")
+        self._need_keys(st, where, "grouped search")
+        flt = dict(q_filter=np.array([fval], dtype=np.int32), q_filter_mask=np.array([fmask], dtype=np.int32)) if fmask else {}
+        for _ in range(LAYOUT_ATTEMPTS):    # row ids belong to one layout of the index, as in _knn
+            layout = _layout_epoch(st.index)
+            built = self._keys_and_bitmap(st, by, where, layout)
+            if built is None:
+                continue
+            keyed, allow = built
+            if keyed is None:
+                return None
+            out = st.index.search_group_hits(q, k_eff, keyed[0], keyed[1], int(group_size), allow=allow, capped=capped, **flt)
+            got = finish(st, out, layout)
+            if got is not None:
+                return got
+        raise RuntimeError(f"{self.index_name}: the index was compacted during every one of {LAYOUT_ATTEMPTS} searches")
+
     def _need_keys(self, st: IndexState, where: Any, what: str) -> None:
         """The refusals of a key-column call, before anything is built."""
         index = st.index
