@@ -1257,7 +1257,9 @@ int rass_gemm_bf16_ws(const void* d_x, const void* d_w, const float* d_bias,
  * app/main.py:225-237): d_qkv bf16 [tokens][3*hidden] (q | k | v per token), sequences packed back to back with
  * d_cu_seqlens[nseq + 1] token offsets (total_tokens = the last one, as the host knows it), heads of 64
  * (hidden = 64 * heads), every sequence <= max_seqlen <= 512, softmax(q k^T / 8) v in fp32, d_ctx bf16
- * [total_tokens][hidden]. */
+ * [total_tokens][hidden].  A sequence may be EMPTY (two equal offsets; the offsets live on the device, so the host
+ * cannot refuse one as rass_encode does): it owns no rows of d_ctx and nothing is written for it, whichever kernel the
+ * launch takes; the rows of its neighbours are what they are without it. */
 int rass_attention_bf16(const void* d_qkv, const int32_t* d_cu_seqlens, int nseq, int total_tokens,
                         int max_seqlen, int hidden, int heads, void* d_ctx, void* stream);
 /* Query time (embed_query / ollama_embed_text, app/main.py:225-237, 266-274: one text, a dozen tokens): the attention and

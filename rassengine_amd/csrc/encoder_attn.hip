@@ -902,7 +902,12 @@ __global__ __launch_bounds__(kA64Threads) void attention64_kernel(const u16* __r
             load_q_next();
             wait_all();
             __syncthreads();
-            if (nc - 1 < nc_next) dma_chunk(next, nc - 1);
+            // nc == 0 is an EMPTY sequence (every wave is here; the branch above has S > 0, so nc >= 1 there): it owns no
+            // rows of the image and has no last chunk to hand over.  Unguarded, -1 < nc_next held whatever nc_next was and
+            // dma_chunk(next, -1) ran: rows -128 .. -1, i.e. the V pieces over the K image's last chunk, the K pieces 16 KiB
+            // in front of the allocation, and with no next item cu_seqlens read past its end.  All of the next item's
+            // chunks were sent above (j = 0 .. nc_next - 1) and have landed behind this barrier.
+            if (nc >= 1 && nc - 1 < nc_next) dma_chunk(next, nc - 1);
         }
 #ifdef RASS_ATTN_STAMPS
         {
@@ -912,7 +917,8 @@ __global__ __launch_bounds__(kA64Threads) void attention64_kernel(const u16* __r
         }
 #endif
         if (!has_next) break;
-        sync0 = nc < 3;  // chunk 1 (nc == 2) or chunk 0 (nc == 1) of the next item was only just sent
+        sync0 = nc < 3;  // chunk 1 (nc == 2) or chunk 0 (nc == 1) of the next item was only just sent (after an empty item,
+                         // nc == 0, nothing is in flight: the wait is then merely redundant)
         q_fresh = true;  // load_q_next() replaced the fragments (both branches above end in wait_all())
         item = next;
     }

@@ -1,5 +1,5 @@
-"""K6 on its own (rass_attention_bf16): the encoder's varlen self-attention against a plain PyTorch fp32 reference of the
-same op (softmax(q k^T / 8) v per sequence and head, fp32 throughout, on the same bf16 inputs).
+"""K6 on its own (rass_attention_bf16): the encoder's varlen self-attention against a plain PyTorch fp64 reference of the
+same op (softmax(q k^T / 8) v per sequence and head, fp64 throughout, on the same bf16 inputs: tests/attention_ref.py).
 
 Tolerance: the kernel rounds the exponentiated scores to bf16 before the second product (relative 2^-9 per term, so
 the bound follows sum_j p_j |v_j|, not the possibly cancelled result) and the output to bf16:
@@ -16,24 +16,16 @@ import os
 import numpy as np
 import pytest
 
+import attention_ref as A
+
 pytestmark = pytest.mark.gpu
 
 LENS_EDGE = [1, 2, 15, 16, 17, 31, 32, 33, 63, 64, 65, 100, 127, 128, 129, 200, 255, 256, 257, 300, 320, 448, 511, 512]
 
 
 def _reference(torch, qkv, lens, heads):
-    hidden = qkv.shape[1] // 3
-    out = torch.empty((qkv.shape[0], hidden), dtype=torch.float32, device=qkv.device)
-    mag = torch.empty_like(out)
-    t = 0
-    for n in lens:
-        blk = qkv[t:t + n].float().view(n, 3, heads, 64)
-        q, k, v = blk[:, 0].transpose(0, 1), blk[:, 1].transpose(0, 1), blk[:, 2].transpose(0, 1)   # [heads][n][64]
-        p = torch.softmax(q @ k.transpose(1, 2) / 8.0, dim=-1)
-        out[t:t + n] = (p @ v).transpose(0, 1).reshape(n, hidden)
-        mag[t:t + n] = (p @ v.abs()).transpose(0, 1).reshape(n, hidden)
-        t += n
-    return out, mag
+    """fp64 on the device (tests/attention_ref.py): (out, mag = p @ |v|)."""
+    return A.reference(qkv, lens, heads)
 
 
 def _run(torch, qkv, lens, heads, max_seqlen=None):
@@ -164,7 +156,7 @@ def _fused_case(torch, lens, seed, scale=1.0):
         ctypes.c_void_p(y.data_ptr()), n, st))
     torch.cuda.synchronize()
     assert bool((y[total:] == 555.0).all()) and bool((y_pair[total:] == 555.0).all())      # rows past the batch untouched
-    # fp32 reference of the whole op on the same bf16 inputs
+    # reference of the whole op on the same bf16 inputs (the context in fp64, the projection in fp32)
     ref_ctx, _ = _reference(torch, qkv[:total], lens, heads)
     ref = ref_ctx.bfloat16().float() @ w.float().t() + bias + res[:total].float()
     return y[:total].float(), y_pair[:total].float(), ref
