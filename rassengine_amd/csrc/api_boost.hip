@@ -2,8 +2,8 @@
 // boost * T(cos) + a per-row bonus column) and the builders of its columns: rass_index_bonus_scatter(_device),
 // rass_index_bonus_from_attr_clauses, rass_index_bonus_mask.  Host-side C++ only: the kernels are scan_boost.hip and bonus.hip;
 // the merge and the store of a pass are the allow-list search's (merge_topk.hip, allow.hip).  The pass driver
-// (boost_device_group) also serves the function-score search (api_fscore.hip, scan_fscore.hip).  The objects and the
-// threading rules: api_internal.h.
+// (boost_device_group), the argument checks and the host and device group loops (boost_search_host / boost_search_device) also
+// serve the function-score search (api_fscore.hip, scan_fscore.hip).  The objects and the threading rules: api_internal.h.
 
 #include <cmath>
 #include <tuple>
@@ -82,58 +82,108 @@ int boost_device_group(rass_index* idx, const BoostRequest& r) {
 
 namespace {
 
-// The argument checks the entry points share (everything that does not need the row count).
-int check_boosted(const rass_index* idx, int nq, int k, int transform, const float* d_bonus, int n_bonus, int64_t bonus_rows,
-                  int64_t bonus_stride, const int32_t* q_filter, const int32_t* q_filter_mask) {
-    if (nq < 0 || nq > RASS_MAX_DEVICE_BATCH) return fail(RASS_ERR_INVALID, "nq must be in [0, RASS_MAX_DEVICE_BATCH]");
-    if (k < 1 || k > RASS_MAX_K_MULTIPASS) return fail(RASS_ERR_INVALID, "k must be in [1, RASS_MAX_K_MULTIPASS]");
-    if (transform != RASS_BOOST_RAW && transform != RASS_BOOST_OPENSEARCH)
+// Launch group [done, done + r.nq) of the call `c` (device pointers): its slice of every per-query array, its column(s).
+BoostRequest group_of(const BoostRequest& c, int done, int dim, int n_cols, int64_t col_stride) {
+    const bool shared = n_cols == 1;
+    BoostRequest r = c;
+    r.queries = c.queries + (int64_t)done * dim, r.nq = std::min(RASS_MAX_QBATCH, c.nq - done);
+    r.boost = c.boost ? c.boost + done : nullptr, r.min_score = c.min_score ? c.min_score + done : nullptr;
+    r.bonus = c.bonus + (shared ? 0 : (int64_t)done * col_stride), r.q_stride = shared ? 0 : col_stride;
+    r.q_filter = c.q_filter ? c.q_filter + done : nullptr, r.q_filter_mask = c.q_filter_mask ? c.q_filter_mask + done : nullptr;
+    r.out_scores = c.out_scores + (int64_t)done * c.k, r.out_ids = c.out_ids + (int64_t)done * c.k;
+    return r;
+}
+
+// The argument checks the entry points share (everything that does not need the row count: fn_rows == the index's rows is
+// checked by boost_device_group under the engine's lock, before a group's first launch).
+int check_boosted(const rass_index* idx, const BoostRequest& c, int n_cols, int64_t col_stride, bool scored) {
+    const char *col = scored ? "fn" : "bonus", *who = scored ? "function-score" : "boosted";   // the words of the messages
+    if (!idx || !c.out_scores || !c.out_ids) return fail(RASS_ERR_INVALID, "NULL argument");
+    if (c.nq > 0 && !c.queries) return fail(RASS_ERR_INVALID, "bad queries / nq");
+    if (c.nq < 0 || c.nq > RASS_MAX_DEVICE_BATCH) return fail(RASS_ERR_INVALID, "nq must be in [0, RASS_MAX_DEVICE_BATCH]");
+    if (c.k < 1 || c.k > RASS_MAX_K_MULTIPASS) return fail(RASS_ERR_INVALID, "k must be in [1, RASS_MAX_K_MULTIPASS]");
+    if (c.transform != RASS_BOOST_RAW && c.transform != RASS_BOOST_OPENSEARCH)
         return fail(RASS_ERR_INVALID, "transform must be RASS_BOOST_RAW or RASS_BOOST_OPENSEARCH");
-    if (nq > 0 && !d_bonus) return fail(RASS_ERR_INVALID, "NULL argument");
-    if (nq > 0 && n_bonus != 1 && n_bonus != nq) return fail(RASS_ERR_INVALID, "n_bonus must be 1 (shared) or nq (one column per query)");
-    if (bonus_rows < 0 || bonus_stride < bonus_rows) return fail(RASS_ERR_INVALID, "bonus_rows must be in [0, bonus_stride]");
-    if (q_filter_mask && !q_filter) return fail(RASS_ERR_INVALID, "q_filter_mask without q_filter");
-    if (idx->dtype != RASS_F32) return fail(RASS_ERR_UNSUPPORTED, "boosted search needs an fp32 index");
-    if (idx->stride > kNarrowStride) return fail(RASS_ERR_UNSUPPORTED, "boosted search needs dim <= 1024 (no wide-row form)");
+    if (scored && (c.combine < RASS_COMBINE_SUM || c.combine > RASS_COMBINE_REPLACE))
+        return fail(RASS_ERR_INVALID, "combine must be one of RASS_COMBINE_*");
+    if (c.nq > 0 && !c.bonus) return fail(RASS_ERR_INVALID, "NULL argument");
+    if (c.nq > 0 && n_cols != 1 && n_cols != c.nq)
+        return fail(RASS_ERR_INVALID, std::string("n_") + col + " must be 1 (shared) or nq (one column per query)");
+    if (c.bonus_rows < 0 || col_stride < c.bonus_rows)
+        return fail(RASS_ERR_INVALID, std::string(col) + "_rows must be in [0, " + col + "_stride]");
+    if (c.q_filter_mask && !c.q_filter) return fail(RASS_ERR_INVALID, "q_filter_mask without q_filter");
+    if (idx->dtype != RASS_F32) return fail(RASS_ERR_UNSUPPORTED, std::string(who) + " search needs an fp32 index");
+    if (idx->stride > kNarrowStride) return fail(RASS_ERR_UNSUPPORTED, std::string(who) + " search needs dim <= 1024 (no wide-row form)");
     return RASS_OK;
 }
 
-// One attempt of the host boosted search (host_groups): the group's queries and filters through a pinned slot as
-// rass_index_search_ex, its boosts and its [b][k] answer through the engine's own staging block (eng->d_allow_io).
-int search_boosted_once(rass_index_t* idx, const float* queries, int nq, int k, const float* boost, int transform, const float* d_bonus,
-                        int n_bonus, int64_t bonus_rows, int64_t bonus_stride, const int32_t* q_filter, const int32_t* q_filter_mask,
-                        float* out_scores, int64_t* out_ids) {
+// One attempt of the host search (host_groups): the group's queries and filters through a pinned slot as
+// rass_index_search_ex, its boosts, its gates (the function-score search's) and its [b][k] answer through the engine's own
+// staging block (eng->d_allow_io).
+int search_boosted_once(rass_index_t* idx, const BoostRequest& c, int n_cols, int64_t col_stride, bool scored) {
     rass_engine* eng = idx->eng;
-    const bool shared = n_bonus == 1;
+    const int k = c.k;
     return host_groups(
-        idx, queries, nq, q_filter, q_filter_mask, /*io_bytes=*/0, no_fill,
+        idx, c.queries, c.nq, c.q_filter, c.q_filter_mask, /*io_bytes=*/0, no_fill,
         [&](HostSlot*, int done, int b) -> int {
             hipStream_t st = eng->stream;
             const size_t cells = (size_t)b * k;
-            Carver c{nullptr};
-            c.take<float>(RASS_MAX_QBATCH * sizeof(float));
-            c.take<float>((size_t)RASS_MAX_QBATCH * k * sizeof(float));
-            c.take<int64_t>((size_t)RASS_MAX_QBATCH * k * sizeof(int64_t));
-            if (int rc = grow_block(&eng->d_allow_io, &eng->allow_io_bytes, c.off, st)) return rc;
-            Carver d{eng->d_allow_io};
-            float* d_boost = d.take<float>(RASS_MAX_QBATCH * sizeof(float));
-            float* d_s = d.take<float>((size_t)RASS_MAX_QBATCH * k * sizeof(float));
-            int64_t* d_i = d.take<int64_t>((size_t)RASS_MAX_QBATCH * k * sizeof(int64_t));
-            // (pageable source: the copy has read the caller's array when it returns)
-            if (boost) HIP_TRY(hipMemcpyAsync(d_boost, boost + done, (size_t)b * sizeof(float), hipMemcpyHostToDevice, st));
-            BoostRequest r;
-            r.queries = eng->d_qraw, r.nq = b, r.k = k, r.boost = boost ? d_boost : nullptr, r.transform = transform;
-            r.bonus = d_bonus + (shared ? 0 : (int64_t)done * bonus_stride), r.q_stride = shared ? 0 : bonus_stride;
-            r.bonus_rows = bonus_rows;
-            r.q_filter = q_filter ? eng->d_qfilter : nullptr, r.q_filter_mask = q_filter_mask ? eng->d_qmask : nullptr;
+            float *d_boost = nullptr, *d_gate = nullptr, *d_s = nullptr;
+            int64_t* d_i = nullptr;
+            auto carve = [&](unsigned char* base) {
+                Carver d{base};
+                d_boost = d.take<float>(RASS_MAX_QBATCH * sizeof(float));
+                if (scored) d_gate = d.take<float>(RASS_MAX_QBATCH * sizeof(float));
+                d_s = d.take<float>((size_t)RASS_MAX_QBATCH * k * sizeof(float));
+                d_i = d.take<int64_t>((size_t)RASS_MAX_QBATCH * k * sizeof(int64_t));
+                return d.off;
+            };
+            if (int rc = grow_block(&eng->d_allow_io, &eng->allow_io_bytes, carve(nullptr), st)) return rc;
+            carve(eng->d_allow_io);
+            // (pageable sources: a copy has read the caller's array when it returns)
+            if (c.boost) HIP_TRY(hipMemcpyAsync(d_boost, c.boost + done, (size_t)b * sizeof(float), hipMemcpyHostToDevice, st));
+            if (c.min_score) HIP_TRY(hipMemcpyAsync(d_gate, c.min_score + done, (size_t)b * sizeof(float), hipMemcpyHostToDevice, st));
+            BoostRequest r = group_of(c, done, idx->dim, n_cols, col_stride);
+            r.queries = eng->d_qraw, r.nq = b, r.boost = c.boost ? d_boost : nullptr, r.min_score = c.min_score ? d_gate : nullptr;
+            r.q_filter = c.q_filter ? eng->d_qfilter : nullptr, r.q_filter_mask = c.q_filter_mask ? eng->d_qmask : nullptr;
             r.out_scores = d_s, r.out_ids = d_i;
             if (int rc = boost_device_group(idx, r)) return rc;
-            HIP_TRY(hipMemcpyAsync(out_scores + (int64_t)done * k, d_s, cells * sizeof(float), hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipMemcpyAsync(out_ids + (int64_t)done * k, d_i, cells * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipMemcpyAsync(c.out_scores + (int64_t)done * k, d_s, cells * sizeof(float), hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipMemcpyAsync(c.out_ids + (int64_t)done * k, d_i, cells * sizeof(int64_t), hipMemcpyDeviceToHost, st));
             return RASS_OK;
         },
         [](HostSlot*, int, int) -> int { return RASS_OK; });   // the answer was copied straight to the caller's arrays
 }
+
+}  // namespace
+
+// The host and the device form of both searches: api_internal.h.
+int boost_search_host(rass_index* idx, const BoostRequest& c, int n_cols, int64_t col_stride, bool scored) {
+    if (int rc = check_boosted(idx, c, n_cols, col_stride, scored)) return rc;
+    for (int q = 0; q < c.nq; ++q) {
+        if (c.boost && !std::isfinite(c.boost[q])) return fail(RASS_ERR_INVALID, "boost[" + std::to_string(q) + "] is not finite");
+        if (c.min_score && std::isnan(c.min_score[q])) return fail(RASS_ERR_INVALID, "min_score[" + std::to_string(q) + "] is NaN");
+    }
+    if (c.nq == 0) return RASS_OK;
+    return one_layout([&] { return idx->layout_epoch.load(std::memory_order_acquire); },
+                      [&] { return search_boosted_once(idx, c, n_cols, col_stride, scored); });
+}
+
+int boost_search_device(rass_index* idx, const BoostRequest& c, int n_cols, int64_t col_stride, bool scored) {
+    if (int rc = check_boosted(idx, c, n_cols, col_stride, scored)) return rc;
+    if (c.nq == 0) return RASS_OK;
+    rass_engine* eng = idx->eng;
+    std::lock_guard<std::mutex> lk(eng->mu);
+    int rc = set_device(eng);
+    if (rc != RASS_OK) return rc;
+    for (int done = 0; done < c.nq; done += RASS_MAX_QBATCH) {
+        rc = boost_device_group(idx, group_of(c, done, idx->dim, n_cols, col_stride));
+        if (rc != RASS_OK) return rc;
+    }
+    return RASS_OK;
+}
+
+namespace {
 
 // What the column builders check of their target: the block [n_bonus][stride] must hold a value for every row of the index.
 int check_bonus_target(const rass_index* idx, const float* d_bonus, int n_bonus, int64_t stride) {
@@ -160,45 +210,20 @@ extern "C" {
 int rass_index_search_boosted(rass_index_t* idx, const float* queries, int nq, int k, const float* boost, int transform,
                               const float* d_bonus, int n_bonus, int64_t bonus_rows, int64_t bonus_stride, const int32_t* q_filter,
                               const int32_t* q_filter_mask, float* out_scores, int64_t* out_ids) {
-    if (!idx || !out_scores || !out_ids) return fail(RASS_ERR_INVALID, "NULL argument");
-    if (nq > 0 && !queries) return fail(RASS_ERR_INVALID, "bad queries / nq");
-    if (int rc = check_boosted(idx, nq, k, transform, d_bonus, n_bonus, bonus_rows, bonus_stride, q_filter, q_filter_mask)) return rc;
-    if (boost)
-        for (int q = 0; q < nq; ++q)
-            if (!std::isfinite(boost[q])) return fail(RASS_ERR_INVALID, "boost[" + std::to_string(q) + "] is not finite");
-    if (nq == 0) return RASS_OK;
-    return one_layout([&] { return idx->layout_epoch.load(std::memory_order_acquire); }, [&] {
-        return search_boosted_once(idx, queries, nq, k, boost, transform, d_bonus, n_bonus, bonus_rows, bonus_stride, q_filter,
-                                   q_filter_mask, out_scores, out_ids);
-    });
+    BoostRequest c;
+    c.queries = queries, c.nq = nq, c.k = k, c.boost = boost, c.transform = transform, c.bonus = d_bonus, c.bonus_rows = bonus_rows;
+    c.q_filter = q_filter, c.q_filter_mask = q_filter_mask, c.out_scores = out_scores, c.out_ids = out_ids;
+    return boost_search_host(idx, c, n_bonus, bonus_stride, /*scored=*/false);
 }
 
 int rass_index_search_boosted_device(rass_index_t* idx, const float* d_queries, int nq, int k, const float* d_boost, int transform,
                                      const float* d_bonus, int n_bonus, int64_t bonus_rows, int64_t bonus_stride,
                                      const int32_t* d_q_filter, const int32_t* d_q_filter_mask, int64_t id_base, float* d_out_scores,
                                      int64_t* d_out_ids) {
-    if (!idx || !d_out_scores || !d_out_ids) return fail(RASS_ERR_INVALID, "NULL argument");
-    if (nq > 0 && !d_queries) return fail(RASS_ERR_INVALID, "bad queries / nq");
-    if (int rc = check_boosted(idx, nq, k, transform, d_bonus, n_bonus, bonus_rows, bonus_stride, d_q_filter, d_q_filter_mask)) return rc;
-    if (nq == 0) return RASS_OK;
-    rass_engine* eng = idx->eng;
-    std::lock_guard<std::mutex> lk(eng->mu);
-    int rc = set_device(eng);
-    if (rc != RASS_OK) return rc;
-    const bool shared = n_bonus == 1;
-    for (int done = 0; done < nq; done += RASS_MAX_QBATCH) {
-        BoostRequest r;
-        r.queries = d_queries + (int64_t)done * idx->dim, r.nq = std::min(RASS_MAX_QBATCH, nq - done), r.k = k;
-        r.boost = d_boost ? d_boost + done : nullptr, r.transform = transform;
-        r.bonus = d_bonus + (shared ? 0 : (int64_t)done * bonus_stride), r.q_stride = shared ? 0 : bonus_stride;
-        r.bonus_rows = bonus_rows;
-        r.q_filter = d_q_filter ? d_q_filter + done : nullptr, r.q_filter_mask = d_q_filter_mask ? d_q_filter_mask + done : nullptr;
-        r.id_base = id_base;
-        r.out_scores = d_out_scores + (int64_t)done * k, r.out_ids = d_out_ids + (int64_t)done * k;
-        rc = boost_device_group(idx, r);
-        if (rc != RASS_OK) return rc;
-    }
-    return RASS_OK;
+    BoostRequest c;
+    c.queries = d_queries, c.nq = nq, c.k = k, c.boost = d_boost, c.transform = transform, c.bonus = d_bonus, c.bonus_rows = bonus_rows;
+    c.q_filter = d_q_filter, c.q_filter_mask = d_q_filter_mask, c.id_base = id_base, c.out_scores = d_out_scores, c.out_ids = d_out_ids;
+    return boost_search_device(idx, c, n_bonus, bonus_stride, /*scored=*/false);
 }
 
 int rass_index_bonus_scatter(rass_index_t* idx, const int32_t* q_of, const int64_t* rows, const float* values, int64_t n, float* d_bonus,
@@ -278,23 +303,8 @@ int rass_index_bonus_from_attr_clauses(rass_index_t* idx, const int32_t* clauses
     }
     std::stable_sort(sorted.begin(), sorted.end(), [](const Clause& x, const Clause& y) { return x.q < y.q; });
     // one upload for all launch groups: [n_bonus + groups] offsets (every group's own, rebased, nq_g + 1 of them), the clauses, the weights
-    const int groups = (n_bonus + RASS_MAX_QBATCH - 1) / RASS_MAX_QBATCH;
-    std::vector<int32_t> q_off;
-    std::vector<size_t> group_at((size_t)groups + 1, 0), group_off((size_t)groups, 0);
-    {
-        size_t at = 0;
-        for (int g = 0; g < groups; ++g) {
-            group_at[(size_t)g] = at;
-            group_off[(size_t)g] = q_off.size();
-            const int q0 = g * RASS_MAX_QBATCH, q1 = std::min(n_bonus, q0 + RASS_MAX_QBATCH);
-            q_off.push_back(0);
-            for (int q = q0; q < q1; ++q) {
-                while (at < sorted.size() && sorted[at].q == q) ++at;
-                q_off.push_back((int32_t)(at - group_at[(size_t)g]));
-            }
-        }
-        group_at[(size_t)groups] = at;
-    }
+    const GroupOffsets off = group_offsets(n_bonus, sorted.size(), [&](size_t i) { return sorted[i].q; });
+    const int groups = (int)off.group_off.size();
     std::vector<int32_t> packed((size_t)n_clauses * 4);
     std::vector<float> w((size_t)n_clauses);
     for (size_t i = 0; i < sorted.size(); ++i) {
@@ -312,24 +322,24 @@ int rass_index_bonus_from_attr_clauses(rass_index_t* idx, const int32_t* clauses
     Carver c{nullptr};
     c.take<int32_t>(packed.size() * sizeof(int32_t) + 16);
     c.take<float>(w.size() * sizeof(float) + 4);
-    c.take<int32_t>(q_off.size() * sizeof(int32_t));
+    c.take<int32_t>(off.q_off.size() * sizeof(int32_t));
     if ((rc = grow_block(&eng->d_allow_io, &eng->allow_io_bytes, c.off, st)) != RASS_OK) return rc;
     Carver d{eng->d_allow_io};
     int4* d_clauses = reinterpret_cast<int4*>(d.take<int32_t>(packed.size() * sizeof(int32_t) + 16));
     float* d_w = d.take<float>(w.size() * sizeof(float) + 4);
-    int32_t* d_off = d.take<int32_t>(q_off.size() * sizeof(int32_t));
+    int32_t* d_off = d.take<int32_t>(off.q_off.size() * sizeof(int32_t));
     if (n_clauses > 0) {
         HIP_TRY(hipMemcpyAsync(d_clauses, packed.data(), packed.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
         HIP_TRY(hipMemcpyAsync(d_w, w.data(), w.size() * sizeof(float), hipMemcpyHostToDevice, st));
     }
-    HIP_TRY(hipMemcpyAsync(d_off, q_off.data(), q_off.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d_off, off.q_off.data(), off.q_off.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
     rc = RASS_OK;
     for (int g = 0; g < groups && rc == RASS_OK; ++g) {
         rass::BonusClauseArgs a;
         for (int col = 0; col < RASS_MAX_ATTRS; ++col) a.col[col] = idx->d_attr[col];
-        a.clauses = d_clauses + group_at[(size_t)g];
-        a.weights = d_w + group_at[(size_t)g];
-        a.q_off = d_off + group_off[(size_t)g];
+        a.clauses = d_clauses + off.group_at[(size_t)g];
+        a.weights = d_w + off.group_at[(size_t)g];
+        a.q_off = d_off + off.group_off[(size_t)g];
         a.n_rows = n_rows;
         a.bonus = d_bonus + (int64_t)g * RASS_MAX_QBATCH * stride;
         a.stride = stride;

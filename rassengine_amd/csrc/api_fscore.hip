@@ -1,8 +1,8 @@
 // api_fscore.hip — the C ABI of include/rass_engine.h: the function-score search rass_index_search_scored(_device) (exact
 // top-k of combine(boost * T(cos), a function column), gated by the transformed similarity) and the builder of its columns,
-// rass_index_fn_from_attr.  Host-side C++ only: the kernels are scan_fscore.hip and score_fn.hip; the pass driver, the merge
-// and the store of a pass are the boosted search's (boost_device_group in api_boost.hip).  The objects and the threading
-// rules: api_internal.h.
+// rass_index_fn_from_attr.  Host-side C++ only: the kernels are scan_fscore.hip and score_fn.hip; the search itself —
+// checks, group loops, pass driver, merge and store — is the boosted search's (boost_search_host / boost_search_device in
+// api_boost.hip).  The objects and the threading rules: api_internal.h.
 
 #include <cmath>
 
@@ -11,65 +11,6 @@
 namespace rass {
 namespace host {
 namespace {
-
-// The argument checks the entry points share (everything that does not need the row count: fn_rows == the index's rows is
-// checked by boost_device_group under the engine's lock, before a group's first launch).
-int check_scored(const rass_index* idx, int nq, int k, int transform, int combine, const float* d_fn, int n_fn, int64_t fn_rows,
-                 int64_t fn_stride, const int32_t* q_filter, const int32_t* q_filter_mask) {
-    if (nq < 0 || nq > RASS_MAX_DEVICE_BATCH) return fail(RASS_ERR_INVALID, "nq must be in [0, RASS_MAX_DEVICE_BATCH]");
-    if (k < 1 || k > RASS_MAX_K_MULTIPASS) return fail(RASS_ERR_INVALID, "k must be in [1, RASS_MAX_K_MULTIPASS]");
-    if (transform != RASS_BOOST_RAW && transform != RASS_BOOST_OPENSEARCH)
-        return fail(RASS_ERR_INVALID, "transform must be RASS_BOOST_RAW or RASS_BOOST_OPENSEARCH");
-    if (combine < RASS_COMBINE_SUM || combine > RASS_COMBINE_REPLACE) return fail(RASS_ERR_INVALID, "combine must be one of RASS_COMBINE_*");
-    if (nq > 0 && !d_fn) return fail(RASS_ERR_INVALID, "NULL argument");
-    if (nq > 0 && n_fn != 1 && n_fn != nq) return fail(RASS_ERR_INVALID, "n_fn must be 1 (shared) or nq (one column per query)");
-    if (fn_rows < 0 || fn_stride < fn_rows) return fail(RASS_ERR_INVALID, "fn_rows must be in [0, fn_stride]");
-    if (q_filter_mask && !q_filter) return fail(RASS_ERR_INVALID, "q_filter_mask without q_filter");
-    if (idx->dtype != RASS_F32) return fail(RASS_ERR_UNSUPPORTED, "function-score search needs an fp32 index");
-    if (idx->stride > kNarrowStride) return fail(RASS_ERR_UNSUPPORTED, "function-score search needs dim <= 1024 (no wide-row form)");
-    return RASS_OK;
-}
-
-// One attempt of the host search (host_groups): the group's queries and filters through a pinned slot as
-// rass_index_search_ex, its boosts, its gates and its [b][k] answer through the engine's own staging block (eng->d_allow_io).
-int search_scored_once(rass_index_t* idx, const float* queries, int nq, int k, const float* boost, int transform, int combine,
-                       const float* min_score, const float* d_fn, int n_fn, int64_t fn_rows, int64_t fn_stride, const int32_t* q_filter,
-                       const int32_t* q_filter_mask, float* out_scores, int64_t* out_ids) {
-    rass_engine* eng = idx->eng;
-    const bool shared = n_fn == 1;
-    return host_groups(
-        idx, queries, nq, q_filter, q_filter_mask, /*io_bytes=*/0, no_fill,
-        [&](HostSlot*, int done, int b) -> int {
-            hipStream_t st = eng->stream;
-            const size_t cells = (size_t)b * k;
-            Carver c{nullptr};
-            c.take<float>(RASS_MAX_QBATCH * sizeof(float));
-            c.take<float>(RASS_MAX_QBATCH * sizeof(float));
-            c.take<float>((size_t)RASS_MAX_QBATCH * k * sizeof(float));
-            c.take<int64_t>((size_t)RASS_MAX_QBATCH * k * sizeof(int64_t));
-            if (int rc = grow_block(&eng->d_allow_io, &eng->allow_io_bytes, c.off, st)) return rc;
-            Carver d{eng->d_allow_io};
-            float* d_boost = d.take<float>(RASS_MAX_QBATCH * sizeof(float));
-            float* d_gate = d.take<float>(RASS_MAX_QBATCH * sizeof(float));
-            float* d_s = d.take<float>((size_t)RASS_MAX_QBATCH * k * sizeof(float));
-            int64_t* d_i = d.take<int64_t>((size_t)RASS_MAX_QBATCH * k * sizeof(int64_t));
-            // (pageable sources: a copy has read the caller's array when it returns)
-            if (boost) HIP_TRY(hipMemcpyAsync(d_boost, boost + done, (size_t)b * sizeof(float), hipMemcpyHostToDevice, st));
-            if (min_score) HIP_TRY(hipMemcpyAsync(d_gate, min_score + done, (size_t)b * sizeof(float), hipMemcpyHostToDevice, st));
-            BoostRequest r;
-            r.queries = eng->d_qraw, r.nq = b, r.k = k, r.boost = boost ? d_boost : nullptr, r.transform = transform;
-            r.combine = combine, r.min_score = min_score ? d_gate : nullptr;
-            r.bonus = d_fn + (shared ? 0 : (int64_t)done * fn_stride), r.q_stride = shared ? 0 : fn_stride;
-            r.bonus_rows = fn_rows;
-            r.q_filter = q_filter ? eng->d_qfilter : nullptr, r.q_filter_mask = q_filter_mask ? eng->d_qmask : nullptr;
-            r.out_scores = d_s, r.out_ids = d_i;
-            if (int rc = boost_device_group(idx, r)) return rc;
-            HIP_TRY(hipMemcpyAsync(out_scores + (int64_t)done * k, d_s, cells * sizeof(float), hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipMemcpyAsync(out_ids + (int64_t)done * k, d_i, cells * sizeof(int64_t), hipMemcpyDeviceToHost, st));
-            return RASS_OK;
-        },
-        [](HostSlot*, int, int) -> int { return RASS_OK; });   // the answer was copied straight to the caller's arrays
-}
 
 // One record, checked and turned into the device's form (the constants derived in double).
 int convert_fn(const rass_score_fn_t& f, int64_t i, int n_fn, int n_filters, rass::ScoreFnRec* out) {
@@ -114,47 +55,22 @@ extern "C" {
 int rass_index_search_scored(rass_index_t* idx, const float* queries, int nq, int k, const float* boost, int transform, int combine,
                              const float* min_score, const float* d_fn, int n_fn, int64_t fn_rows, int64_t fn_stride,
                              const int32_t* q_filter, const int32_t* q_filter_mask, float* out_scores, int64_t* out_ids) {
-    if (!idx || !out_scores || !out_ids) return fail(RASS_ERR_INVALID, "NULL argument");
-    if (nq > 0 && !queries) return fail(RASS_ERR_INVALID, "bad queries / nq");
-    if (int rc = check_scored(idx, nq, k, transform, combine, d_fn, n_fn, fn_rows, fn_stride, q_filter, q_filter_mask)) return rc;
-    for (int q = 0; q < nq; ++q) {
-        if (boost && !std::isfinite(boost[q])) return fail(RASS_ERR_INVALID, "boost[" + std::to_string(q) + "] is not finite");
-        if (min_score && std::isnan(min_score[q])) return fail(RASS_ERR_INVALID, "min_score[" + std::to_string(q) + "] is NaN");
-    }
-    if (nq == 0) return RASS_OK;
-    return one_layout([&] { return idx->layout_epoch.load(std::memory_order_acquire); }, [&] {
-        return search_scored_once(idx, queries, nq, k, boost, transform, combine, min_score, d_fn, n_fn, fn_rows, fn_stride, q_filter,
-                                  q_filter_mask, out_scores, out_ids);
-    });
+    BoostRequest c;
+    c.queries = queries, c.nq = nq, c.k = k, c.boost = boost, c.transform = transform, c.combine = combine, c.min_score = min_score;
+    c.bonus = d_fn, c.bonus_rows = fn_rows, c.q_filter = q_filter, c.q_filter_mask = q_filter_mask;
+    c.out_scores = out_scores, c.out_ids = out_ids;
+    return boost_search_host(idx, c, n_fn, fn_stride, /*scored=*/true);
 }
 
 int rass_index_search_scored_device(rass_index_t* idx, const float* d_queries, int nq, int k, const float* d_boost, int transform,
                                     int combine, const float* d_min_score, const float* d_fn, int n_fn, int64_t fn_rows,
                                     int64_t fn_stride, const int32_t* d_q_filter, const int32_t* d_q_filter_mask, int64_t id_base,
                                     float* d_out_scores, int64_t* d_out_ids) {
-    if (!idx || !d_out_scores || !d_out_ids) return fail(RASS_ERR_INVALID, "NULL argument");
-    if (nq > 0 && !d_queries) return fail(RASS_ERR_INVALID, "bad queries / nq");
-    if (int rc = check_scored(idx, nq, k, transform, combine, d_fn, n_fn, fn_rows, fn_stride, d_q_filter, d_q_filter_mask)) return rc;
-    if (nq == 0) return RASS_OK;
-    rass_engine* eng = idx->eng;
-    std::lock_guard<std::mutex> lk(eng->mu);
-    int rc = set_device(eng);
-    if (rc != RASS_OK) return rc;
-    const bool shared = n_fn == 1;
-    for (int done = 0; done < nq; done += RASS_MAX_QBATCH) {
-        BoostRequest r;
-        r.queries = d_queries + (int64_t)done * idx->dim, r.nq = std::min(RASS_MAX_QBATCH, nq - done), r.k = k;
-        r.boost = d_boost ? d_boost + done : nullptr, r.transform = transform;
-        r.combine = combine, r.min_score = d_min_score ? d_min_score + done : nullptr;
-        r.bonus = d_fn + (shared ? 0 : (int64_t)done * fn_stride), r.q_stride = shared ? 0 : fn_stride;
-        r.bonus_rows = fn_rows;
-        r.q_filter = d_q_filter ? d_q_filter + done : nullptr, r.q_filter_mask = d_q_filter_mask ? d_q_filter_mask + done : nullptr;
-        r.id_base = id_base;
-        r.out_scores = d_out_scores + (int64_t)done * k, r.out_ids = d_out_ids + (int64_t)done * k;
-        rc = boost_device_group(idx, r);
-        if (rc != RASS_OK) return rc;
-    }
-    return RASS_OK;
+    BoostRequest c;
+    c.queries = d_queries, c.nq = nq, c.k = k, c.boost = d_boost, c.transform = transform, c.combine = combine, c.min_score = d_min_score;
+    c.bonus = d_fn, c.bonus_rows = fn_rows, c.q_filter = d_q_filter, c.q_filter_mask = d_q_filter_mask, c.id_base = id_base;
+    c.out_scores = d_out_scores, c.out_ids = d_out_ids;
+    return boost_search_device(idx, c, n_fn, fn_stride, /*scored=*/true);
 }
 
 int rass_index_fn_from_attr(rass_index_t* idx, const rass_score_fn_t* fns, int64_t n_fns, int n_fn, int score_mode, double max_boost,
@@ -180,23 +96,8 @@ int rass_index_fn_from_attr(rass_index_t* idx, const rass_score_fn_t* fns, int64
     }
     std::stable_sort(sorted.begin(), sorted.end(), [](const auto& x, const auto& y) { return x.first < y.first; });
     // one upload for all launch groups: every group's own offsets (rebased, nq_g + 1 of them), then the records
-    const int groups = (n_fn + RASS_MAX_QBATCH - 1) / RASS_MAX_QBATCH;
-    std::vector<int32_t> q_off;
-    std::vector<size_t> group_at((size_t)groups + 1, 0), group_off((size_t)groups, 0);
-    {
-        size_t at = 0;
-        for (int g = 0; g < groups; ++g) {
-            group_at[(size_t)g] = at;
-            group_off[(size_t)g] = q_off.size();
-            const int q0 = g * RASS_MAX_QBATCH, q1 = std::min(n_fn, q0 + RASS_MAX_QBATCH);
-            q_off.push_back(0);
-            for (int q = q0; q < q1; ++q) {
-                while (at < sorted.size() && sorted[at].first == q) ++at;
-                q_off.push_back((int32_t)(at - group_at[(size_t)g]));
-            }
-        }
-        group_at[(size_t)groups] = at;
-    }
+    const GroupOffsets off = group_offsets(n_fn, sorted.size(), [&](size_t i) { return sorted[i].first; });
+    const int groups = (int)off.group_off.size();
     std::vector<rass::ScoreFnRec> recs((size_t)n_fns);
     for (size_t i = 0; i < sorted.size(); ++i) recs[i] = sorted[i].second;
 
@@ -212,19 +113,19 @@ int rass_index_fn_from_attr(rass_index_t* idx, const rass_score_fn_t* fns, int64
     if (filtered && (rc = check_words(n_rows, words)) != RASS_OK) return rc;
     Carver c{nullptr};
     c.take<rass::ScoreFnRec>((recs.size() + 1) * sizeof(rass::ScoreFnRec));
-    c.take<int32_t>(q_off.size() * sizeof(int32_t));
+    c.take<int32_t>(off.q_off.size() * sizeof(int32_t));
     if ((rc = grow_block(&eng->d_allow_io, &eng->allow_io_bytes, c.off, st)) != RASS_OK) return rc;
     Carver d{eng->d_allow_io};
     rass::ScoreFnRec* d_recs = d.take<rass::ScoreFnRec>((recs.size() + 1) * sizeof(rass::ScoreFnRec));
-    int32_t* d_off = d.take<int32_t>(q_off.size() * sizeof(int32_t));
+    int32_t* d_off = d.take<int32_t>(off.q_off.size() * sizeof(int32_t));
     if (n_fns > 0) HIP_TRY(hipMemcpyAsync(d_recs, recs.data(), recs.size() * sizeof(rass::ScoreFnRec), hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(d_off, q_off.data(), q_off.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d_off, off.q_off.data(), off.q_off.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
     rc = RASS_OK;
     for (int g = 0; g < groups && rc == RASS_OK; ++g) {
         rass::ScoreFnArgs a;
         for (int col = 0; col < RASS_MAX_ATTRS; ++col) a.col[col] = idx->d_attr[col];
-        a.recs = d_recs + group_at[(size_t)g];
-        a.q_off = d_off + group_off[(size_t)g];
+        a.recs = d_recs + off.group_at[(size_t)g];
+        a.q_off = d_off + off.group_off[(size_t)g];
         a.filters = d_filters;
         a.words = words;
         a.n_rows = n_rows;

@@ -13,9 +13,11 @@
 //                    list, the probe and the batch on one fine scan, the delta, the host API (host_groups)
 //   api_ivf_allow.hip  the IVF probe within a row bitmap (probe plan -> slab-order bitmap words -> the allow-list scan), the probed lists
 //   api_allow.hip    the allow-list search (top-k within a per-query row bitmap), its bitmap builders, its plan, a bitmap's popcount
-//   api_boost.hip    the boosted search (top-k of boost * T(cos) + a per-row bonus column) and the builders of its columns
-//   api_fscore.hip   the function-score search (top-k of combine(boost * T(cos), a function column), gated by similarity) and
-//                    the builder of its columns; one pass driver with the boosted search (boost_device_group)
+//   api_boost.hip    the boosted search (top-k of boost * T(cos) + a per-row bonus column) and the builders of its columns;
+//                    its checks, group loops and pass driver (boost_search_host / _device, boost_device_group) also run the
+//                    function-score search
+//   api_fscore.hip   the function-score search (top-k of combine(boost * T(cos), a function column), gated by similarity): its
+//                    entry points on api_boost.hip's search path, and the builder of its columns
 //   api_grouptop.hip the grouped search with inner hits (the group_size best rows of each top group, the capped list) over a
 //                    key column, on a scan family of its own (scan_grouptop.hip) and the grouped search's table block
 //   api_keys.hip     the key columns built from the attribute columns (what the grouped search and the aggregation group by)
@@ -143,6 +145,34 @@ struct Carver {
         return p;
     }
 };
+
+// ---- per-launch-group offsets of a list of `n` records sorted by the query (of `n_queries`) that query_of(i) names: what a
+// column builder uploads once for all its launch groups of <= RASS_MAX_QBATCH queries.  Group g's records start at
+// group_at[g] (group_at[groups] = n); its nq_g + 1 offsets, rebased to that start, are q_off[group_off[g] ..]: query q of the
+// group owns records [q_off[.. + q], q_off[.. + q + 1]).
+struct GroupOffsets {
+    std::vector<int32_t> q_off;
+    std::vector<size_t> group_at, group_off;
+};
+template <class QueryOf>
+GroupOffsets group_offsets(int n_queries, size_t n, QueryOf query_of) {
+    const int groups = (n_queries + RASS_MAX_QBATCH - 1) / RASS_MAX_QBATCH;
+    GroupOffsets o;
+    o.group_at.assign((size_t)groups + 1, 0), o.group_off.assign((size_t)groups, 0);
+    size_t at = 0;
+    for (int g = 0; g < groups; ++g) {
+        o.group_at[(size_t)g] = at;
+        o.group_off[(size_t)g] = o.q_off.size();
+        const int q0 = g * RASS_MAX_QBATCH, q1 = std::min(n_queries, q0 + RASS_MAX_QBATCH);
+        o.q_off.push_back(0);
+        for (int q = q0; q < q1; ++q) {
+            while (at < n && query_of(at) == q) ++at;
+            o.q_off.push_back((int32_t)(at - o.group_at[(size_t)g]));
+        }
+    }
+    o.group_at[(size_t)groups] = at;
+    return o;
+}
 
 // The engine scratch of one launch group (and the caller's workspace of rass_scan_topk_f32: rass_scan_workspace_bytes).
 struct ScratchView {
@@ -691,6 +721,13 @@ struct BoostRequest {
     const float* min_score = nullptr;   // [nq] or nullptr (function-score scan only)
 };
 int boost_device_group(rass_index* idx, const BoostRequest& r);
+// The whole of rass_index_search_boosted / _scored (host pointers; checks boost and min_score, retries on a layout change) and
+// of their _device forms (takes eng->mu): `c` describes the CALL — nq <= RASS_MAX_DEVICE_BATCH queries, c.bonus the block of
+// n_cols columns (1: shared, or nq) of col_stride floats, q_stride not read — and is cut into launch groups for
+// boost_device_group.  scored: the function-score search (c.combine is checked and the messages name fn_*), else the boosted
+// one (c.combine stays < 0).
+int boost_search_host(rass_index* idx, const BoostRequest& c, int n_cols, int64_t col_stride, bool scored);
+int boost_search_device(rass_index* idx, const BoostRequest& c, int n_cols, int64_t col_stride, bool scored);
 // The first two stages of a probe of one launch group (api_ivf.hip; the caller holds eng->mu): the top-nprobe centroids per
 // query — the flat fused scan for nprobe <= RASS_MAX_K (the lists, best first, stay at v->d_probe_ids [nq][min(nprobe, nlist)]),
 // the threshold path above — and the plan: the union of the probed lists as the work list v->d_work_* / d_n_work with per-tile

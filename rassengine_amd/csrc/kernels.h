@@ -148,7 +148,8 @@ hipError_t launch_scan_topk_f32_pair(const ScanArgs& a, int grid, hipStream_t st
 constexpr int kStepMaxPairs = 16;
 hipError_t launch_scan_topk_f32_step(const ScanArgs& a, int grid, hipStream_t stream);
 
-// ---- boosted scan (scan_boost.hip): exact top-k of fused = boost[q] * T(cos) + bonus[q][row] for one launch group.
+// ---- boosted scan (scan_boost.hip; the flat pair loop it shares with the function-score scan: scan_flat.h):
+// exact top-k of fused = boost[q] * T(cos) + bonus[q][row] for one launch group.
 // `scan` carries what a flat EXT launch of launch_scan_topk_f32 would (corpus, row_tag, q_padded [32][row_stride] zero-padded,
 // q_filter / q_filter_mask, q_after_score / q_after_id — the continuation bound, on the FUSED score and the slab row —,
 // part_* [grid][nq][k], row_stride 128 * {1..8}, n_rows >= 1, nq <= 32, k <= 32, id_base 0: the lists hold slab rows); every
@@ -215,8 +216,8 @@ hipError_t launch_bonus_clauses(const BonusClauseArgs& a, hipStream_t stream);
 hipError_t launch_bonus_mask(float* bonus, int n_bonus, int64_t stride, int64_t n_rows, const uint32_t* allow, int64_t allow_q_stride,
                              hipStream_t stream);
 
-// ---- function-score scan (scan_fscore.hip): exact top-k of fused = combine(boost[q] * T(cos), fn[q][row]) for one launch
-// group.  `scan`, `boost` and `transform` as in BoostArgs.  fn: query q's function column at fn + q * fn_q_stride (0: one
+// ---- function-score scan (scan_fscore.hip, on scan_flat.h's loop): exact top-k of fused = combine(boost[q] * T(cos),
+// fn[q][row]) for one launch group.  `scan`, `boost` and `transform` as in BoostArgs.  fn: query q's function column at fn + q * fn_q_stride (0: one
 // column shared by every query), fn_rows values each — fn_rows must equal scan.n_rows (no "rows past the column" here);
 // fn_bytes = 4 * ((nq - 1) * fn_q_stride + fn_rows) <= kBoostMaxBonusBytes.  mode: RASS_COMBINE_* (0 sum a + f, 1 multiply
 // a * f, 2 avg (a + f) * 0.5f, 3 max f > a ? f : a, 4 min f < a ? f : a, 5 replace f), every operation rounded on its own.

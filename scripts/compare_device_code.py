@@ -1,14 +1,15 @@
 #!/usr/bin/env python3
 """Are the kernels of two source trees the same device code?  (CPU: cross-compiles, runs nothing.)
 
-    python scripts/compare_device_code.py OLD/rassengine_amd/csrc NEW/rassengine_amd/csrc [UNIT ...]
+    python scripts/compare_device_code.py [--details] OLD/rassengine_amd/csrc NEW/rassengine_amd/csrc [UNIT ...]
 
 Compiles the named units of each tree (scan_topk group_topk ...: UNIT.hip; by default every encoder GEMM unit,
 encoder_gemm.hip and gemm_*.hip, whichever exist) with the Makefile's flags for that unit, its own "FLAGS +=" line
 included, plus --cuda-device-only -S and compares, kernel by kernel: the instruction text of the function (local labels
 .LBB* / .Ltmp* renumbered in order of appearance, comments and debug directives dropped) and the .amdhsa_ resource lines
 of its kernel descriptor (VGPR / AGPR / SGPR counts, scratch, LDS).  One line per kernel; exit status 1 if a kernel
-differs or the two sets of kernel symbols differ."""
+differs or the two sets of kernel symbols differ.  --details adds, under every kernel that differs, what moved: the
+descriptor values old -> new and the instruction classes (a mnemonic's first two words) whose counts differ or agree."""
 import glob
 import os
 import re
@@ -94,10 +95,39 @@ def tree(csrc, tmp, tag, names):
     return table
 
 
+def classes(text):
+    """instruction class -> count; the class of a mnemonic is its first two words (v_mfma, buffer_load, ds_read, s_waitcnt)."""
+    out = {}
+    for ln in text.splitlines():
+        word = ln.split()[0]
+        if not word.endswith(":") and not word.startswith((".", ";")):
+            c = "_".join(word.split("_")[:2])
+            out[c] = out.get(c, 0) + 1
+    return out
+
+
+def explain(old, new):
+    """The lines --details prints under a kernel that differs: descriptor values old -> new (the registers, scratch and LDS
+    always, the rest where they differ) and the instruction classes whose counts differ."""
+    do, dn = (dict(ln.split(None, 1) for ln in d) for d in (old[1], new[1]))
+    always = (".amdhsa_next_free_vgpr", ".amdhsa_accum_offset", ".amdhsa_next_free_sgpr", ".amdhsa_private_segment_fixed_size",
+              ".amdhsa_group_segment_fixed_size")
+    desc = ["%s %s -> %s" % (k[len(".amdhsa_"):], do.get(k, "-"), dn.get(k, "-"))
+            for k in sorted(set(do) | set(dn), key=lambda k: (k not in always, k)) if k in always or do.get(k) != dn.get(k)]
+    co, cn = classes(old[0]), classes(new[0])
+    diff = ["%s %d -> %d" % (c, co.get(c, 0), cn.get(c, 0)) for c in sorted(set(co) | set(cn)) if co.get(c, 0) != cn.get(c, 0)]
+    same = sorted(c for c in co if co[c] == cn.get(c))
+    return ["    " + "; ".join(desc),
+            "    instructions %d -> %d; classes that differ: %s" % (sum(co.values()), sum(cn.values()), "; ".join(diff) or "none"),
+            "    classes with equal counts: " + " ".join("%s=%d" % (c, co[c]) for c in same)]
+
+
 def main():
-    old_csrc, new_csrc = os.path.abspath(sys.argv[1]), os.path.abspath(sys.argv[2])
+    argv = [a for a in sys.argv[1:] if a != "--details"]
+    details = len(argv) != len(sys.argv) - 1
+    old_csrc, new_csrc = os.path.abspath(argv[0]), os.path.abspath(argv[1])
     with tempfile.TemporaryDirectory() as tmp:
-        old, new = tree(old_csrc, tmp, "old", sys.argv[3:]), tree(new_csrc, tmp, "new", sys.argv[3:])
+        old, new = tree(old_csrc, tmp, "old", argv[2:]), tree(new_csrc, tmp, "new", argv[2:])
     bad = 0
     for k in sorted(set(old) | set(new)):
         if k not in old or k not in new:
@@ -108,6 +138,8 @@ def main():
         bad += res != "identical"
         n = len((new.get(k) or old[k])[0].splitlines())
         print("%-10s %6d lines  %-18s %s" % (res, n, (new.get(k) or old[k])[2], k))
+        if details and res.startswith("DIFFERS"):
+            print("\n".join(explain(old[k], new[k])))
     print("%d kernels, %d not identical" % (len(set(old) | set(new)), bad))
     return 1 if bad else 0
 

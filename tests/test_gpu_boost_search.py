@@ -525,3 +525,28 @@ def _only_should(st, should):
         hit = np.array([d is not None and AR.doc_matches(leaf, d, KINDS, NOW) for d in st.row_doc])
         b = np.where(hit, (b + np.float32(wgt)).astype(np.float32), b)
     return b
+
+
+# ---- 11. the loop's steady state: three iterations per workgroup
+def deep_rows(torch):
+    """5 * CUs + 3 tiles and a tail of 7 rows (41 063 rows on 256 CUs).  The scan launches one workgroup per CU, so every
+    workgroup runs the pair loop three times, some over 5 tiles and some over 6 (odd and even counts): a column value
+    requested in one iteration is parked and ranked in the next, the LDS image pair flips twice, and the run-ahead refill goes
+    past the last tile.  At the shapes above (<= 129 tiles) every workgroup runs the loop body once."""
+    return (5 * torch.cuda.get_device_properties(0).multi_processor_count + 3) * 32 + 7
+
+
+@pytest.mark.parametrize("nq", [16, 17])
+@pytest.mark.parametrize("dim", [128, 1024])
+def test_deep_loop_parks_each_pair_for_its_own_tiles(gpu, worlds, dim, nq):
+    n = deep_rows(gpu)
+    w = worlds(n, dim)
+    rng = np.random.default_rng(111 + dim)
+    # one column per query, every row its own value: a value parked for the wrong tile, pair or query changes the answer
+    per_query = (rng.permutation(NQ_MAX * n).reshape(NQ_MAX, n) * (0.25 / (NQ_MAX * n))).astype(np.float32)
+    assert all(len(np.unique(per_query[q])) == n for q in range(nq))
+    boost = rng.uniform(0.5, 2.0, size=NQ_MAX).astype(np.float32)
+    for mode in ("raw", "opensearch"):
+        w.check(nq, 10, per_query, boost=boost, mode=mode, what="deep")
+    # the column ends inside the fourth round of tiles: the late tiles read 0
+    w.check(nq, 10, per_query, boost=boost, mode="raw", bonus_rows=(n * 7 // 10) | 1, what="deep, short column")

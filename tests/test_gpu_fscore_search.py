@@ -23,7 +23,8 @@ import pytest
 import attr_ref as AR
 import boost_ref as B
 import fscore_ref as F
-from test_gpu_boost_search import KINDS, KS, NOW, NQ_MAX, NQS, ORACLE_MAX_K, SHAPES, STRIDE_DIMS, World, _corpus, assert_same, filters
+from test_gpu_boost_search import (KINDS, KS, NOW, NQ_MAX, NQS, ORACLE_MAX_K, SHAPES, STRIDE_DIMS, World, _corpus, assert_same, deep_rows,
+                                    filters)
 
 pytestmark = pytest.mark.gpu
 
@@ -530,3 +531,21 @@ def test_shim_scored_and_recent(gpu, oracle, monkeypatch):
         REGISTRY.set_index_factory(None)
         REGISTRY.clear()
         eng.close()
+
+
+# ---- 9. the loop's steady state: three iterations per workgroup (the boosted tests' deep shape)
+@pytest.mark.parametrize("nq", [16, 17])
+@pytest.mark.parametrize("dim", [128, 1024])
+def test_deep_loop_parks_each_pair_for_its_own_tiles(gpu, worlds, dim, nq):
+    n = deep_rows(gpu)
+    w = worlds(n, dim)
+    rng = np.random.default_rng(1111 + dim)
+    # one column per query, every row its own value (replace ranks by it alone; multiply by it times the similarity)
+    per_query = ((rng.permutation(NQ_MAX * n).reshape(NQ_MAX, n) + 1) * (2.0 / (NQ_MAX * n))).astype(np.float32)
+    assert all(len(np.unique(per_query[q])) == n for q in range(nq))
+    boost = random_boosts(rng)
+    gate = np.where(np.arange(NQ_MAX) % 2 == 0, np.float32(0.0), NEG_INF).astype(np.float32)     # every other query gated
+    check(w, nq, 10, per_query, "multiply", boost=boost, transform="opensearch", what="deep multiply")
+    want = check(w, nq, 10, per_query, "replace", boost=boost, transform="raw", gate=gate, what="deep replace, gated")
+    cus = gpu.cuda.get_device_properties(0).multi_processor_count
+    assert (want[1] >= 0).all() and len(np.unique(want[1] // 32 // cus)) > 1      # hits from more than one round of tiles

@@ -184,6 +184,21 @@ def test_full_grid_under_contention(gpu, oracle):
         eng.close()
 
 
+@pytest.mark.parametrize("nq", [16, 17])
+@pytest.mark.parametrize("dim", [128, 1024])
+def test_deep_loop_three_iterations_per_workgroup(gpu, world, dim, nq):
+    """5 * CUs + 3 tiles and a tail of 7 rows (41 063 rows on 256 CUs): the scan launches one workgroup per CU, so every
+    workgroup runs the pair loop three times, some over 5 tiles and some over 6.  A tile's keys requested in one iteration are
+    parked and read in the next, the LDS image pair flips twice, and the run-ahead refill goes past the last tile."""
+    n = (5 * gpu.cuda.get_device_properties(0).multi_processor_count + 3) * 32 + 7
+    eng, idx, case = world((n, dim, nq))
+    rng = np.random.default_rng(n + dim + nq)
+    keys = rng.integers(0, 64, size=n)          # a row's group says nothing about its tile: keys parked for the wrong tile show
+    keys[rng.random(n) < 0.05] = -1
+    check(gpu, idx, case, case.live_tags, keys, 64, 10, 3, what="deep")
+    check(gpu, idx, case, case.live_tags, keys, 64, 10, 3, allow=rng.random((nq, n)) < 0.3, what="deep, per-query bitmap")
+
+
 def test_every_row_its_own_group_and_small_groups(gpu, world):
     eng, idx, case = world(SWEEP[2])
     n = case.n
