@@ -768,6 +768,54 @@ int rass_index_aggregate_keys_device(rass_index_t* idx, const float* d_queries, 
                                      const int32_t* d_q_filter, const int32_t* d_q_filter_mask,
                                      int64_t id_base, int32_t* d_out_groups, int64_t* d_out_counts, float* d_out_scores,
                                      int64_t* d_out_ids, int64_t* d_n_buckets, int64_t* d_total_hits, int32_t* d_status);
+/* STATS SUB-AGGREGATION: rass_index_aggregate_keys(_device) with the count, sum, min and max of an attribute column over each
+ * bucket's hits — OpenSearch's `stats` / `min` / `max` / `sum` / `avg` / `value_count` metrics under a `terms` or `histogram`
+ * aggregation, `"order": {"<metric>": "asc" | "desc"}`, or, with d_keys NULL, on their own.  Still ONE corpus pass per launch
+ * group: the scan keeps, per (query, group), the hit count, the best hit, and the count / sum / min / max of the hits' values
+ * in column value_col; then one select over the query's groups and one gather of the listed buckets.  All of it is integer
+ * arithmetic on int32 values: the answer is a function of the index and the arguments alone.  Arguments, hit test, padding,
+ * totals, ids, status word, filters, bitmap, tombstones, layout epochs and locking as rass_index_aggregate_keys(_device), plus:
+ * d_keys NULL with n_groups == 1: the GLOBAL form — every row is in group 0, n_keys is not read.  NULL with any other
+ *   n_groups: RASS_ERR_INVALID.
+ * value_col in [0, RASS_MAX_ATTRS), else RASS_ERR_INVALID.  A hit whose value is RASS_ATTR_MISSING (every row of a column
+ *   that was never set) counts in out_counts and not in the metrics.
+ * order_by, order_desc (0: ascending, else descending): the bucket order before the `size` first are listed.
+ *   RASS_STATS_BY_COUNT descending is rass_index_aggregate_keys' order, and groups / counts / scores / ids / n_buckets /
+ *   total_hits are then exactly what that call reports.  _BY_VALUE_COUNT, _BY_MIN, _BY_MAX order by that metric.  Only buckets
+ *   with a hit are listed; ties break by group key ascending; a bucket with no present value comes after every bucket that
+ *   has one, in BOTH directions, by group key ascending.  Any other order_by: RASS_ERR_INVALID.  (Ordering by sum or avg has
+ *   no device form: a caller that lists every bucket orders them itself.)
+ * out_value_counts / out_sums (int64) and out_mins / out_maxs (int32), each [nq][size]: per listed bucket the number of hits
+ *   with a value, their exact sum, the smallest and the largest; (0, 0, 0, 0) for a bucket with no present value and past the
+ *   last bucket.  avg = sum / value_count is the caller's division.
+ * The table is nq x n_groups 32-byte slots in the engine-owned block of the grouped search — 1 GiB for 32 queries at the
+ *   n_groups bound — grown on demand; RASS_ERR_OOM leaves the engine as it was.
+ * A bound broken, or a NaN min_score in the host variant: RASS_ERR_INVALID, nothing is launched and the outputs are untouched.
+ * fp32 flat indices with dim <= 1024 only: a bf16 index or a wide-row index answers RASS_ERR_UNSUPPORTED.  The prefilter mode
+ * is ignored: always the exact fp32 scan, and a score is the flat scan's bit for bit.  The host variant takes any nq in launch
+ * groups of RASS_MAX_QBATCH and fails with RASS_ERR_INVALID where a hit's key is >= n_groups; the device variant takes nq <=
+ * RASS_MAX_QBATCH, is stream-ordered, synchronises nothing and reports that condition as *d_status = 1 (0 otherwise). */
+#define RASS_STATS_BY_COUNT 0
+#define RASS_STATS_BY_VALUE_COUNT 1
+#define RASS_STATS_BY_MIN 2
+#define RASS_STATS_BY_MAX 3
+int rass_index_aggregate_stats_keys(rass_index_t* idx, const float* queries, int nq, const float* min_score, int size,
+                                    const int32_t* d_keys, int64_t n_keys, int32_t n_groups,
+                                    int value_col, int order_by, int order_desc,
+                                    const uint32_t* d_allow, int n_bitmaps, int64_t words_per_bitmap,
+                                    const int32_t* q_filter, const int32_t* q_filter_mask,
+                                    int32_t* out_groups, int64_t* out_counts, float* out_scores, int64_t* out_ids,
+                                    int64_t* out_value_counts, int64_t* out_sums, int32_t* out_mins, int32_t* out_maxs,
+                                    int64_t* out_n_buckets, int64_t* out_total_hits);
+int rass_index_aggregate_stats_keys_device(rass_index_t* idx, const float* d_queries, int nq, const float* d_min_score, int size,
+                                           const int32_t* d_keys, int64_t n_keys, int32_t n_groups,
+                                           int value_col, int order_by, int order_desc,
+                                           const uint32_t* d_allow, int n_bitmaps, int64_t words_per_bitmap,
+                                           const int32_t* d_q_filter, const int32_t* d_q_filter_mask,
+                                           int64_t id_base, int32_t* d_out_groups, int64_t* d_out_counts, float* d_out_scores,
+                                           int64_t* d_out_ids, int64_t* d_out_value_counts, int64_t* d_out_sums,
+                                           int32_t* d_out_mins, int32_t* d_out_maxs, int64_t* d_n_buckets,
+                                           int64_t* d_total_hits, int32_t* d_status);
 
 /* GRAM matrices of short row lists: out[l][i][j] = the fp32 dot product of stored rows rows[l][i] and rows[l][j], as they lie
  * in the slab (normalised at add time: their cosine).  The similarity structure of a result set, duplicate detection over an

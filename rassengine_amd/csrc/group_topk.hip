@@ -15,6 +15,10 @@
 // keys are unique too and the select, the gather and the sort are the ones above.  A listed bucket's score and id come from
 // the slot of the group-max table the scan kept next to the counters; the counters' sum is the query's number of hits.
 //
+// group_stats_select_kernel finishes a stats aggregation ordered by a metric (scan_stats.hip; kernels.h launch_group_stats_select):
+// the select again, its sort key made on the fly from a plane of the stats table; group_stats_gather_kernel then decodes the
+// stats planes of the listed buckets.  The select's body is group_select_body.inc, included inside each select kernel.
+//
 // group_hits_finish_kernel runs behind the select of a grouped search with inner hits (scan_grouptop.hip; kernels.h
 // launch_group_hits_finish): the table then has group_size planes, the select has read plane 0, and the finish reads every plane
 // of the slots it chose.
@@ -41,6 +45,14 @@ __device__ __forceinline__ void hist_add(unsigned* hist, bool on, unsigned digit
     if (on && !same) atomicAdd(&hist[digit], 1u);
 }
 
+// What the metric order of a stats aggregation adds to the select (kernels.h launch_group_stats_select): the plane that says
+// whether a slot has a value (non-zero), the plane the metric is read from, and whether the metric field is complemented.
+struct MetricOrder {
+    const unsigned* has;
+    const unsigned* metric;
+    bool flip;
+};
+
 // COUNT = false: the grouped search (counts, out_counts, total_hits unused).  COUNT = true: the terms aggregation.
 template <bool COUNT>
 __global__ __launch_bounds__(kGroupSelThreads) void group_select_kernel(const unsigned long long* __restrict__ table,
@@ -50,151 +62,49 @@ __global__ __launch_bounds__(kGroupSelThreads) void group_select_kernel(const un
                                                                         int32_t* __restrict__ out_groups, int64_t* __restrict__ out_counts,
                                                                         int64_t* __restrict__ total, int64_t* __restrict__ total_hits,
                                                                         const unsigned* __restrict__ status, int32_t* __restrict__ out_status) {
-    __shared__ unsigned long long keys[kGroupMaxK];
-    __shared__ int grp[kGroupMaxK];
-    __shared__ unsigned hist[256];
-    __shared__ int sh_digit, sh_rank, n_sel, n_live;
-    __shared__ unsigned long long n_hits;
-    const int q = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-    const unsigned long long* tab = table + (int64_t)q * n_groups;
-    const unsigned* cnt = COUNT ? counts + (int64_t)q * n_groups : nullptr;
-    // the sort key of slot i: the group's best candidate key, or (count, 0xffffffff - i); 0 = an empty slot
-    auto key_of = [&](int i) -> unsigned long long {
-        if (!COUNT) return tab[i];
-        const unsigned c = cnt[i];
-        return c != 0u ? ((unsigned long long)c << 32) | (unsigned long long)(0xffffffffu - (unsigned)i) : 0ull;
-    };
-    if (tid == 0) {
-        n_sel = 0;
-        n_live = 0;
-        n_hits = 0ull;
-    }
-    __syncthreads();
-    int mine = 0;
-    unsigned long long hits = 0ull;
-    for (int i = tid; i < n_groups; i += kGroupSelThreads) {
-        if (COUNT) {
-            const unsigned c = cnt[i];
-            mine += c != 0u ? 1 : 0;
-            hits += c;
-        } else {
-            mine += tab[i] != 0ull ? 1 : 0;
-        }
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) mine += __shfl_xor(mine, o, 64);
-    if (lane == 0 && mine) atomicAdd(&n_live, mine);
-    if (COUNT) {
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) hits += __shfl_xor(hits, o, 64);
-        if (lane == 0 && hits) atomicAdd(&n_hits, hits);
-    }
-    __syncthreads();
-    const int live = n_live;
-    if (tid == 0) total[q] = (int64_t)live;
-    if (COUNT && tid == 0) total_hits[q] = (int64_t)n_hits;
-    if (tid == 0 && q == 0) *out_status = *status != 0u ? 1 : 0;   // the scan's out-of-range flag, handed to the caller
+    constexpr bool METRIC = false;
+    const MetricOrder mo{nullptr, nullptr, false};
+#include "group_select_body.inc"
+}
 
-    // T: the k-th largest key where more than k slots are taken (selected = keys >= T), else 1 (every non-zero slot)
-    unsigned long long T = 1ull;
-    if (live > k) {
-        unsigned long long prefix = 0, pmask = 0;
-        int rank = k;
-        for (int shift = 56; shift >= 0; shift -= 8) {
-            if (tid < 256) hist[tid] = 0u;
-            __syncthreads();
-            // whole rounds of the workgroup: hist_add's ballots need every lane of a wave in the same iteration
-            for (int i0 = 0; i0 < n_groups; i0 += kGroupSelThreads) {
-                const int i = i0 + tid;
-                const unsigned long long key = i < n_groups ? key_of(i) : 0ull;
-                hist_add(hist, key != 0ull && (key & pmask) == prefix, (unsigned)(key >> shift) & 255u);
-            }
-            __syncthreads();
-            if (wid == 0) {   // lane l: digits 4l .. 4l+3; the largest digit d with #(digit >= d) >= rank
-                const unsigned c0 = hist[4 * lane], c1 = hist[4 * lane + 1], c2 = hist[4 * lane + 2], c3 = hist[4 * lane + 3];
-                const unsigned own = c0 + c1 + c2 + c3;
-                unsigned suf = own;   // inclusive suffix over lanes >= l
-#pragma unroll
-                for (int o = 1; o < 64; o <<= 1) {
-                    const unsigned v = __shfl_down(suf, o, 64);
-                    if (lane + o < 64) suf += v;
-                }
-                const unsigned above = suf - own;
-                const unsigned s3 = above + c3, s2 = s3 + c2, s1 = s2 + c1, s0 = s1 + c0;
-                const unsigned r = (unsigned)rank;
-                int d = -1;
-                unsigned sup = 0;   // #(digit > d)
-                if (s0 >= r) { d = 4 * lane; sup = s1; }
-                if (s1 >= r) { d = 4 * lane + 1; sup = s2; }
-                if (s2 >= r) { d = 4 * lane + 2; sup = s3; }
-                if (s3 >= r) { d = 4 * lane + 3; sup = above; }
-                const unsigned long long b = __ballot(d >= 0);
-                const int top = 63 - __clzll(b);
-                if (lane == top) {
-                    sh_digit = d;
-                    sh_rank = rank - (int)sup;
-                }
-            }
-            __syncthreads();
-            prefix |= (unsigned long long)sh_digit << shift;
-            pmask |= 255ull << shift;
-            rank = sh_rank;
-            __syncthreads();
-        }
-        T = prefix;
-    }
-    // gather the taken keys with their slots (min(live, k) of them), pad to a power of two with key 0, sort descending
-    const int n = live < k ? live : k;
-    int n2 = 1;
-    while (n2 < n) n2 <<= 1;
-    for (int i = tid; i < n_groups; i += kGroupSelThreads) {
-        const unsigned long long key = key_of(i);
-        if (key >= T) {
-            const int pos = atomicAdd(&n_sel, 1);
-            if (pos < kGroupMaxK) {
-                keys[pos] = key;
-                grp[pos] = i;
-            }
+// The terms aggregation of a stats scan ordered by a metric (kernels.h launch_group_stats_select).
+__global__ __launch_bounds__(kGroupSelThreads) void group_stats_select_kernel(const unsigned long long* __restrict__ table,
+                                                                              const unsigned* __restrict__ counts, const MetricOrder mo,
+                                                                              int n_groups, int k, int64_t id_base,
+                                                                              const int64_t* __restrict__ id_map, float* __restrict__ out_scores,
+                                                                              int64_t* __restrict__ out_ids, int32_t* __restrict__ out_groups,
+                                                                              int64_t* __restrict__ out_counts, int64_t* __restrict__ total,
+                                                                              int64_t* __restrict__ total_hits,
+                                                                              const unsigned* __restrict__ status, int32_t* __restrict__ out_status) {
+    constexpr bool COUNT = true, METRIC = true;
+#include "group_select_body.inc"
+}
+
+// The decoded stats planes of the buckets a select listed (kernels.h launch_group_stats_gather): one thread per output cell.
+__global__ void group_stats_gather_kernel(const int32_t* __restrict__ groups, const unsigned* __restrict__ vcount,
+                                          const long long* __restrict__ sum, const unsigned* __restrict__ vmin,
+                                          const unsigned* __restrict__ vmax, int nq, int n_groups, int size,
+                                          int64_t* __restrict__ out_vcounts, int64_t* __restrict__ out_sums, int32_t* __restrict__ out_mins,
+                                          int32_t* __restrict__ out_maxs) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (int64_t)nq * size) return;
+    const int q = (int)(i / size);
+    const int g = groups[i];
+    int64_t vc = 0, sm = 0;
+    int32_t mn = 0, mx = 0;
+    if (g >= 0 && g < n_groups) {
+        const int64_t at = (int64_t)q * n_groups + g;
+        vc = (int64_t)vcount[at];
+        if (vc != 0) {
+            sm = (int64_t)sum[at];
+            mn = stats_unbias(~vmin[at]);
+            mx = stats_unbias(vmax[at]);
         }
     }
-    for (int i = n + tid; i < n2; i += kGroupSelThreads) keys[i] = 0ull;   // [n, n2): no gathered key lands there
-    __syncthreads();
-    for (int size = 2; size <= n2; size <<= 1)
-        for (int stride = size >> 1; stride > 0; stride >>= 1) {
-            for (int i = tid; i < n2; i += kGroupSelThreads) {
-                const int j = i ^ stride;
-                if (j > i) {
-                    const unsigned long long a = keys[i], b = keys[j];
-                    const bool descending = (i & size) == 0;
-                    if ((a < b) == descending) {
-                        keys[i] = b, keys[j] = a;
-                        const int ga = grp[i];
-                        grp[i] = grp[j], grp[j] = ga;
-                    }
-                }
-            }
-            __syncthreads();
-        }
-    float* os = out_scores + (int64_t)q * k;
-    int64_t* oi = out_ids + (int64_t)q * k;
-    int32_t* og = out_groups + (int64_t)q * k;
-    for (int i = tid; i < k; i += kGroupSelThreads) {
-        float s = -INFINITY;
-        int64_t id = -1, c = 0;
-        int32_t g = -1;
-        if (i < n) {
-            g = grp[i];
-            c = COUNT ? (int64_t)(keys[i] >> 32) : 0;
-            const unsigned long long key = COUNT ? tab[g] : keys[i];   // the bucket's best row: a counted slot has one
-            const int64_t row = (int64_t)(0xffffffffu - (unsigned)key);
-            s = key_score((unsigned)(key >> 32));
-            id = id_map ? id_map[row] : id_base + row;
-        }
-        os[i] = s;
-        oi[i] = id;
-        og[i] = g;
-        if (COUNT) out_counts[(int64_t)q * k + i] = c;
-    }
+    out_vcounts[i] = vc;
+    out_sums[i] = sm;
+    out_mins[i] = mn;
+    out_maxs[i] = mx;
 }
 
 // The inner hits of a group-top scan (kernels.h launch_group_hits_finish): levels 0 .. gs - 1 of every slot the select chose,
@@ -293,6 +203,43 @@ hipError_t launch_group_count_select(const unsigned* counts, const unsigned long
         return hipErrorInvalidValue;
     hipLaunchKernelGGL(group_select_kernel<true>, dim3(nq), dim3(kGroupSelThreads), 0, stream, best, counts, n_groups, size, id_base,
                        id_map, out_scores, out_ids, out_groups, out_counts, n_buckets, total_hits, status, out_status);
+    return hipGetLastError();
+}
+
+hipError_t launch_group_stats_select(const unsigned* counts, const unsigned long long* best, const unsigned* vcount, const unsigned* vmin,
+                                     const unsigned* vmax, int order_by, bool descending, int nq, int n_groups, int size, int64_t id_base,
+                                     const int64_t* id_map, int32_t* out_groups, int64_t* out_counts, float* out_scores, int64_t* out_ids,
+                                     int64_t* n_buckets, int64_t* total_hits, const unsigned* status, int32_t* out_status,
+                                     hipStream_t stream) {
+    if (order_by == kStatsByCount && descending)   // OpenSearch's default bucket order: the select as it is
+        return launch_group_count_select(counts, best, nq, n_groups, size, id_base, id_map, out_groups, out_counts, out_scores, out_ids,
+                                         n_buckets, total_hits, status, out_status, stream);
+    if (nq < 1 || size < 1 || size > kGroupMaxK || n_groups < 1 || n_groups > kGroupMaxGroups || !counts || !best || !vcount || !vmin ||
+        !vmax || !out_groups || !out_counts || !out_scores || !out_ids || !n_buckets || !total_hits || !status || !out_status)
+        return hipErrorInvalidValue;
+    MetricOrder mo;
+    switch (order_by) {
+        // the planes hold count, vcount and biased max as they order, and the biased min complemented
+        case kStatsByCount: mo = MetricOrder{counts, counts, !descending}; break;
+        case kStatsByValueCount: mo = MetricOrder{vcount, vcount, !descending}; break;
+        case kStatsByMin: mo = MetricOrder{vcount, vmin, descending}; break;
+        case kStatsByMax: mo = MetricOrder{vcount, vmax, !descending}; break;
+        default: return hipErrorInvalidValue;
+    }
+    hipLaunchKernelGGL(group_stats_select_kernel, dim3(nq), dim3(kGroupSelThreads), 0, stream, best, counts, mo, n_groups, size, id_base,
+                       id_map, out_scores, out_ids, out_groups, out_counts, n_buckets, total_hits, status, out_status);
+    return hipGetLastError();
+}
+
+hipError_t launch_group_stats_gather(const int32_t* groups, const unsigned* vcount, const long long* sum, const unsigned* vmin,
+                                     const unsigned* vmax, int nq, int n_groups, int size, int64_t* out_vcounts, int64_t* out_sums,
+                                     int32_t* out_mins, int32_t* out_maxs, hipStream_t stream) {
+    if (nq < 1 || size < 1 || size > kGroupMaxK || n_groups < 1 || n_groups > kGroupMaxGroups || !groups || !vcount || !sum || !vmin ||
+        !vmax || !out_vcounts || !out_sums || !out_mins || !out_maxs)
+        return hipErrorInvalidValue;
+    const int64_t cells = (int64_t)nq * size;
+    hipLaunchKernelGGL(group_stats_gather_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, stream, groups, vcount, sum, vmin,
+                       vmax, nq, n_groups, size, out_vcounts, out_sums, out_mins, out_maxs);
     return hipGetLastError();
 }
 

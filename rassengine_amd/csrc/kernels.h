@@ -189,6 +189,38 @@ struct GroupTopArgs {
 };
 hipError_t launch_scan_grouptop_f32(const GroupTopArgs& a, int grid, hipStream_t stream);
 
+// ---- stats scan (scan_stats.hip, on scan_flat.h's loop): per (query, group), the hits of a key-column group-count scan AND
+// the count / sum / min / max of an int32 value column over them, for one launch group, in one pass.
+// `scan` carries what a key-column group-count launch of launch_scan_topk_f32 would (corpus, row_tag or nullptr, q_padded
+// [32][row_stride] zero-padded, q_filter / q_filter_mask, range_thr [nq], group_keys / group_key_rows, group_n, group_status,
+// allow / allow_q_stride, row_stride 128 * {1..8}, n_rows >= 1, nq <= 32) except count_table, which stays nullptr as every
+// other field of it does: the counters are `count` below.  group_keys == nullptr: every row < group_key_rows has key 0 (the
+// global form; group_n is then 1).  values: the value of row r is values[r], kStatsMissing = no value; nullptr: every row
+// reads kStatsMissing (a column that was never set) and no memory request is made.
+// The table is PLANE-MAJOR, six arrays of [nq][group_n] zeroed by the caller, slot q * group_n + g:
+//   scan.group_table  u64  the best hit's candidate key (scan_core.h cand_key), as the group-count scan folds it
+//   count             u32  hits
+//   vcount            u32  hits with a value
+//   sum               i64  the sum of those values (|v| < 2^31 and < 2^31 rows: it cannot overflow)
+//   vmax              u32  stats_bias(largest value), stats_bias(v) = (uint32)v ^ 0x80000000: order-preserving, under atomicMax
+//   vmin              u32  ~stats_bias(smallest value), under atomicMax too
+// vcount == 0 says that vmin / vmax hold no value: the all-zero table is the empty table.  group_table and count end byte for
+// byte as a kGroupCountKeys scan leaves them, so launch_group_count_select reads them as they stand.  A hit with key >=
+// group_n is left out and sets *group_status.  ScanArgs itself is untouched.
+constexpr int32_t kStatsMissing = INT32_MIN;   // = RASS_ATTR_MISSING
+__host__ __device__ inline unsigned stats_bias(int32_t v) { return (unsigned)v ^ 0x80000000u; }
+__host__ __device__ inline int32_t stats_unbias(unsigned u) { return (int32_t)(u ^ 0x80000000u); }
+struct StatsArgs {
+    ScanArgs scan;
+    const int32_t* values = nullptr;
+    unsigned* count = nullptr;
+    unsigned* vcount = nullptr;
+    long long* sum = nullptr;
+    unsigned* vmin = nullptr;
+    unsigned* vmax = nullptr;
+};
+hipError_t launch_scan_stats_f32(const StatsArgs& a, int grid, hipStream_t stream);
+
 // ---- bonus columns (bonus.hip): the dense fp32 columns the boosted scan adds.  A column block is [n_bonus][stride] floats.
 // Plain vector loads and stores, no atomics.
 // bonus[q_of[i] * stride + rows[i]] = that value + values[i] (one rounded add) for i < n.  The (q, row) pairs must be UNIQUE
@@ -320,6 +352,24 @@ hipError_t launch_group_hits_finish(const unsigned long long* table, int nq, int
                                     const int64_t* id_map, const int32_t* groups, float* out_scores, int64_t* out_ids,
                                     float* cap_scores, int64_t* cap_ids, const unsigned* status, int32_t* out_status, bool accumulate,
                                     hipStream_t stream);
+// The answer of a stats scan (StatsArgs above), in two launches (group_topk.hip).
+// launch_group_stats_select: launch_group_count_select's outputs with the buckets ordered by `order_by` (kStatsBy*), descending
+// or ascending.  kStatsByCount descending IS launch_group_count_select, the same kernel.  Otherwise the select's key of slot g
+// with count > 0 is  1 << 53 | has_value << 52 | metric << 20 | (2^20 - 1 - g),  metric = the counter, vcount, or the biased
+// min / max of the slot, complemented for ascending order: the buckets without a value (vcount == 0; never under kStatsByCount)
+// come after every bucket that has one in both directions, and ties break by group ascending.  n_buckets / total_hits as there.
+// launch_group_stats_gather: for the buckets the select listed (groups [nq][size], -1 past the end) the decoded planes,
+// out_vcounts / out_sums (int64) and out_mins / out_maxs (int32) [nq][size]; (0, 0, 0, 0) past the end and for a bucket
+// without a value.
+enum StatsOrder { kStatsByCount = 0, kStatsByValueCount = 1, kStatsByMin = 2, kStatsByMax = 3 };
+hipError_t launch_group_stats_select(const unsigned* counts, const unsigned long long* best, const unsigned* vcount, const unsigned* vmin,
+                                     const unsigned* vmax, int order_by, bool descending, int nq, int n_groups, int size, int64_t id_base,
+                                     const int64_t* id_map, int32_t* out_groups, int64_t* out_counts, float* out_scores, int64_t* out_ids,
+                                     int64_t* n_buckets, int64_t* total_hits, const unsigned* status, int32_t* out_status,
+                                     hipStream_t stream);
+hipError_t launch_group_stats_gather(const int32_t* groups, const unsigned* vcount, const long long* sum, const unsigned* vmin,
+                                     const unsigned* vmax, int nq, int n_groups, int size, int64_t* out_vcounts, int64_t* out_sums,
+                                     int32_t* out_mins, int32_t* out_maxs, hipStream_t stream);
 
 // ---- allow-list search (allow.hip): row bitmaps, their work list, and the store of a pass.  A bitmap is uint32 words, bit
 // (r & 31) of word r >> 5 allows row r.  Plain vector loads, stores and atomics.

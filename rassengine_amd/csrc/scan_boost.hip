@@ -51,6 +51,7 @@ struct BoostPolicy {
     __device__ __forceinline__ void pair_top(const WorkItem& w0, const WorkItem& w1) {
         col.park_and_request(w0.tile, bonus_rows_of(w0), w1.tile, bonus_rows_of(w1));
     }
+    __device__ __forceinline__ void tile_ahead(int, const WorkItem&) {}
     __device__ __forceinline__ void last_pair() { col.park(); }
     // The fused score of one (row, query), inserted into the query's list.
     __device__ __forceinline__ void rank(const FlatPart<NT>& c, int, int which, int pq) {

@@ -1,4 +1,4 @@
-// scan_flat.h — the flat pair loop of the boosted and function-score scans (scan_boost.hip, scan_fscore.hip), written once:
+// scan_flat.h — the flat pair loop of the boosted, function-score and stats scans (scan_boost.hip, scan_fscore.hip, scan_stats.hip), written once:
 // scan_topk_f32_kernel's flat loop (scan_topk.hip) built from the blocks of scan_core.h.  The K axis is split over the 8
 // waves, two 16-row blocks of a tile run against NT N-tiles of queries, one v_mfma_f32_16x16x4_f32 chain per (row, query) in
 // k order from zero, the partials are summed p0 + ... + p7 out of LDS, two tiles go per barrier and the previous pair is
@@ -150,12 +150,15 @@ struct FlatShared {
 
 // The loop.  A Policy is an object in the kernel's registers with
 //     setup(q, live)            thread q < 32 fills the policy's per-query LDS words (live: q < nq); a barrier follows
+//     tile_ahead(which, w)      tile w is about to be requested into register set `which` (0 / 1): ahead of its corpus loads,
+//                               in the prologue and before each refill; every thread
 //     pair_top(w0, w1)          the top of the iteration that multiplies (w0, w1), ahead of its refills; every thread
 //     rank(part, buf, which, pq)  rank or emit one lane's FlatPart of tile `which` of the previous pair, dumped in image buf
 //     last_pair()               before the last pair is ranked, behind the loop
 // and the order of these against the corpus loads is the loop's: requests ahead of the refills, parking before the
 // requests, one barrier per iteration.
-// Both column scans fill every hook.  The group-top scan (scan_grouptop.hip) keeps a loop of its own: on this one it measured
+// Both column scans leave tile_ahead empty (their columns are requested a pair at a time, in pair_top) and fill every other
+// hook; the stats scan (scan_stats.hip) requests its key and value words there, as the group-top scan does.  The group-top scan (scan_grouptop.hip) keeps a loop of its own: on this one it measured
 // 0.66 % slower at group_size 3 over 100 groups, or, with its key read first, carried one s_waitcnt more in 4 kernels.
 template <int CH, int NT, typename Policy>
 __device__ __forceinline__ void flat_pair_scan(const ScanArgs& p, const FlatShared& sh, Policy& pol) {
@@ -205,6 +208,8 @@ __device__ __forceinline__ void flat_pair_scan(const ScanArgs& p, const FlatShar
         return w;
     };
     WorkItem W0 = work(t), W1 = work(t + G);
+    pol.tile_ahead(0, W0);
+    pol.tile_ahead(1, W1);
     issue_tile_loads<CH>(R0, make_tile_desc(p.corpus, p.row_stride, p.row_tag, W0), voff_lane, mt_step);
     issue_tile_loads<CH>(R1, make_tile_desc(p.corpus, p.row_stride, p.row_tag, W1), voff_lane, mt_step);
     __builtin_amdgcn_sched_barrier(0);
@@ -247,6 +252,7 @@ __device__ __forceinline__ void flat_pair_scan(const ScanArgs& p, const FlatShar
         const WorkItem Wa = W0;
         t += 2 * G;
         WorkItem Wn = work(t);
+        pol.tile_ahead(0, Wn);
         auto rank_prev = [&](int slot) {
 #pragma unroll
             for (int part = 0; part < kParts; ++part)
@@ -263,6 +269,7 @@ __device__ __forceinline__ void flat_pair_scan(const ScanArgs& p, const FlatShar
         W0 = Wn;
         const WorkItem Wb = W1;
         Wn = work(t + G);
+        pol.tile_ahead(1, Wn);
         multiply_and_refill<CH, NT>(R1, qf, acc, make_tile_desc(p.corpus, p.row_stride, p.row_tag, Wn), voff_lane, mt_step,
                                     [&](int j) { rank_prev(CH + j); });
         dump_tile(acc, pair + 1);

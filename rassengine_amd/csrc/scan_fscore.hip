@@ -55,6 +55,7 @@ struct FscorePolicy {
     __device__ __forceinline__ void pair_top(const WorkItem& w0, const WorkItem& w1) {
         col.park_and_request(w0.tile, w0.rows, w1.tile, w1.rows);
     }
+    __device__ __forceinline__ void tile_ahead(int, const WorkItem&) {}
     __device__ __forceinline__ void last_pair() { col.park(); }
     // The fused score of one (row, query), inserted into the query's list.
     __device__ __forceinline__ void rank(const FlatPart<NT>& c, int, int which, int pq) {

@@ -888,6 +888,81 @@ class FlatIndex:
                     ctypes.c_void_p(d_out_scores_ptr), ctypes.c_void_p(d_out_ids_ptr), ctypes.c_void_p(d_n_buckets_ptr),
                     ctypes.c_void_p(d_total_hits_ptr), ctypes.c_void_p(d_status_ptr)))
 
+    STATS_ORDERS = {"_count": N.RASS_STATS_BY_COUNT, "value_count": N.RASS_STATS_BY_VALUE_COUNT, "min": N.RASS_STATS_BY_MIN,
+                    "max": N.RASS_STATS_BY_MAX}
+
+    @staticmethod
+    def _check_stats(value_col, order_by, keys, n_groups) -> Tuple[int, int]:
+        value_col = int(value_col)
+        if not 0 <= value_col < N.RASS_MAX_ATTRS:
+            raise ValueError(f"value_col must be in [0, {N.RASS_MAX_ATTRS}), got {value_col}")
+        if order_by not in FlatIndex.STATS_ORDERS:
+            raise ValueError(f"order_by must be one of {sorted(FlatIndex.STATS_ORDERS)}, got {order_by!r}")
+        if keys is None and int(n_groups) != 1:
+            raise ValueError(f"keys=None is the global form: n_groups must be 1, got {n_groups}")
+        return value_col, FlatIndex.STATS_ORDERS[order_by]
+
+    def search_stats_by_keys(self, queries: np.ndarray, min_score, size: int, keys, n_groups: int, value_col: int,
+                             order_by: str = "_count", descending: bool = True, allow=None,
+                             q_filter: Optional[np.ndarray] = None, q_filter_mask: Optional[np.ndarray] = None):
+        """``search_counts_by_keys`` with a stats sub-aggregation (``rass_index_aggregate_stats_keys``): per listed bucket also
+        the count, sum, min and max of attribute column ``value_col`` over the bucket's hits, in the same corpus pass.
+        ``keys=None`` with ``n_groups=1`` is the global form (every row in bucket 0).  ``order_by``: ``"_count"``,
+        ``"value_count"``, ``"min"`` or ``"max"``, ``descending`` or not; ties by key ascending, buckets without a present
+        value last in both directions.  Returns ``(groups, counts, scores, ids, value_counts, sums, mins, maxs, n_buckets,
+        total_hits)``: the first four and last two as ``search_counts_by_keys`` (identical to it under ``"_count"``
+        descending), the stats ``[nq, size]`` int64 / int64 / int32 / int32 with zeros where a bucket has no present value
+        and past the last bucket.  fp32 indices with dim <= 1024."""
+        q = self._queries(queries)
+        nq = q.shape[0]
+        thr = self._thresholds(min_score, nq)
+        size, _, n_groups = self._check_counts(size, 1, n_groups)
+        value_col, by = self._check_stats(value_col, order_by, keys, n_groups)
+        f, m = self._filters(q_filter, q_filter_mask, nq)
+        fit = keys if keys is not None else np.zeros(0, dtype=np.int32)
+        self._check_keys(fit, allow, nq)
+        out_g = np.empty((nq, size), dtype=np.int32)
+        out_c = np.empty((nq, size), dtype=np.int64)
+        out_s = np.empty((nq, size), dtype=np.float32)
+        out_i = np.empty((nq, size), dtype=np.int64)
+        out_vc = np.empty((nq, size), dtype=np.int64)
+        out_sum = np.empty((nq, size), dtype=np.int64)
+        out_min = np.empty((nq, size), dtype=np.int32)
+        out_max = np.empty((nq, size), dtype=np.int32)
+        n_buckets = np.empty((nq,), dtype=np.int64)
+        total = np.empty((nq,), dtype=np.int64)
+        if nq > 0:
+            fn = "rass_index_aggregate_stats_keys"
+            self._by_keys(fn, fit, allow, lambda d_keys, n_keys, d_allow, n_bitmaps, words: self._L.rass_index_aggregate_stats_keys(
+                self._h, _np_ptr(q), nq, _np_ptr(thr), size, d_keys if keys is not None else None, n_keys, n_groups, value_col, by,
+                1 if descending else 0, d_allow, n_bitmaps, words, _np_ptr(f), _np_ptr(m), _np_ptr(out_g), _np_ptr(out_c),
+                _np_ptr(out_s), _np_ptr(out_i), _np_ptr(out_vc), _np_ptr(out_sum), _np_ptr(out_min), _np_ptr(out_max),
+                _np_ptr(n_buckets), _np_ptr(total)))
+        return out_g, out_c, out_s, out_i, out_vc, out_sum, out_min, out_max, n_buckets, total
+
+    def search_stats_by_keys_device(self, d_queries_ptr: int, nq: int, d_min_score_ptr: int, size: int, d_keys_ptr: int,
+                                    n_keys: int, n_groups: int, value_col: int, d_out_groups_ptr: int, d_out_counts_ptr: int,
+                                    d_out_scores_ptr: int, d_out_ids_ptr: int, d_out_value_counts_ptr: int, d_out_sums_ptr: int,
+                                    d_out_mins_ptr: int, d_out_maxs_ptr: int, d_n_buckets_ptr: int, d_total_hits_ptr: int,
+                                    d_status_ptr: int, order_by: str = "_count", descending: bool = True, d_allow_ptr: int = 0,
+                                    n_bitmaps: int = 0, words_per_bitmap: int = 0, id_base: int = 0, d_q_filter_ptr: int = 0,
+                                    d_q_filter_mask_ptr: int = 0) -> None:
+        """Async, device-resident ``search_stats_by_keys`` (``rass_index_aggregate_stats_keys_device``); nq <= 32.
+        ``d_keys_ptr`` 0 with ``n_groups`` 1 is the global form.  Nothing is padded.  ``*d_status`` as in
+        ``search_counts_device``."""
+        size, _, n_groups = self._check_counts(size, 1, n_groups)
+        value_col, by = self._check_stats(value_col, order_by, d_keys_ptr or None, n_groups)
+        N.check("rass_index_aggregate_stats_keys_device",
+                self._L.rass_index_aggregate_stats_keys_device(
+                    self._h, ctypes.c_void_p(d_queries_ptr), int(nq), ctypes.c_void_p(d_min_score_ptr), size,
+                    ctypes.c_void_p(d_keys_ptr or 0), int(n_keys), n_groups, value_col, by, 1 if descending else 0,
+                    ctypes.c_void_p(d_allow_ptr or 0), int(n_bitmaps), int(words_per_bitmap),
+                    ctypes.c_void_p(d_q_filter_ptr or 0), ctypes.c_void_p(d_q_filter_mask_ptr or 0), int(id_base),
+                    ctypes.c_void_p(d_out_groups_ptr), ctypes.c_void_p(d_out_counts_ptr), ctypes.c_void_p(d_out_scores_ptr),
+                    ctypes.c_void_p(d_out_ids_ptr), ctypes.c_void_p(d_out_value_counts_ptr), ctypes.c_void_p(d_out_sums_ptr),
+                    ctypes.c_void_p(d_out_mins_ptr), ctypes.c_void_p(d_out_maxs_ptr), ctypes.c_void_p(d_n_buckets_ptr),
+                    ctypes.c_void_p(d_total_hits_ptr), ctypes.c_void_p(d_status_ptr)))
+
     # ---- allow-list search: exact top-k within a per-query row bitmap
     @property
     def allow_words(self) -> int:

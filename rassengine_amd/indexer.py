@@ -553,6 +553,117 @@ class HipIndexer:
                         "cardinality": int(n_buckets[0]), "total": total}
         raise RuntimeError(f"{self.index_name}: the index was compacted during every one of {LAYOUT_ATTEMPTS} searches")
 
+    STATS_ORDERS = ("_count", "value_count", "min", "max", "sum", "avg")
+
+    def semantic_stats(self, query_emb: np.ndarray, min_score: float, field: str, by: Optional[str] = None, size: int = 5,
+                       interval: Optional[Any] = None, order: Optional[Dict[str, str]] = None, where: Optional[Any] = None,
+                       filter_clause: Optional[Dict] = None, patient_id: Optional[str] = None) -> Dict[str, Any]:
+        """``semantic_aggregate`` with OpenSearch's ``stats`` metric sub-aggregation on ``field`` (an int or date attribute
+        field; a keyword raises ``ValueError``: codes have no arithmetic): per bucket also the count, min, max, sum and avg
+        of ``field`` over the chunks that score at least ``min_score``, in the same single pass over the index
+        (``FlatIndex.search_stats_by_keys``).  ``by=None`` gives the global stats (one bucket, ``key`` None); ``by`` and
+        ``interval`` as in ``semantic_aggregate`` (``patientId`` / ``doc_type`` go through a key column built from the tag).
+        The result has ``semantic_aggregate``'s shape, each bucket gaining::
+
+            "stats": {"count": chunks with a value, "min", "max", "sum", "avg": float(sum) / float(count)}
+
+        with ``min`` / ``max`` / ``avg`` None where ``count`` is 0, and ``min_as_string`` / ``max_as_string`` (ISO dates) on
+        a date field, whose values are days since 1970-01-01.
+
+        ``order``: ``{"_count" | "value_count" | "min" | "max" | "sum" | "avg": "asc" | "desc"}``, default ``_count``
+        descending (a histogram without ``order`` stays in key order).  Ties go to the first-indexed value, and buckets
+        whose chunks all lack the field come last in both directions.  The first four are ordered on the GPU before the
+        ``size`` cut; ``sum`` and ``avg`` are ordered here, which needs every bucket listed: a histogram, or a first answer
+        with ``cardinality <= size`` — otherwise ``ValueError``.  ``where`` and the filters as ``semantic_aggregate``.
+        IVF-backed and sharded indices raise ``NotImplementedError``; errors raise."""
+        st: Optional[IndexState] = REGISTRY.get(self.index_name, create=False)
+        found = st.attrs.column(field) if st is not None and isinstance(field, str) and getattr(st, "attrs", None) else None
+        if st is not None and found is None:
+            raise ValueError(f"field must be an int or date attribute field of the index, not {field!r}")
+        if found is not None and found[1] not in ("int", "date"):
+            raise ValueError(f"stats need an int or date attribute field, and {field!r} is a {found[1]} (codes have no arithmetic)")
+        order = {"_count": "desc"} if order is None and interval is None else order
+        if order is not None and (not isinstance(order, dict) or len(order) != 1 or next(iter(order)) not in self.STATS_ORDERS
+                                  or next(iter(order.values())) not in ("asc", "desc")):
+            raise ValueError(f"order must be {{one of {self.STATS_ORDERS}: 'asc' | 'desc'}}, not {order!r}")
+        grp = _GroupBy("by", by, st, interval) if by is not None else None
+        if grp is None and interval is not None:
+            raise ValueError("interval needs by=")
+        empty = {"buckets": [], "sum_other_doc_count": 0, "cardinality": 0, "total": 0}
+        if _empty(query_emb) or st is None:
+            return empty
+        prep = self._prepare(st, query_emb, size, filter_clause, patient_id, None)
+        if prep is None:
+            return empty
+        q, size_eff, (fval, fmask) = prep
+        if not hasattr(st.index, "search_stats_by_keys"):
+            raise NotImplementedError(f"{self.index_name}: {type(st.index).__name__} has no stats aggregation "
+                                      "(IVF-backed and sharded indices cannot aggregate per group; use a flat fp32 index)")
+        self._need_keys(st, where, "stats aggregation")
+        col, kind = found
+        thr = np.array([_cos_of_score(min_score)], dtype=np.float32)
+        if np.isnan(thr[0]):
+            raise ValueError("min_score must not be NaN")
+        flt = dict(q_filter=np.array([fval], dtype=np.int32), q_filter_mask=np.array([fmask], dtype=np.int32)) if fmask else {}
+        by_name, direction = next(iter(order.items())) if order is not None else ("_count", "desc")
+        on_host = by_name in ("sum", "avg")
+        for _ in range(LAYOUT_ATTEMPTS):    # top_hit ids belong to one layout of the index, as in _knn
+            layout = _layout_epoch(st.index)
+            if grp is None:
+                from .attrfilter import compile_filter, run_plan
+                with st.lock:
+                    if _layout_epoch(st.index) != layout:
+                        continue
+                    allow = run_plan(st.index, compile_filter(where, st.attrs, st.patients, st.doc_types)) if where is not None else None
+                keyed = (None, 1, lambda g: None)
+            else:
+                built = self._keys_and_bitmap(st, grp, where, layout)
+                if built is None:
+                    continue
+                keyed, allow = built
+                if keyed is None:
+                    return empty
+            keys, n_groups, label = keyed
+            # a histogram lists every bucket; so does a host-side order, which cannot cut before it has sorted
+            ask = n_groups if interval is not None else size_eff
+            out = st.index.search_stats_by_keys(q, thr, ask, keys, n_groups, col, "_count" if on_host else by_name,
+                                                True if on_host else direction == "desc", allow=allow, **flt)
+            groups, counts, scores, ids, vcounts, sums, mins, maxs, n_buckets, totals = out
+            if on_host and int(n_buckets[0]) > ask:
+                raise ValueError(f"order by {by_name!r} is computed on the host and needs every bucket listed: the answer has "
+                                 f"{int(n_buckets[0])} buckets and size is {ask} (use a histogram, a larger size, or order by "
+                                 "'_count', 'value_count', 'min' or 'max')")
+            listed = [(int(g), int(c), s, i, int(vc), int(sm), int(mn), int(mx)) for g, c, s, i, vc, sm, mn, mx in
+                      zip(groups[0], counts[0], scores[0], ids[0], vcounts[0], sums[0], mins[0], maxs[0]) if g >= 0]
+            if order is None:
+                listed.sort()               # a histogram without an order: key order
+            elif on_host:                   # metric asc / desc, ties by key, buckets without a value last in both directions
+                sign = 1.0 if direction == "asc" else -1.0
+                metric = (lambda b: float(b[5])) if by_name == "sum" else (lambda b: float(b[5]) / float(b[4]))
+                listed.sort(key=lambda b: (b[4] == 0, sign * metric(b) if b[4] else 0.0, b[0]))
+                listed = listed[:size_eff] if interval is None else listed
+            as_string = (lambda v: _day_date(v).isoformat()) if kind == "date" else None
+            buckets = []
+            for g, c, s, i, vc, sm, mn, mx in listed:
+                top = self._hits(st, [s], [i], 1.0, None, layout)
+                if top is None:
+                    buckets = None
+                    break
+                stats = {"count": vc, "min": mn if vc else None, "max": mx if vc else None, "sum": sm,
+                         "avg": float(sm) / float(vc) if vc else None}
+                if as_string is not None:
+                    stats["min_as_string"] = as_string(mn) if vc else None
+                    stats["max_as_string"] = as_string(mx) if vc else None
+                bucket = {"key": label(g), "doc_count": c, "top_hit": top[0] if top else None, "stats": stats}
+                if interval is not None and grp.kind == "date":
+                    bucket["key_as_string"] = _day_date(bucket["key"]).isoformat()
+                buckets.append(bucket)
+            if buckets is not None:
+                total = int(totals[0])
+                return {"buckets": buckets, "sum_other_doc_count": total - sum(b["doc_count"] for b in buckets),
+                        "cardinality": int(n_buckets[0]), "total": total}
+        raise RuntimeError(f"{self.index_name}: the index was compacted during every one of {LAYOUT_ATTEMPTS} searches")
+
     def semantic_search_within(self, query_emb: np.ndarray, k: int = TOP_K, patient_ids: Optional[List[Any]] = None,
                                doc_types: Optional[List[str]] = None, doc_ids: Optional[List[str]] = None,
                                filter_clause: Optional[Dict] = None, patient_id: Optional[str] = None
