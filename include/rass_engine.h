@@ -816,6 +816,41 @@ int rass_index_aggregate_stats_keys_device(rass_index_t* idx, const float* d_que
                                            int64_t* d_out_ids, int64_t* d_out_value_counts, int64_t* d_out_sums,
                                            int32_t* d_out_mins, int32_t* d_out_maxs, int64_t* d_n_buckets,
                                            int64_t* d_total_hits, int32_t* d_status);
+/* TOP HITS SUB-AGGREGATION: rass_index_aggregate_keys(_device) with the top_hits best hits of every listed bucket — OpenSearch's
+ * `terms` -> `top_hits {size: n}`, the buckets ordered by doc_count or by `"order": {"max_score": "desc"}`.  Still ONE corpus
+ * pass per launch group, whatever top_hits is: the scan keeps, per (query, group), the hit count and a chain of top_hits slots
+ * that ends as the group's best hits (as rass_index_search_group_hits_keys keeps its rows, here for the hits above min_score
+ * only); then one select over the query's groups and one finish over the listed buckets.  Arguments, hit test, totals, ids
+ * (id_base, caller-assigned ids), status word, filters, bitmap, tombstones, RASS_KEY_NONE, n_keys >= rows, layout epochs and
+ * locking as rass_index_aggregate_keys(_device), plus:
+ * top_hits in [1, RASS_MAX_GROUP_SIZE], with n_groups * top_hits <= 1048576 (the engine-owned table, grown on demand;
+ *   RASS_ERR_OOM leaves the engine as it was).
+ * order_by: RASS_AGG_BY_COUNT — doc_count descending, then key ascending: rass_index_aggregate_keys' order, and groups /
+ *   counts / n_buckets / total_hits are exactly what that call reports; RASS_AGG_BY_SCORE — by each bucket's best hit under
+ *   (score descending, row ordinal ascending).  Only buckets with a hit are listed either way.  Any other: RASS_ERR_INVALID.
+ * out_groups / out_counts [nq][size]; out_scores / out_ids [nq][size][top_hits]: bucket j's hits best first under (score
+ *   descending, row ordinal ascending); entry [q][j][0] is what rass_index_aggregate_keys reports as the bucket's best hit.
+ *   (-inf, -1) past a bucket's last hit; (-1, 0, -inf, -1) past the last bucket.
+ * 1 <= size <= RASS_MAX_K_MULTIPASS.  A bound broken, or a NaN min_score in the host variant (on the device it matches
+ * nothing): RASS_ERR_INVALID, nothing is launched and the outputs are untouched.  fp32 flat indices with dim <= 1024 only: a
+ * bf16 index or a wide-row index answers RASS_ERR_UNSUPPORTED.  The prefilter mode is ignored: always the exact fp32 scan, and
+ * a score is the flat scan's bit for bit.  The host variant takes any nq in launch groups of RASS_MAX_QBATCH and fails with
+ * RASS_ERR_INVALID where a hit's key is >= n_groups; the device variant takes nq <= RASS_MAX_QBATCH, is stream-ordered,
+ * synchronises nothing and reports that condition as *d_status = 1 (0 otherwise). */
+#define RASS_AGG_BY_COUNT 0
+#define RASS_AGG_BY_SCORE 1
+int rass_index_aggregate_hits_keys(rass_index_t* idx, const float* queries, int nq, const float* min_score, int size,
+                                   const int32_t* d_keys, int64_t n_keys, int32_t n_groups, int top_hits, int order_by,
+                                   const uint32_t* d_allow, int n_bitmaps, int64_t words_per_bitmap,
+                                   const int32_t* q_filter, const int32_t* q_filter_mask,
+                                   int32_t* out_groups, int64_t* out_counts, float* out_scores, int64_t* out_ids,
+                                   int64_t* out_n_buckets, int64_t* out_total_hits);
+int rass_index_aggregate_hits_keys_device(rass_index_t* idx, const float* d_queries, int nq, const float* d_min_score, int size,
+                                          const int32_t* d_keys, int64_t n_keys, int32_t n_groups, int top_hits, int order_by,
+                                          const uint32_t* d_allow, int n_bitmaps, int64_t words_per_bitmap,
+                                          const int32_t* d_q_filter, const int32_t* d_q_filter_mask,
+                                          int64_t id_base, int32_t* d_out_groups, int64_t* d_out_counts, float* d_out_scores,
+                                          int64_t* d_out_ids, int64_t* d_n_buckets, int64_t* d_total_hits, int32_t* d_status);
 
 /* GRAM matrices of short row lists: out[l][i][j] = the fp32 dot product of stored rows rows[l][i] and rows[l][j], as they lie
  * in the slab (normalised at add time: their cosine).  The similarity structure of a result set, duplicate detection over an

@@ -21,7 +21,9 @@
 //
 // group_hits_finish_kernel runs behind the select of a grouped search with inner hits (scan_grouptop.hip; kernels.h
 // launch_group_hits_finish): the table then has group_size planes, the select has read plane 0, and the finish reads every plane
-// of the slots it chose.
+// of the slots it chose.  It needs only the listed groups and the level-major table, so it also runs behind the COUNT select of
+// a terms aggregation with top hits (scan_tophits.hip); where that aggregation orders its buckets by their best hit (the
+// plain select over plane 0), group_counts_gather_kernel fetches the listed buckets' counters and sums a query's counters.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -105,6 +107,30 @@ __global__ void group_stats_gather_kernel(const int32_t* __restrict__ groups, co
     out_sums[i] = sm;
     out_mins[i] = mn;
     out_maxs[i] = mx;
+}
+
+// The counters of the buckets a select over plane 0 of a top-hits table listed, and the sum of a query's counters (kernels.h
+// launch_group_counts_gather): one workgroup per query.
+__global__ __launch_bounds__(kGroupSelThreads) void group_counts_gather_kernel(const int32_t* __restrict__ groups,
+                                                                               const unsigned* __restrict__ counts, int n_groups, int size,
+                                                                               int64_t* __restrict__ out_counts,
+                                                                               int64_t* __restrict__ total_hits) {
+    __shared__ unsigned long long n_hits;
+    const int q = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
+    const unsigned* cnt = counts + (int64_t)q * n_groups;
+    if (tid == 0) n_hits = 0ull;
+    __syncthreads();
+    unsigned long long hits = 0ull;
+    for (int i = tid; i < n_groups; i += kGroupSelThreads) hits += cnt[i];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) hits += __shfl_xor(hits, o, 64);
+    if (lane == 0 && hits) atomicAdd(&n_hits, hits);
+    for (int i = tid; i < size; i += kGroupSelThreads) {
+        const int g = groups[(int64_t)q * size + i];
+        out_counts[(int64_t)q * size + i] = g >= 0 && g < n_groups ? (int64_t)cnt[g] : 0;
+    }
+    __syncthreads();
+    if (tid == 0) total_hits[q] = (int64_t)n_hits;
 }
 
 // The inner hits of a group-top scan (kernels.h launch_group_hits_finish): levels 0 .. gs - 1 of every slot the select chose,
@@ -240,6 +266,16 @@ hipError_t launch_group_stats_gather(const int32_t* groups, const unsigned* vcou
     const int64_t cells = (int64_t)nq * size;
     hipLaunchKernelGGL(group_stats_gather_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, stream, groups, vcount, sum, vmin,
                        vmax, nq, n_groups, size, out_vcounts, out_sums, out_mins, out_maxs);
+    return hipGetLastError();
+}
+
+hipError_t launch_group_counts_gather(const int32_t* groups, const unsigned* counts, int nq, int n_groups, int size,
+                                      int64_t* out_counts, int64_t* total_hits, hipStream_t stream) {
+    if (nq < 1 || size < 1 || size > kGroupMaxK || n_groups < 1 || n_groups > kGroupMaxGroups || !groups || !counts || !out_counts ||
+        !total_hits)
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(group_counts_gather_kernel, dim3(nq), dim3(kGroupSelThreads), 0, stream, groups, counts, n_groups, size, out_counts,
+                       total_hits);
     return hipGetLastError();
 }
 

@@ -221,6 +221,26 @@ struct StatsArgs {
 };
 hipError_t launch_scan_stats_f32(const StatsArgs& a, int grid, hipStream_t stream);
 
+// ---- top-hits scan (scan_tophits.hip, on scan_flat.h's loop): per (query, group), the hits of a key-column group-count scan
+// AND the `top_hits` best of them, for one launch group, in one pass: a terms aggregation with a top_hits sub-aggregation.
+// `scan` carries what a key-column group-count launch of launch_scan_topk_f32 would (see StatsArgs above; group_keys is not
+// nullptr here) except count_table, which stays nullptr: the counters are `count` below.
+//   scan.group_table  u64  LEVEL-MAJOR [top_hits][nq][group_n] as GroupTopArgs' table: level l of (q, g) at
+//                          group_table[l * level_stride + q * group_n + g], level_stride >= nq * group_n.  Per (q, g) the
+//                          candidate keys (scan_core.h cand_key) of the group's HITS from the largest down, 0 past the last
+//   count             u32  [nq][group_n] hits
+// all zeroed by the caller.  Plane 0 and count end byte for byte as a kGroupCountKeys scan leaves its two tables, so
+// launch_group_count_select and launch_group_select (over plane 0: only hits are in it) read them as they stand, and
+// launch_group_hits_finish runs behind either.  1 <= top_hits <= kGroupHitsMaxSize, group_n * top_hits <= kGroupMaxGroups.
+// A hit with key >= group_n is left out and sets *group_status.  ScanArgs itself is untouched.
+struct TopHitsArgs {
+    ScanArgs scan;
+    unsigned* count = nullptr;
+    int64_t level_stride = 0;
+    int top_hits = 0;
+};
+hipError_t launch_scan_tophits_f32(const TopHitsArgs& a, int grid, hipStream_t stream);
+
 // ---- bonus columns (bonus.hip): the dense fp32 columns the boosted scan adds.  A column block is [n_bonus][stride] floats.
 // Plain vector loads and stores, no atomics.
 // bonus[q_of[i] * stride + rows[i]] = that value + values[i] (one rounded add) for i < n.  The (q, row) pairs must be UNIQUE
@@ -370,6 +390,11 @@ hipError_t launch_group_stats_select(const unsigned* counts, const unsigned long
 hipError_t launch_group_stats_gather(const int32_t* groups, const unsigned* vcount, const long long* sum, const unsigned* vmin,
                                      const unsigned* vmax, int nq, int n_groups, int size, int64_t* out_vcounts, int64_t* out_sums,
                                      int32_t* out_mins, int32_t* out_maxs, hipStream_t stream);
+// The counters of a top-hits scan (TopHitsArgs above) behind launch_group_select over plane 0 of its table (the buckets
+// ordered by their best hit), one workgroup per query.  groups [nq][size] is what the select wrote (-1 past the end);
+// out_counts [nq][size] = the listed buckets' counters, 0 past the end; total_hits[q] = the sum of the query's counters.
+hipError_t launch_group_counts_gather(const int32_t* groups, const unsigned* counts, int nq, int n_groups, int size,
+                                      int64_t* out_counts, int64_t* total_hits, hipStream_t stream);
 
 // ---- allow-list search (allow.hip): row bitmaps, their work list, and the store of a pass.  A bitmap is uint32 words, bit
 // (r & 31) of word r >> 5 allows row r.  Plain vector loads, stores and atomics.

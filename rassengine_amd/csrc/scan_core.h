@@ -383,6 +383,41 @@ __device__ __forceinline__ void emit_group_count(bool hit, float s, int row, int
     if (key > __hip_atomic_load(best + slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(best + slot, key);
 }
 
+// The emission of a top-hits scan (scan_tophits.hip), in the place of insert_candidates: emit_group_count's counters with
+// emit_group_top's chain in the place of its one best-row slot — a terms aggregation whose buckets carry their `levels` best
+// hits.  g is the row's group (>= 0; a key column, no tag field).  The count comes FIRST and is emit_group_count's half-wave
+// logic to the letter: the chain's pre-read of the last level may skip the chain of a hit that cannot be among the bucket's
+// `levels` best, never its count.  Count slot of a hit: q * n_groups + g; level l of the chain at table[q * n_groups + l *
+// level_stride + g].  With one level the chain is emit_group_max's atomic: count and plane 0 end byte for byte as
+// emit_group_count leaves them.  Everything is addressed by one 32-bit slot index (< 2^25) from wave-uniform bases.
+// Plain vector loads, stores and atomics.
+__device__ __forceinline__ void emit_group_count_top(bool hit, float s, int row, int g, int q, int n_groups, unsigned long long* table,
+                                                     unsigned level_stride, int levels, unsigned* count, unsigned* status) {
+    const bool inside = (unsigned)g < (unsigned)n_groups;
+    hit = hit && s > -INFINITY;   // NaN and -inf never rank: no hit, no status
+    if (hit && !inside) __hip_atomic_store(status, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    hit = hit && inside;
+    const unsigned long long b = __ballot(hit);
+    if (b == 0) return;   // wave-uniform
+    const unsigned lo = (unsigned)b, hi = (unsigned)(b >> 32);
+    // the first hit lane of each half (a half without hits: any lane of it, nothing is compared with its key and it adds nothing)
+    const int f_lo = __builtin_amdgcn_readfirstlane(lo ? __builtin_ctz(lo) : 0);
+    const int f_hi = __builtin_amdgcn_readfirstlane(hi ? 32 + __builtin_ctz(hi) : 32);
+    const unsigned g_lo = (unsigned)__builtin_amdgcn_readlane(g, f_lo), g_hi = (unsigned)__builtin_amdgcn_readlane(g, f_hi);
+    const int lane = lane_id();
+    const bool upper = (lane & 32) != 0;
+    const unsigned long long d = __ballot(hit && (unsigned)g != (upper ? g_hi : g_lo));
+    const bool shared = (upper ? (unsigned)(d >> 32) : (unsigned)d) == 0u;   // my half's hits are of one group
+    if (!hit) return;
+    const unsigned slot_q = (unsigned)q * (unsigned)n_groups;
+    if (!shared)
+        atomicAdd(count + (slot_q + (unsigned)g), 1u);
+    else if (lane == (upper ? f_hi : f_lo))
+        atomicAdd(count + (slot_q + (unsigned)g), (unsigned)__popc(upper ? hi : lo));
+    // a hit lane from here on: in range and s > -inf, so emit_group_top neither drops it nor touches the status word
+    emit_group_top(true, s, row, g, n_groups, table, slot_q, level_stride, levels, status);
+}
+
 // Half-wave sorted list: lanes 0..31 hold query A's best-first top-32, lanes 32..63 query B's.
 struct TopList {
     float s;

@@ -963,6 +963,68 @@ class FlatIndex:
                     ctypes.c_void_p(d_out_mins_ptr), ctypes.c_void_p(d_out_maxs_ptr), ctypes.c_void_p(d_n_buckets_ptr),
                     ctypes.c_void_p(d_total_hits_ptr), ctypes.c_void_p(d_status_ptr)))
 
+    AGG_ORDERS = {"_count": N.RASS_AGG_BY_COUNT, "max_score": N.RASS_AGG_BY_SCORE}
+
+    @staticmethod
+    def _check_counts_hits(size, n_groups, top_hits, order_by) -> Tuple[int, int, int, int]:
+        size, _, n_groups = FlatIndex._check_counts(size, 1, n_groups)
+        top_hits = int(top_hits)
+        if not 1 <= top_hits <= FlatIndex.MAX_GROUP_SIZE:
+            raise ValueError(f"top_hits must be in [1, {FlatIndex.MAX_GROUP_SIZE}], got {top_hits}")
+        if n_groups * top_hits > FlatIndex.MAX_GROUPS:
+            raise ValueError(f"n_groups * top_hits must not exceed {FlatIndex.MAX_GROUPS}, got {n_groups} * {top_hits}")
+        if order_by not in FlatIndex.AGG_ORDERS:
+            raise ValueError(f"order_by must be one of {sorted(FlatIndex.AGG_ORDERS)}, got {order_by!r}")
+        return size, n_groups, top_hits, FlatIndex.AGG_ORDERS[order_by]
+
+    def search_counts_hits_by_keys(self, queries: np.ndarray, min_score, size: int, keys, n_groups: int, top_hits: int,
+                                   order_by: str = "_count", allow=None, q_filter: Optional[np.ndarray] = None,
+                                   q_filter_mask: Optional[np.ndarray] = None):
+        """``search_counts_by_keys`` with a top_hits sub-aggregation (``rass_index_aggregate_hits_keys``): per listed bucket
+        also its ``top_hits`` best hits, in the same corpus pass.  ``order_by``: ``"_count"`` (doc_count descending, then key
+        ascending: ``search_counts_by_keys``' order) or ``"max_score"`` (by each bucket's best hit).  ``keys`` / ``allow`` /
+        filters as in ``search_counts_by_keys``.  Returns ``(groups [nq, size], counts, scores [nq, size, top_hits], ids,
+        n_buckets [nq], total_hits)``: a bucket's hits best first (score descending, row ascending), ``(-inf, -1)`` past its
+        last hit, ``(-1, 0, -inf, -1)`` past the last bucket.  fp32 indices with dim <= 1024."""
+        q = self._queries(queries)
+        nq = q.shape[0]
+        thr = self._thresholds(min_score, nq)
+        size, n_groups, top_hits, by = self._check_counts_hits(size, n_groups, top_hits, order_by)
+        f, m = self._filters(q_filter, q_filter_mask, nq)
+        self._check_keys(keys, allow, nq)
+        out_g = np.empty((nq, size), dtype=np.int32)
+        out_c = np.empty((nq, size), dtype=np.int64)
+        out_s = np.empty((nq, size, top_hits), dtype=np.float32)
+        out_i = np.empty((nq, size, top_hits), dtype=np.int64)
+        n_buckets = np.empty((nq,), dtype=np.int64)
+        total = np.empty((nq,), dtype=np.int64)
+        if nq > 0:
+            fn = "rass_index_aggregate_hits_keys"
+            self._by_keys(fn, keys, allow, lambda d_keys, n_keys, d_allow, n_bitmaps, words: self._L.rass_index_aggregate_hits_keys(
+                self._h, _np_ptr(q), nq, _np_ptr(thr), size, d_keys, n_keys, n_groups, top_hits, by, d_allow, n_bitmaps, words,
+                _np_ptr(f), _np_ptr(m), _np_ptr(out_g), _np_ptr(out_c), _np_ptr(out_s), _np_ptr(out_i), _np_ptr(n_buckets),
+                _np_ptr(total)))
+        return out_g, out_c, out_s, out_i, n_buckets, total
+
+    def search_counts_hits_by_keys_device(self, d_queries_ptr: int, nq: int, d_min_score_ptr: int, size: int, d_keys_ptr: int,
+                                          n_keys: int, n_groups: int, top_hits: int, d_out_groups_ptr: int, d_out_counts_ptr: int,
+                                          d_out_scores_ptr: int, d_out_ids_ptr: int, d_n_buckets_ptr: int, d_total_hits_ptr: int,
+                                          d_status_ptr: int, order_by: str = "_count", d_allow_ptr: int = 0, n_bitmaps: int = 0,
+                                          words_per_bitmap: int = 0, id_base: int = 0, d_q_filter_ptr: int = 0,
+                                          d_q_filter_mask_ptr: int = 0) -> None:
+        """Async, device-resident ``search_counts_hits_by_keys`` (``rass_index_aggregate_hits_keys_device``); nq <= 32.
+        Outputs ``[nq, size]`` groups / counts, ``[nq, size, top_hits]`` scores / ids, ``[nq]`` n_buckets / total_hits.
+        Nothing is padded.  ``*d_status`` as in ``search_counts_device``."""
+        size, n_groups, top_hits, by = self._check_counts_hits(size, n_groups, top_hits, order_by)
+        N.check("rass_index_aggregate_hits_keys_device",
+                self._L.rass_index_aggregate_hits_keys_device(
+                    self._h, ctypes.c_void_p(d_queries_ptr), int(nq), ctypes.c_void_p(d_min_score_ptr), size,
+                    ctypes.c_void_p(d_keys_ptr or 0), int(n_keys), n_groups, top_hits, by, ctypes.c_void_p(d_allow_ptr or 0),
+                    int(n_bitmaps), int(words_per_bitmap), ctypes.c_void_p(d_q_filter_ptr or 0),
+                    ctypes.c_void_p(d_q_filter_mask_ptr or 0), int(id_base), ctypes.c_void_p(d_out_groups_ptr),
+                    ctypes.c_void_p(d_out_counts_ptr), ctypes.c_void_p(d_out_scores_ptr), ctypes.c_void_p(d_out_ids_ptr),
+                    ctypes.c_void_p(d_n_buckets_ptr), ctypes.c_void_p(d_total_hits_ptr), ctypes.c_void_p(d_status_ptr)))
+
     # ---- allow-list search: exact top-k within a per-query row bitmap
     @property
     def allow_words(self) -> int:

@@ -466,7 +466,8 @@ class HipIndexer:
 
     def semantic_aggregate(self, query_emb: np.ndarray, min_score: float, by: str = "patientId", size: int = 5,
                            filter_clause: Optional[Dict] = None, patient_id: Optional[str] = None,
-                           interval: Optional[Any] = None, where: Optional[Any] = None) -> Dict[str, Any]:
+                           interval: Optional[Any] = None, where: Optional[Any] = None, top_hits: int = 1,
+                           order: str = "_count") -> Dict[str, Any]:
         """A ``terms`` aggregation on ``by`` (``"patientId"``, ``"doc_type"`` or any attribute field of the index:
         ``conditionCodeText``, ``resourceType``, a date) under the k-NN clause with a ``min_score``:
         how many chunks score at least ``min_score``, of how many distinct values, and the ``size`` values with the most such
@@ -489,6 +490,14 @@ class HipIndexer:
         without the field are not counted; more than 4 096 buckets between the smallest and the largest value raise
         ``ValueError``.
 
+        ``top_hits`` (1 .. 16) and ``order`` (``"_count"`` | ``"max_score"``): OpenSearch's ``top_hits {size: n}``
+        sub-aggregation and ``"order": {"max_score": "desc"}``.  With ``top_hits > 1`` or ``order="max_score"`` every ``by``,
+        ``patientId`` and ``doc_type`` included, goes through a key column built on the GPU and ONE pass keeps the counts and
+        each bucket's best chunks together (``FlatIndex.search_counts_hits_by_keys``; fp32 flat indices with dim <= 1024);
+        each bucket gains ``"top_hits": [(doc_dict, float(score)), ...]`` best first, at most ``top_hits`` of them, and
+        ``"top_hit"`` is the first.  ``"max_score"`` lists the ``size`` buckets with the best chunk instead of those with the
+        most; with ``interval`` it raises ``ValueError`` (a histogram stays in key order).
+
         ``where``: an OpenSearch filter as ``semantic_search_filtered`` takes it (a date range, a ``term``), compiled into
         a bitmap the scan honours (dim <= 1024; the whole index is still streamed).  Filters as ``semantic_search``.  An
         empty embedding or an unindexed patient gives the empty aggregation with zeros; errors raise (this method has no
@@ -496,6 +505,13 @@ class HipIndexer:
         engine)."""
         st: Optional[IndexState] = REGISTRY.get(self.index_name, create=False)
         grp = _GroupBy("by", by, st, interval)
+        if isinstance(top_hits, bool) or not isinstance(top_hits, (int, np.integer)) or not 1 <= int(top_hits) <= 16:
+            raise ValueError(f"top_hits must be an int in [1, 16], not {top_hits!r}")
+        if order not in ("_count", "max_score"):
+            raise ValueError(f"order must be '_count' or 'max_score', not {order!r}")
+        if order == "max_score" and interval is not None:
+            raise ValueError("order='max_score' cannot go with interval=: a histogram stays in key order")
+        with_hits = int(top_hits) > 1 or order == "max_score"
         empty = {"buckets": [], "sum_other_doc_count": 0, "cardinality": 0, "total": 0}
         if _empty(query_emb):
             return empty
@@ -512,11 +528,17 @@ class HipIndexer:
         if np.isnan(thr[0]):
             raise ValueError("min_score must not be NaN")
         flt = dict(q_filter=np.array([fval], dtype=np.int32), q_filter_mask=np.array([fmask], dtype=np.int32)) if fmask else {}
-        if grp.tag_mask is None or where is not None:
+        if with_hits:
+            if not hasattr(st.index, "search_counts_hits_by_keys"):
+                raise NotImplementedError(f"{self.index_name}: {type(st.index).__name__} has no aggregation with top hits "
+                                          "(IVF-backed and sharded indices cannot count per group; use a flat fp32 index)")
+            if int(getattr(st.index, "dim", 0)) > 1024:
+                raise NotImplementedError(f"{self.index_name}: the aggregation with top hits needs dim <= 1024 (no wide-row form)")
+        if with_hits or grp.tag_mask is None or where is not None:
             self._need_keys(st, where, "aggregation")
         for _ in range(LAYOUT_ATTEMPTS):    # top_hit ids belong to one layout of the index, as in _knn
             layout = _layout_epoch(st.index)
-            if grp.tag_mask is not None and where is None:      # the tag path, call for call
+            if grp.tag_mask is not None and where is None and not with_hits:      # the tag path, call for call
                 # codes run 1 .. len, 0 = none; read per attempt: a concurrent ingest may have added a value
                 names = grp.tag_names(st)
                 label = lambda g, names=names: names[g - 1] if g > 0 else None
@@ -532,18 +554,25 @@ class HipIndexer:
                 keys, n_groups, label = keyed
                 # a histogram lists every bucket: the select is asked for all of them and the host puts them in key order
                 ask = n_groups if interval is not None else size_eff
-                groups, counts, scores, ids, n_buckets, totals = st.index.search_counts_by_keys(q, thr, ask, keys, n_groups,
-                                                                                                allow=allow, **flt)
-            listed = [(int(g), int(c), s, i) for g, c, s, i in zip(groups[0], counts[0], scores[0], ids[0]) if g >= 0]
+                if with_hits:       # scores / ids are [1, ask, top_hits]: a bucket's best chunks, best first
+                    groups, counts, scores, ids, n_buckets, totals = st.index.search_counts_hits_by_keys(
+                        q, thr, ask, keys, n_groups, int(top_hits), order, allow=allow, **flt)
+                else:
+                    groups, counts, scores, ids, n_buckets, totals = st.index.search_counts_by_keys(q, thr, ask, keys, n_groups,
+                                                                                                    allow=allow, **flt)
+            listed = [(int(g), int(c), j) for j, (g, c) in enumerate(zip(groups[0], counts[0])) if g >= 0]
             if interval is not None:
                 listed.sort()
             buckets = []
-            for g, c, s, i in listed:
-                top = self._hits(st, [s], [i], 1.0, None, layout)
+            for g, c, j in listed:
+                top = self._hits(st, scores[0, j] if with_hits else [scores[0, j]], ids[0, j] if with_hits else [ids[0, j]],
+                                 1.0, None, layout)
                 if top is None:
                     buckets = None
                     break
                 bucket = {"key": label(g), "doc_count": c, "top_hit": top[0] if top else None}
+                if with_hits:
+                    bucket["top_hits"] = top
                 if interval is not None and grp.kind == "date":
                     bucket["key_as_string"] = _day_date(bucket["key"]).isoformat()
                 buckets.append(bucket)
